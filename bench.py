@@ -12,7 +12,11 @@ Workload (BASELINE.json configs[1]): 4-modal 128^3 patches, base width 32, 4 cla
 0.2, batch 2 per GPU (the nnU-Net BraTS 3d_fullres plan batch), fp32.  N > 1: data-parallel replicas (weak scaling),
 bucketed RCCL all-reduce of the gradients overlapped with the backward pass.  Prints ONE JSON line (rank 0):
 
-  value / ms_per_step    K timed steps, uninstrumented
+  value / ms_per_step    K timed steps, uninstrumented (a plain run sets up, warms up, times the K steps and prints only this)
+  --dump-outputs DIR     after the timed steps: what the last one handed its caller, as DIR/<name>.npy (dump_outputs)
+
+  --full adds every other record (each one its own extra steps, runs or child processes; --no-extras / --no-cpu-baseline
+  leave out parts of it), and for N > 1 the cost of the gradient all-reduce (rccl.allreduce_exposed_ms):
   roofline               the step's dominant kernel, the 1x3x3 conv walk (e2e_conv133_fwd + e2e_conv133_dgrad):
                          HIP-event time of every launch over extra instrumented steps, algorithmic bytes against the
                          HBM peak and live FLOPs (from the DSFF kernel maps) against the fp32 FMA peak
@@ -29,6 +33,7 @@ bucketed RCCL all-reduce of the gradients overlapped with the backward pass.  Pr
   cpu_baseline           the CPU oracle on the same 128^3 patch (B = 1: fwd + loss + bwd), 1 warm-up + up to 3 timed
   parity                 the metric's "Dice vs CPU ref" half: engine vs that oracle on the IDENTICAL patch (the GPU network's
                          weights and masks): Dice of the argmax maps, max |dlogit| per head, loss difference
+  pure_fp32              the headline step with every split-operand kernel switched off (child process)
 """
 import argparse
 import contextlib
@@ -106,6 +111,29 @@ def synthetic_batch(device, patch, batch, seed, cin=CIN, k=K):
     return x.to(device), [t.to(device) for t in targets]
 
 
+DUMP_MAX_ELEMS = 1 << 21       # per array: at most 7 arrays (<= 5 heads, parameters, gradients) x 8 MB stay under 64 MB
+
+
+def dump_outputs(path, outs, loss, named_params, grads):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy -- the logits of every head
+    (logits_<i>, float32), the loss (float64; training step only), the parameters after the optimizer step and their
+    gradients (params / grads: float32, every tensor of net.named_parameters() flattened in that order).  An array of more
+    than DUMP_MAX_ELEMS elements is replaced by the same seeded sample of DUMP_MAX_ELEMS of its elements in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"logits_%d" % i: o for i, o in enumerate(outs if isinstance(outs, (list, tuple)) else [outs])}
+    if loss is not None:
+        arrays["loss"] = loss.double()
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for _, p in named_params])
+        arrays["grads"] = torch.cat([grads[n].reshape(-1) for n, _ in named_params])
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(1234).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if name == "loss" else np.float32, copy=False))
+
+
 class KernelTimer:
     """HIP-event timing of one C-ABI entry point on the stream it is launched on (torch's current stream)."""
 
@@ -146,7 +174,7 @@ def collect_live_traffic():
     env.pop("WORLD_SIZE", None)
     for sub, ctr in (("pmc_fetch", "FETCH_SIZE"), ("pmc_write", "WRITE_SIZE")):
         cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", os.path.join(root, sub), "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+               os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"]
         r = subprocess.run(cmd, env=env, cwd="/tmp", capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             sys.stderr.write("bench.py --live-traffic: %s pass failed (rc %d): %s\n" % (ctr, r.returncode, r.stderr[-400:]))
@@ -313,7 +341,8 @@ def pure_fp32_record(steps=6, warmup=2):
     import subprocess
     env = dict(os.environ, **PURE_FP32_ENV)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--no-extras", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-extras",
+           "--no-cpu-baseline"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -605,9 +634,10 @@ def dry_rank(args, rank, world, json_fd):
     if rank == 0:
         rec = {"metric": "dry run of the launcher (no GPU work)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "rccl": {"backend": "gloo", "world": dist.get_world_size(), "allreduce_of_ones": float(ones.item()),
-                        "device_per_rank": list(range(world)),
-                        "ms_per_step_without_allreduce": 0.0, "allreduce_exposed_ms": 0.0, "allreduce_bytes_per_step": 0},
+                        "device_per_rank": list(range(world))},
                "ms_per_step_per_rank": [float(t.item()) for t in per_rank]}
+        if args.full:
+            rec["rccl"].update(ms_per_step_without_allreduce=0.0, allreduce_exposed_ms=0.0, allreduce_bytes_per_step=0)
         os.write(json_fd, (json.dumps(rec) + "\n").encode())
     dist.barrier()
     dist.destroy_process_group()
@@ -623,13 +653,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--patch", type=int, default=128)
     ap.add_argument("--batch", type=int, default=BATCH)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward_only / sliding_window / dsff_update sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other record (roofline, sub-workloads, CPU baseline, parity, pure_fp32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline / parity records")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the forward_only / sliding_window / dsff_update / config / pure_fp32 sub-records")
     ap.add_argument("--forward-only", action="store_true", help="time the inference forward as the main loop (diagnostic)")
-    ap.add_argument("--op-profile", action="store_true", help="print per-entry-point GPU time (diagnostic)")
+    ap.add_argument("--op-profile", action="store_true", help="with --full: print per-entry-point GPU time (diagnostic)")
     ap.add_argument("--live-traffic", action="store_true",
-                    help="collect roofline.traffic in this run (two rocprofv3 --pmc child passes first; N = 1 only; adds ~2 minutes)")
+                    help="with --full: collect roofline.traffic in this run (two rocprofv3 --pmc child passes first; N = 1 only; "
+                         "adds ~2 minutes)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.op_profile or args.live_traffic) and not args.full:
+        ap.error("--op-profile and --live-traffic report on the instrumented steps of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))           # before anything touches a GPU
@@ -670,14 +709,15 @@ def main():
     ds_w = np.array([8, 4, 2, 1, 0], dtype=np.float64) / 15.0
     overlap = None
     sample = None
+    last = {"outs": None, "loss": None}          # what the latest step handed its caller (--dump-outputs)
 
     def train_step():
         nonlocal overlap
-        eng.forward(x, True)
+        last["outs"] = eng.forward(x, True)
         if use_dist and overlap is None:
             eng.prepare_backward()
             overlap = parallel.OverlappedGradAllReduce(eng, force=force_dist)   # bucketed all-reduce under the backward pass
-        loss = eng.loss_backward(targets, ds_w, batch_dice=False)
+        loss = last["loss"] = eng.loss_backward(targets, ds_w, batch_dice=False)
         if use_dist:
             overlap.finish()
         fused.step(eng.grads, mask.masks)
@@ -686,7 +726,7 @@ def main():
 
     def fwd_step():
         with torch.no_grad():
-            eng.forward(x, False)
+            last["outs"] = eng.forward(x, False)
 
     step = fwd_step if args.forward_only else train_step
     L = lib()
@@ -707,9 +747,13 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    kernel_clock(L, 0), kernel_clock(L, 1)                       # reset: the clocks below are those of the timed steps
+    if args.full:
+        kernel_clock(L, 0), kernel_clock(L, 1)                   # reset: the clocks below are those of the timed steps
     dt = timed(step, args.steps)
-    clk_mm, clk_wg = kernel_clock(L, 0), kernel_clock(L, 1)       # (outside the timed region)
+    if args.full:
+        clk_mm, clk_wg = kernel_clock(L, 0), kernel_clock(L, 1)   # (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["outs"], last["loss"], list(net.named_parameters()), eng.grads)
     rccl = per_rank_ms = None
     if use_dist:
         mine = torch.tensor([dt], dtype=torch.float64, device=device)
@@ -727,7 +771,7 @@ def main():
         assert rccl["allreduce_of_ones"] == float(world), "RCCL all-reduce of ones gave %r on %d ranks" % (rccl["allreduce_of_ones"], world)
         if torch.cuda.device_count() >= world:
             assert len(set(rccl["device_per_rank"])) == world, "ranks share a GPU: %r" % (rccl["device_per_rank"],)
-        if not args.forward_only:
+        if args.full and not args.forward_only:
             # what the gradient all-reduce costs the step: the same steps with the bucket hook off (every rank trains alone; no
             # collective inside the step), MAX over ranks like the headline; exposed = step with the overlapped all-reduce - that
             hook, eng.grad_bucket_hook = eng.grad_bucket_hook, None
@@ -749,33 +793,34 @@ def main():
             rccl["allreduce_exposed_ms"] = dt / args.steps * 1e3 - ms_local
             rccl["allreduce_bytes_per_step"] = int(eng.grad_flat.numel()) * 4
 
-    # ---- instrumented steps (outside the timed region): HIP events around the conv entry points --------------------
-    # (_splitk: the deep levels' forward / data gradient, same kernel + a sum kernel; _dense: the unmasked layers on the matrix cores)
-    names = ["conv133_fwd", "conv133_fwd_splitk", "conv133_fwd_dense", "conv133_fwd_sparse", "conv133_fwd_mm", "conv133_dgrad", "conv133_dgrad_splitk",
-             "conv133_dgrad_dense", "conv133_dgrad_sparse", "conv133_dgrad_mm", "conv133_sparse_pack", "conv133_mm_pack",
-             "conv133_input_ranges", "conv133_wgrad"]
-    if args.op_profile:
-        names += ["in_stats_finalize", "in_lrelu_bwd", "convT_fwd", "convT_dgrad", "convT_wgrad", "maxpool_fwd", "maxpool_bwd",
-                  "head1x1_fwd", "head1x1_dgrad", "head1x1_wgrad", "dc_ce_reduce", "dc_ce_grad", "grad_sqnorm", "sgd_clip_mask_step"]
-    timers = {n: KernelTimer(L, n) for n in names}
-    isteps = max(1, min(args.steps, 5))
-    # the timed steps above overlap the deep levels and the weight gradients with the full-resolution kernels on extra HIP
-    # streams; a pair of events around a launch only brackets THAT kernel when nothing else shares the device, so the
-    # instrumented steps issue everything on one stream (the kernels and their inputs are the same)
-    from e2enet_medical_amd import engine as _engine
-    conc = (_engine.LANES, _engine.WGRAD_STREAM)
-    _engine.LANES = _engine.WGRAD_STREAM = False
-    for t in timers.values():
-        t.enabled = True
-    for _ in range(isteps):
-        step()
-    torch.cuda.synchronize()
-    for t in timers.values():
-        t.enabled = False
-    _engine.LANES, _engine.WGRAD_STREAM = conc
+    if args.full:
+        # ---- instrumented steps (outside the timed region): HIP events around the conv entry points --------------------
+        # (_splitk: the deep levels' forward / data gradient, same kernel + a sum kernel; _dense: the unmasked layers on the matrix cores)
+        names = ["conv133_fwd", "conv133_fwd_splitk", "conv133_fwd_dense", "conv133_fwd_sparse", "conv133_fwd_mm", "conv133_dgrad", "conv133_dgrad_splitk",
+                 "conv133_dgrad_dense", "conv133_dgrad_sparse", "conv133_dgrad_mm", "conv133_sparse_pack", "conv133_mm_pack",
+                 "conv133_input_ranges", "conv133_wgrad"]
+        if args.op_profile:
+            names += ["in_stats_finalize", "in_lrelu_bwd", "convT_fwd", "convT_dgrad", "convT_wgrad", "maxpool_fwd", "maxpool_bwd",
+                      "head1x1_fwd", "head1x1_dgrad", "head1x1_wgrad", "dc_ce_reduce", "dc_ce_grad", "grad_sqnorm", "sgd_clip_mask_step"]
+        timers = {n: KernelTimer(L, n) for n in names}
+        isteps = max(1, min(args.steps, 5))
+        # the timed steps above overlap the deep levels and the weight gradients with the full-resolution kernels on extra HIP
+        # streams; a pair of events around a launch only brackets THAT kernel when nothing else shares the device, so the
+        # instrumented steps issue everything on one stream (the kernels and their inputs are the same)
+        from e2enet_medical_amd import engine as _engine
+        conc = (_engine.LANES, _engine.WGRAD_STREAM)
+        _engine.LANES = _engine.WGRAD_STREAM = False
+        for t in timers.values():
+            t.enabled = True
+        for _ in range(isteps):
+            step()
+        torch.cuda.synchronize()
+        for t in timers.values():
+            t.enabled = False
+        _engine.LANES, _engine.WGRAD_STREAM = conc
 
     sw_multi = None
-    if world > 1 and not args.no_extras and not args.forward_only:
+    if world > 1 and args.full and not args.no_extras and not args.forward_only:
         # the north_star's multi-GPU path: tile-sharded sliding-window inference with RCCL all-gather (every rank takes part)
         sw_multi = sliding_window_record(device, rank, world)
 
@@ -800,6 +845,7 @@ def main():
         }
         if args.forward_only:
             out["metric"] = "voxels/sec (inference forward only), 128^3 patch 32ch density=0.2"
+    if rank == 0 and args.full:
         work = conv_work(eng, mask)
         ev = [(e0.elapsed_time(e1), work[a[0]]) for e0, e1, a in timers["conv133_fwd"].events + timers["conv133_fwd_splitk"].events +
               timers["conv133_fwd_dense"].events + timers["conv133_fwd_sparse"].events + timers["conv133_fwd_mm"].events]
@@ -915,6 +961,7 @@ def main():
                 out["parity"]["config1_engine_vs_cpu"] = out["parity"]["config1"]["config1_engine_vs_cpu"]
         if world == 1 and not args.no_extras and not args.forward_only and not any(os.environ.get(k) == v for k, v in PURE_FP32_ENV.items()):
             out["pure_fp32"] = pure_fp32_record()
+    if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if use_dist:
         dist.barrier()

@@ -49,8 +49,17 @@ def test_module_tree_and_init_match_reference_bit_for_bit(tag, args):
     assert list(sd.keys()) == [str(s) for s in g[tag + "_names"]]
     assert [str(tuple(v.shape)) for v in sd.values()] == [str(s) for s in g[tag + "_shapes"]]
     assert [n for n, _ in net.named_parameters()] == [str(s) for s in g[tag + "_param_order"]]
-    assert np.array_equal(np.array([v.double().sum().item() for v in sd.values()]), g[tag + "_sum"])
-    assert np.array_equal(np.array([v.double().abs().sum().item() for v in sd.values()]), g[tag + "_abs"])
+    # the checksums are torch sums: their reduction order follows the thread count, so they are taken with the 8 threads the
+    # golden sums were taken with (the weights themselves do not depend on it)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        sums = np.array([v.double().sum().item() for v in sd.values()])
+        abs_sums = np.array([v.double().abs().sum().item() for v in sd.values()])
+    finally:
+        torch.set_num_threads(threads)
+    assert np.array_equal(sums, g[tag + "_sum"])
+    assert np.array_equal(abs_sums, g[tag + "_abs"])
 
 
 def test_network_attributes_and_errors():
@@ -496,7 +505,7 @@ def test_bench_self_launches_n_ranks_without_torchrun():
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment (the form the driver uses): the parent starts two
     children, one rank each, and relays exactly one JSON line from rank 0 (dry mode: gloo, no GPU work)."""
     import json
-    r = _bench({"E2E_BENCH_DRY": "1"}, "--gpus", "2", "--steps", "4", "--warmup", "1")
+    r = _bench({"E2E_BENCH_DRY": "1"}, "--gpus", "2", "--steps", "4", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -505,6 +514,49 @@ def test_bench_self_launches_n_ranks_without_torchrun():
     assert rec["rccl"]["world"] == 2 and rec["rccl"]["allreduce_of_ones"] == 2.0
     assert {"ms_per_step_without_allreduce", "allreduce_exposed_ms", "allreduce_bytes_per_step", "device_per_rank"} <= set(rec["rccl"])   # the N > 1 record
     assert rec["ms_per_step_per_rank"] == [1.0, 2.0]                  # rank r contributed r + 1: both ranks were in the group
+
+
+def test_bench_plain_run_leaves_the_other_records_to_full():
+    """A run without --full measures the headline only: no all-reduce cost steps for N > 1 (dry mode), and the options that
+    report on the instrumented steps of --full are refused without it."""
+    import json
+    r = _bench({"E2E_BENCH_DRY": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert rec["steps"] == 3 and rec["rccl"]["allreduce_of_ones"] == 2.0
+    assert not {"ms_per_step_without_allreduce", "allreduce_exposed_ms", "allreduce_bytes_per_step"} & set(rec["rccl"])
+    for flag in ("--op-profile", "--live-traffic"):
+        r = _bench({"E2E_BENCH_DRY": "1"}, "--steps", "2", flag)
+        assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: every head, the loss, the parameters and their gradients as .npy (float32, loss float64); an array
+    larger than DUMP_MAX_ELEMS becomes the same seeded sample in every run (parameters and gradients at the same indices)."""
+    import bench
+    n = bench.DUMP_MAX_ELEMS
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randn(2, 4, n // 4 + 8, generator=g), torch.randn(2, 4, 8, 8, generator=g)]
+    named = [("a.weight", torch.randn(n, generator=g)), ("b.bias", torch.randn(9, generator=g))]
+    grads = {nm: p * 2.0 for nm, p in named}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), outs, torch.tensor(0.25), named, grads)
+    names = sorted(os.listdir(tmp_path / "one"))
+    assert names == ["grads.npy", "logits_0.npy", "logits_1.npy", "loss.npy", "params.npy"]
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / "one" / nm), np.load(tmp_path / "two" / nm)
+        assert a.dtype == (np.float64 if nm == "loss.npy" else np.float32) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "one" / "logits_0.npy").shape == (n,)                        # sampled
+    assert np.array_equal(np.load(tmp_path / "one" / "logits_1.npy"), outs[1].numpy())     # kept whole
+    p, gr = np.load(tmp_path / "one" / "params.npy"), np.load(tmp_path / "one" / "grads.npy")
+    assert p.shape == (n,) and np.array_equal(gr, 2.0 * p)
+    assert np.isin(p, torch.cat([t.reshape(-1) for _, t in named]).numpy()).all()
+    assert float(np.load(tmp_path / "one" / "loss.npy")) == 0.25
+    bench.dump_outputs(str(tmp_path / "fwd"), outs[1], None, named, grads)                  # --forward-only: the logits alone
+    assert sorted(os.listdir(tmp_path / "fwd")) == ["logits_0.npy"]
 
 
 def test_bench_launcher_propagates_a_failed_rank_and_refuses_a_mismatched_world():
@@ -657,6 +709,7 @@ def test_trainer_never_trains_on_noise_by_accident_and_splits_like_sklearn(tmp_p
     tr2.setup_DA_params()
     assert tr2.data_aug_params["dummy_2D"] and tr2.data_aug_params["rotation_x"][1] == pytest.approx(np.pi)
     assert tr2.basic_generator_patch_size[0] == 16 and tr2.basic_generator_patch_size[1] > 64 and tr2.basic_generator_patch_size[2] > 64
+    tr.load_plans_file()                       # (initialize() above loaded them only where no GPU made it raise first)
     tr.process_plans(tr.plans)
     tr.setup_DA_params()
     assert not tr.data_aug_params["dummy_2D"] and all(b >= p for b, p in zip(tr.basic_generator_patch_size, tr.patch_size))

@@ -6,8 +6,8 @@ O=gpurun_out/r05_atomic; mkdir -p $O
 timeout 1200 python -m pytest tests/test_gpu_ops.py tests/test_gpu_configs.py -m gpu -q -x --tb=short -k "conv133 or config5 or width48 or whole_net_fixed or config3" 2>&1 | grep -v "curr_density\|amdgpu.ids" | tail -15 > $O/tests.txt
 RMW=$PWD/e2enet_medical_amd/csrc/libe2e_hip_rmw.so
 for rep in 1 2; do
-  python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/atomic_$rep.json 2> /dev/null
-  E2E_LIB_PATH=$RMW python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/rmw_$rep.json 2> /dev/null
+  python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/atomic_$rep.json 2> /dev/null
+  E2E_LIB_PATH=$RMW python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/rmw_$rep.json 2> /dev/null
 done
 python - <<'PY' > gpurun_out/r05_atomic/summary.txt
 import json, glob

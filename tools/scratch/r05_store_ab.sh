@@ -9,8 +9,8 @@ for rep in 1 2 3; do
 done
 } > $O/kbench.txt 2>&1
 for rep in 1 2; do
-  E2E_LIB_PATH=$A python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/dword_$rep.json 2> /dev/null
-  python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/x4_$rep.json 2> /dev/null
+  E2E_LIB_PATH=$A python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/dword_$rep.json 2> /dev/null
+  python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/x4_$rep.json 2> /dev/null
 done
 python - <<'PY' > gpurun_out/r05_store/summary.txt
 import json, glob
