@@ -19,6 +19,7 @@
 //   * epilogue (fwd): bias, store, per-tile (count, mean, M2) partial for InstanceNorm;
 //     epilogue (dgrad): un-shift on store into the per-channel destination (scatter back through the concat).
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 #include <cstdio>
 #include <type_traits>
@@ -38,6 +39,8 @@ __device__ unsigned long long g_conv_stamps[1024 * 8];
 #endif
 
 namespace {
+
+using namespace e2e;
 
 struct ConvParams {
   const e2e_in_chan_t* chans;   // P input planes (null: plain tensor `xin`, used by the data gradient)
@@ -137,20 +140,6 @@ __device__ __forceinline__ void load_row(const float* __restrict__ src, float* _
 #pragma unroll
   for (; c < NC; ++c) dst[c] = src[c];
 }
-
-// wave-uniform read-only operands (liveness words, bias, destination descriptors) go through the scalar cache: a vector
-// load of them would sit in the same vmcnt queue as the staged planes and make the wave wait for those too
-template <class T>
-__device__ __forceinline__ T load_uniform(const T* ptr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *reinterpret_cast<const T __attribute__((address_space(4)))*>((unsigned long long)ptr);
-#else
-  return *ptr;
-#endif
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef const f32x4_t __attribute__((address_space(1)))* gfloat4_p;
 
 template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW, int PIPE, int PERSIST>
 __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
@@ -366,7 +355,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
         pd_ok[j] = pl < p.P && __builtin_amdgcn_readfirstlane(ds.valid) != 0;
         if (pd_ok[j]) {
 #pragma unroll
-          for (int i = 0; i < NUP; ++i) v4[j][i] = *reinterpret_cast<gfloat4_p>(base + (unsigned)su_goff[i]);
+          for (int i = 0; i < NUP; ++i) v4[j][i] = *reinterpret_cast<gf4_p>(base + (unsigned)su_goff[i]);
         }
       }
     } else {
@@ -416,7 +405,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
         const char __attribute__((address_space(1)))* base =
             (const char __attribute__((address_space(1)))*)(((unsigned long long)pf_bhi << 32) | pf_blo);
         const unsigned off = live && pd_ok[0] ? (unsigned)su_goff[k] : 0u;      // (plane bases are always dereferenceable)
-        v4[0][k] = *reinterpret_cast<gfloat4_p>(base + off);
+        v4[0][k] = *reinterpret_cast<gf4_p>(base + off);
       } else if (k < NSTEP) {
         const int i = k - NUP;
         const unsigned off = WRND ? wu_off[0] + pf_coff + (unsigned)(i * QPR * p.wq_stride) * 4u : wu_off[WRND ? 0 : i] + pf_coff;

@@ -30,6 +30,7 @@
 // Shapes: stride (1,1,1), Cin <= 128 (the LDS table), W % 32 == 0, H % 16 == 0, H > 16 (the patch sizes of the BASELINE configs at the levels this kernel is
 // dispatched for); everything else stays on conv133_kernel.
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 
 #ifndef DENSE_DIAG
@@ -38,12 +39,9 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+using namespace e2e;
+
 typedef const u32x4_t __attribute__((address_space(1)))* gu4_p;
-typedef const f32x4_t __attribute__((address_space(1)))* gf4_p;
 
 constexpr int SUBH = 8, TW = 32, XR = SUBH + 2, XC = TW + 2;
 constexpr int PXB = 48;                          // bytes per staged pixel and piece: 16 channels bf16 + 16 (odd multiple of 16)
@@ -71,23 +69,6 @@ struct DenseParams {
   int nchunks, qblocks, tiles_x, tiles_y, tiles_per_n, total, padded_total;
 };
 
-template <class T>
-__device__ __forceinline__ T load_uniform(const T* ptr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *reinterpret_cast<const T __attribute__((address_space(4)))*>((unsigned long long)ptr);
-#else
-  return *ptr;
-#endif
-}
-
-__device__ __forceinline__ void split1(float v, unsigned& h, unsigned& m, unsigned& l) {
-  h = __builtin_bit_cast(unsigned, v);
-  const float r1 = v - __builtin_bit_cast(float, h & 0xffff0000u);            // exact
-  m = __builtin_bit_cast(unsigned, r1);
-  const float r2 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);           // exact, <= 8 significant bits
-  l = __builtin_bit_cast(unsigned, r2);
-}
-
 // ---- weights: fp32 [Q][P][9] (strides wq, wp; reversed taps for the data gradient) -> packed three-piece bf16 -------------------
 // `quads` (null = dense layer): the DSFF liveness quad words of this direction, word [q / 4][p / 8], bit (p % 8) * 4 + q % 4
 // (e2e_dsff_expand_quads).  A pruned (q, p) kernel is packed as zeros: the matrix-pipe kernel multiplies whole tiles, and its
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(256) void pack_weights_bf3_kernel(const float* __re
     if (alive) v = w[(long long)q * wq_stride + (long long)pp * wp_stride + (reverse ? 8 - tap : tap)];
   }
   unsigned h, m, l;
-  split1(v, h, m, l);
+  split_bf3(v, h, m, l);
   // the two 8-channel halves of rows 16..31 are swapped: with lane -> (row fq = lane & 31, half lane >> 5) fixed by the MFMA
   // operand layout, the 16 lanes of a ds_read_b128 group then fall on 16 distinct bank quads of the 32-byte rows
   const long long base = ((((long long)qb * nchunks + ch) * 9 + tap) * 3) * 512 + ql * 16 + (k ^ ((ql >> 4) << 3));
@@ -212,16 +193,12 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
         }
         v = (((pvalid >> j) & 1u) && inside) ? v : 0.f;
         if (DENSE_DIAG == 3) { hh[j] = mm[j] = ll[j] = __builtin_bit_cast(unsigned, v); }
-        else split1(v, hh[j], mm[j], ll[j]);
+        else split_bf3(v, hh[j], mm[j], ll[j]);
       }
       unsigned char* dst = lds + (s_pix0 + k) * PXB + shalf * 16;
-      // v_perm_b32 0x07060302: (S1 >> 16) | (S0 & 0xffff0000): two bf16 pieces per word, element 0 in the low half
-      *reinterpret_cast<u32x4_t*>(dst) = u32x4_t{__builtin_amdgcn_perm(hh[1], hh[0], 0x07060302u), __builtin_amdgcn_perm(hh[3], hh[2], 0x07060302u),
-                                                 __builtin_amdgcn_perm(hh[5], hh[4], 0x07060302u), __builtin_amdgcn_perm(hh[7], hh[6], 0x07060302u)};
-      *reinterpret_cast<u32x4_t*>(dst + SPL) = u32x4_t{__builtin_amdgcn_perm(mm[1], mm[0], 0x07060302u), __builtin_amdgcn_perm(mm[3], mm[2], 0x07060302u),
-                                                       __builtin_amdgcn_perm(mm[5], mm[4], 0x07060302u), __builtin_amdgcn_perm(mm[7], mm[6], 0x07060302u)};
-      *reinterpret_cast<u32x4_t*>(dst + 2 * SPL) = u32x4_t{__builtin_amdgcn_perm(ll[1], ll[0], 0x07060302u), __builtin_amdgcn_perm(ll[3], ll[2], 0x07060302u),
-                                                           __builtin_amdgcn_perm(ll[5], ll[4], 0x07060302u), __builtin_amdgcn_perm(ll[7], ll[6], 0x07060302u)};
+      *reinterpret_cast<u32x4_t*>(dst) = u32x4_t{pack_hi16(hh[0], hh[1]), pack_hi16(hh[2], hh[3]), pack_hi16(hh[4], hh[5]), pack_hi16(hh[6], hh[7])};
+      *reinterpret_cast<u32x4_t*>(dst + SPL) = u32x4_t{pack_hi16(mm[0], mm[1]), pack_hi16(mm[2], mm[3]), pack_hi16(mm[4], mm[5]), pack_hi16(mm[6], mm[7])};
+      *reinterpret_cast<u32x4_t*>(dst + 2 * SPL) = u32x4_t{pack_hi16(ll[0], ll[1]), pack_hi16(ll[2], ll[3]), pack_hi16(ll[4], ll[5]), pack_hi16(ll[6], ll[7])};
     }
   };
 
@@ -229,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
   // weight fragment (B operand): out channel fq, channels 8 fh8 .. + 7 of the chunk, from the LDS copy of the chunk's packed
   // weights (all four waves use the same fragments; straight from global each wave waited for L2 at every tap)
   const unsigned char* const wfbase = wlds + fq * 32 + ((fh8 ^ (fq >> 4)) << 4);
-  auto wfrag = [&](int tap, int s) -> bf16x8 { return *reinterpret_cast<const bf16x8*>(wfbase + (tap * 3 + s) * 1024); };
+  auto wfrag = [&](int tap, int s) -> bf16x8_t { return *reinterpret_cast<const bf16x8_t*>(wfbase + (tap * 3 + s) * 1024); };
   u32x4_t vw[WRND];
   auto prefetch_w = [&](int c) {
     const unsigned char* src = reinterpret_cast<const unsigned char*>(p.wpk) + ((long long)qb * p.nchunks + c) * WBYTES;
@@ -272,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
   }
   prefetch_x(0);
   for (int sub = 0; sub < 2; ++sub) {
-    f32x16 acc[2];
+    f32x16_t acc[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -284,16 +261,16 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
       STAMP();
       __syncthreads();
       STAMP();
-      bf16x8 wb[2][3];                                    // ring over taps: [tap & 1][piece]
+      bf16x8_t wb[2][3];                                  // ring over taps: [tap & 1][piece]
 #pragma unroll
       for (int s = 0; s < 3; ++s) wb[0][s] = wfrag(0, s);
       // A fragment: pixel (row 2 wave + r + kh, column fq + kw), channels 8 fh8 .. + 7.  The 18 (tap, row) steps are software
       // pipelined: the three pieces of step i + 1 are read from LDS before the six matrix instructions of step i are issued
       // (two waves per SIMD do not hide a ds_read -> mfma dependency by themselves).
       const unsigned char* abase = lds + ((2 * wave) * XC + fq) * PXB + fh8 * 16;
-      bf16x8 af[2][3];
+      bf16x8_t af[2][3];
 #pragma unroll
-      for (int s = 0; s < 3; ++s) af[0][s] = *reinterpret_cast<const bf16x8*>(abase + s * SPL);
+      for (int s = 0; s < 3; ++s) af[0][s] = *reinterpret_cast<const bf16x8_t*>(abase + s * SPL);
 #pragma unroll
       for (int step = 0; step < (DENSE_DIAG == 1 ? 1 : 18); ++step) {
         const int tap = step >> 1, r = step & 1;
@@ -310,9 +287,9 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
           const int nt = (step + 1) >> 1, nr = (step + 1) & 1;
 #pragma unroll
           for (int s = 0; s < 3; ++s)
-            af[(step + 1) & 1][s] = *reinterpret_cast<const bf16x8*>(abase + ((nr + nt / 3) * XC + nt % 3) * PXB + s * SPL);
+            af[(step + 1) & 1][s] = *reinterpret_cast<const bf16x8_t*>(abase + ((nr + nt / 3) * XC + nt % 3) * PXB + s * SPL);
         }
-        f32x16 a = acc[r];
+        f32x16_t a = acc[r];
         // small terms first: lo*hi, mid*mid, hi*lo, then mid*hi, hi*mid, then hi*hi
         a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[step & 1][2], wb[tap & 1][0], a, 0, 0, 0);
         a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[step & 1][1], wb[tap & 1][1], a, 0, 0, 0);

@@ -14,14 +14,12 @@
 // GEMM per tap: D[out channel][pixel] += W[out channel][16 in] x X[16 in][pixel] -- the WEIGHTS are the A operand, 32 pixels of a
 // tile row the B operand (v_mfma_f32_32x32x16_f16): an accumulator register of a lane is one out channel at 32 consecutive pixels
 // across the lanes, so the epilogue stores whole 128-byte lines without a transposition and the InstanceNorm sums of an out channel
-// are DPP row reductions (row_bcast:15 + v_readlane).  x = hi + lo (hi = rn16(x), lo = rn16(x - hi), 11 + 11 significant bits),
-// every operand moved into the fp16 range by an exact power of two before it is split: the weights by the 2^k that puts max |w| of
-// the tensor in [2^14, 2^15) (recorded by the packing launch), the activations by the 2^k derived from a BOUND of |x| over all input
-// planes of the launch (e2e_conv133_input_ranges: |gamma| sqrt(N - 1) + |beta| for a normalised source -- round 6; until round 5 a
-// fixed 2^3, which turned |x| > 8188 into Inf); product = lo_w hi_x + hi_w lo_x + hi_w hi_x, accumulated in fp32, un-scaled on store.  The data gradient runs the
-// same kernel on dy (pre-scaled by the power of two that puts max |dy|, recorded by e2e_in_lrelu_bwd, in [2^14, 2^15)) with
-// transposed, tap-reversed weights; its destinations (un-shift on store, accumulate or overwrite) are resolved per item into LDS
-// records by the staging waves.
+// are DPP row reductions (row_bcast:15 + v_readlane).  Operands in the fp16 two-piece form of e2e_split.h, scaled before the split:
+// the weights by max |w| of the tensor (recorded by the packing launch), the activations by a BOUND of |x| over all input planes of
+// the launch (e2e_conv133_input_ranges: |gamma| sqrt(N - 1) + |beta| for a normalised source); product = hi_w lo_x + lo_w hi_x +
+// hi_w hi_x in that order, accumulated in fp32, un-scaled on store.  The data gradient runs the same kernel on dy (scaled by max
+// |dy|, recorded by e2e_in_lrelu_bwd) with transposed, tap-reversed weights; its destinations (un-shift on store, accumulate or
+// overwrite) are resolved per item into LDS records by the staging waves.
 //
 // Workgroup = 8 waves = 4 matrix waves + 4 staging waves (two per SIMD; the streams of different waves of a SIMD overlap,
 // tools/scratch/mfma_overlap.hip), PERSISTENT: one workgroup per CU walks the items (a 512-pixel tile of one depth slice x 32 out
@@ -39,6 +37,7 @@
 //
 // Shapes: stride (1,1,1), W % 32 == 0, H % 16 == 0, more than 16 channels on the reduction side, at most CT_MAX.
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -58,13 +57,7 @@ __device__ unsigned long long g_mm_stamps[16];   // staging: [0] dma [1] ctab [2
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef const f32x4_t __attribute__((address_space(1)))* gf4_p;
+using namespace e2e;
 
 // Tile geometries (all 512 output pixels per item, so the items of a depth slice and the InstanceNorm partial records of
 // conv133_kernel's 16 x 32 tile class are the same in number):
@@ -98,16 +91,6 @@ constexpr int WTAP = 32 * 32;                    // one (tap, piece) block: 32 o
 constexpr int WCH = 9 * 2 * WTAP;                // one chunk of packed weights: 18 432 B
 constexpr int WUNITS = WCH / 16;                 // 1152 16-byte units
 constexpr int WSH = 8;                           // weights are packed as w 2^WSH when no max |w| word is given (|w| < 256)
-constexpr int XSH = 3;                           // forward without a range word: activations are staged as x 2^XSH (lo piece normal down to |x| = 2^-6; Inf beyond 8188)
-// the power of two that moves a tensor whose max |v| has the bit pattern `word` into [2^14, 2^15): k = 141 - E (E the biased exponent;
-// zero / denormal max: E = 1; Inf / NaN propagate), clamped so that 2^k and 2^-k are normal numbers
-__host__ __device__ inline int scale_exp(unsigned word, int lim) {
-  int E = (int)((word >> 23) & 0xffu);
-  E = E < 1 ? 1 : E;
-  int k = 141 - E;
-  return k > lim ? lim : (k < -lim ? -lim : k);
-}
-__device__ __forceinline__ float pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
 template <int GEOM> constexpr int lds_bytes() {
   return 2 * Geo<GEOM>::IMG + 2 * WCH + 2 * Geo<GEOM>::CT_MAX * 20 + Geo<GEOM>::LREC_MAX * 24 + 2 * 4 * 32 * 2 * 4 + (Geo<GEOM>::CT_MAX + 32) * 4;
 }
@@ -191,9 +174,9 @@ __global__ __launch_bounds__(256) void pack_weights_h2_kernel(const e2e_mm_pack_
     const bool alive = jb.quads == nullptr || ((jb.quads[(long long)(q >> 2) * ((P + 7) >> 3) + (pp >> 3)] >> (((pp & 7) << 2) + (q & 3))) & 1u);
     if (alive) v = jb.w[(long long)q * jb.wq_stride + (long long)pp * jb.wp_stride + (jb.reverse ? 8 - tap : tap)];
   }
-  v *= pow2f(jb.w_absmax != nullptr ? scale_exp(*jb.w_absmax, 60) : WSH);
-  const _Float16 h = (_Float16)v;
-  const _Float16 l = (_Float16)(v - (float)h);
+  v *= pow2f(jb.w_absmax != nullptr ? scale_exp<LIM_W>(*jb.w_absmax) : WSH);
+  _Float16 h, l;
+  split_f16_cvt_sub(v, h, l);
   // 32-byte rows; the two 16-byte halves of rows with bit 3 set are swapped (conflict-free ds_read_b128 fragments)
   unsigned short* wpk = reinterpret_cast<unsigned short*>(jb.wpk);
   const long long base = ((((long long)qb * nchunks + ch) * 9 + tap) * 2) * 512 + ql * 16 + (k ^ (((ql >> 3) & 1) << 3));
@@ -260,8 +243,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // operand scales: xsc = 2^kx moves the reduction-side planes (forward: the activations after normalise-on-load, bound by
   // *x_absmax; data gradient: dy, max |dy| recorded by e2e_in_lrelu_bwd) into the fp16 range, the weights were packed as w 2^kw;
   // the accumulators are un-scaled by the two exact factors 2^-kw and 2^-kx (two: the sum of the exponents may leave the fp32 range)
-  const int kx = p.x_absmax != nullptr ? scale_exp(__builtin_nontemporal_load(p.x_absmax), 110) : (MODE == 0 ? XSH : 0);
-  const int kw = p.w_absmax != nullptr ? scale_exp(__builtin_nontemporal_load(p.w_absmax), 60) : WSH;
+  const int kx = p.x_absmax != nullptr ? scale_exp<LIM_X>(__builtin_nontemporal_load(p.x_absmax)) : (MODE == 0 ? XSH : 0);
+  const int kw = p.w_absmax != nullptr ? scale_exp<LIM_W>(__builtin_nontemporal_load(p.w_absmax)) : WSH;
   const float xsc = pow2f(kx), unsc_w = pow2f(-kw), unsc = pow2f(-kx);
 
   // channel table of an item: plane pointer (batch item, shifted depth) and normalise-on-load coefficients per reduction-side
@@ -490,13 +473,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             if (MM_DIAG & 4) { hv[j] = __builtin_bit_cast(unsigned, t[2 * j]); lv[j] = __builtin_bit_cast(unsigned, t[2 * j + 1]); continue; }
-            // hi = rn16(t) (one v_cvt_pk_f16_f32 per pair), lo = rn16(t - hi) as ONE mixed-precision FMA per value: fma(hi as f16, -1, t)
-            // is exact in fp32 and rounded to fp16 into the low / high half of the destination (3 instead of 7 instructions per pair)
-            const f16x2_t h2 = __builtin_convertvector((f32x2_t{t[2 * j], t[2 * j + 1]}), f16x2_t);
-            hv[j] = __builtin_bit_cast(unsigned, h2);
-            unsigned lw;
-            asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                : "=&v"(lw) : "v"(hv[j]), "v"(t[2 * j]), "v"(t[2 * j + 1]));
+            unsigned hw, lw;
+            split_f16x2_fma_mix(t[2 * j], t[2 * j + 1], hw, lw);       // 3 instructions per pair
+            hv[j] = hw;
             lv[j] = lw;
           }
           if (s_act[r] && hc >= 0 && hc < XC) {
@@ -588,7 +567,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int px = (RPW * wr + ir) * XC + kw + fq;
       aoff[ir][kw] = px * PXB + ((fh8 ^ ((px >> 3) & 1)) << 4);
     }
-  f32x16 acc[4];
+  f32x16_t acc[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -620,15 +599,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // instructions of the current one.  The workgroup barrier of a chunk sits in front of its LAST half-phase: by then every read of
   // the chunk's image has been issued and has landed, the staging waves have finished the next image, and the first fragments of
   // the next chunk are requested right behind it.
-  f16x8 fa[2][NF][2], fb[2][3][2];
+  f16x8_t fa[2][NF][2], fb[2][3][2];
   auto load_a = [&](auto HPC, int s) __attribute__((always_inline)) {                        // A fragments of half-phase HP of chunk s -> set HP & 1
     constexpr int HP = decltype(HPC)::value, SET = HP & 1, KW = HP >> 1, HALF = HP & 1;
     const unsigned char* img = lds_x + (s & 1) * IMG;
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
       const unsigned char* ap = img + aoff[GE::frag_ir(HALF, j)][KW] + GE::frag_cb(HALF, j) * 32 * PXB;
-      fa[SET][j][0] = *reinterpret_cast<const f16x8*>(ap);
-      fa[SET][j][1] = *reinterpret_cast<const f16x8*>(ap + PSZ);
+      fa[SET][j][0] = *reinterpret_cast<const f16x8_t*>(ap);
+      fa[SET][j][1] = *reinterpret_cast<const f16x8_t*>(ap + PSZ);
     }
   };
   auto load_b = [&](auto SETC, auto KWC, int s) __attribute__((always_inline)) {             // B fragments of kernel column KW of chunk s -> set SET
@@ -636,8 +615,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned char* wl = lds_w + (s & 1) * WCH + wfo;
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
-      fb[SET][kh][0] = *reinterpret_cast<const f16x8*>(wl + ((kh * 3 + KW) * 2) * WTAP);
-      fb[SET][kh][1] = *reinterpret_cast<const f16x8*>(wl + ((kh * 3 + KW) * 2 + 1) * WTAP);
+      fb[SET][kh][0] = *reinterpret_cast<const f16x8_t*>(wl + ((kh * 3 + KW) * 2) * WTAP);
+      fb[SET][kh][1] = *reinterpret_cast<const f16x8_t*>(wl + ((kh * 3 + KW) * 2 + 1) * WTAP);
     }
   };
   auto mma = [&](auto HPC, auto BSETC) __attribute__((always_inline)) {
@@ -650,7 +629,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (rr < 0 || rr >= RPW) continue;
         const int ai = rr * CB + GE::frag_cb(HALF, j);
         if (MM_DIAG & 1) { acc[ai][0] += (float)fa[SET][j][0][0] + (float)fb[BS][kh][1][0] + (float)fa[SET][j][1][0] + (float)fb[BS][kh][0][0]; continue; }
-        f32x16 a = acc[ai];                                   // small terms first: lo*hi, hi*lo, then hi*hi
+        f32x16_t a = acc[ai];                                 // small terms first: lo*hi, hi*lo, then hi*hi
         // D[out channel][pixel]: the weight fragment is the A operand (row = out channel fq), the pixel fragment the B operand
         // (column = pixel fq): a lane then owns ONE pixel column and 16 out channels, so a store of one accumulator register is two
         // whole 128-byte lines (lanes 0-31 / 32-63: channels 4 apart) -- with D[pixel][channel] it was 32 partial lines

@@ -32,6 +32,7 @@
 // Everything else (16 x 32 tile, 8 waves x 4 output planes, 2 x 4 micro-tile per lane, register-prefetched float4 plane staging
 // with normalise-on-load, quad-nibble walk unrolled over the eight plane slots, fp64 statistics records) is conv133_kernel's.
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -49,6 +50,8 @@ __device__ unsigned long long g_sparse_stamps[1024 * 8];
 #endif
 
 namespace {
+
+using namespace e2e;
 
 constexpr int TH = 16, TW = 32, LX = 8, PH = 2, PW = 4, OPW = 4, NW = 8, CK = 8, OCG = 32;
 constexpr int IH = TH + 2, IW = TW + 2;
@@ -85,21 +88,9 @@ struct PlaneDesc {
   int valid;
 };
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef const f32x4_t __attribute__((address_space(1)))* gfloat4_p;
 typedef const volatile f32x2_t __attribute__((address_space(3)))* lds_v2_p;      // (volatile: not merged into ds_read2_b64)
 typedef const f32x4_t __attribute__((address_space(3)))* lds_v4_p;
 typedef const float __attribute__((address_space(3)))* lds_f_p;
-
-template <class T>
-__device__ __forceinline__ T load_uniform(const T* ptr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *reinterpret_cast<const T __attribute__((address_space(4)))*>((unsigned long long)ptr);      // scalar cache
-#else
-  return *ptr;
-#endif
-}
 
 template <int MODE>
 __global__ __launch_bounds__(NW * 64, 4) void conv133_sparse_kernel(SparseParams p) {
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(NW * 64, 4) void conv133_sparse_kernel(SparseParams
 #else
     const unsigned off = live && pd_ok ? (unsigned)su_goff[k] : 0u;
 #endif
-    v4[k] = *reinterpret_cast<gfloat4_p>(base + off);
+    v4[k] = *reinterpret_cast<gf4_p>(base + off);
   };
   // a chunk's weight block = 3 kmax float4 units; wave w moves units [uw w, uw w + uw) with up to two LDS-DMA instructions
   // (LDS destination = wave-uniform base + 16 * lane)

@@ -14,11 +14,12 @@
 // with channel strides == 2 (mod 32) so that the A/B fragment reads (16 channels x 4 consecutive pixels) hit 32
 // distinct banks.  Per-chunk partial sums go to a slab, reduced in fixed order by a second kernel (deterministic).
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace e2e;
 
 struct WgParams {
   const e2e_in_chan_t* chans;
@@ -63,9 +64,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_kernel(WgParams p) {
   const long long in_plane = (long long)p.Hi * p.Wi;
   const long long out_plane = (long long)p.Ho * p.Wo;
 
-  f32x4 acc[9];
+  f32x4_t acc[9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   for (int ti = 0; ti < p.tiles_per_chunk; ++ti) {
     const long long tile = (long long)chunk * p.tiles_per_chunk + ti;
@@ -166,8 +167,6 @@ __global__ __launch_bounds__(256) void conv133_wgrad_kernel(WgParams p) {
 // channels so that the dy tile is staged once for all of them (NCB * 4 waves).  Each wave stages 8 input channels
 // and 32 / (4 NCB) dy channels; the channel descriptors are wave-uniform and live in scalar registers for as long
 // as the batch item does not change.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef const f32x4_t __attribute__((address_space(1)))* gf4_p;
 
 template <int ND, int TH, int TW, int NCB>
 struct W2Cfg {
@@ -208,9 +207,9 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
   const long long out_plane = (long long)p.Ho * p.Wo;
   const int cbase = cg * NCB * 32;
 
-  f32x4 acc[9];
+  f32x4_t acc[9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const long long tile_lo = (long long)chunk * p.tiles_per_chunk;
   long long tile_hi = tile_lo + p.tiles_per_chunk;
@@ -472,9 +471,9 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
   const long long out_plane = (long long)p.Ho * p.Wo;
   const int cbase = cg * NCB * 32;
 
-  f32x4 acc[9];
+  f32x4_t acc[9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int tile_lo = seg * p.tiles_per_chunk;
   int tile_hi = tile_lo + p.tiles_per_chunk;
@@ -679,9 +678,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
   const long long in_plane = (long long)p.Hi * p.Wi;
   const long long out_plane = (long long)p.Ho * p.Wo;
 
-  f32x4 acc[3];
+  f32x4_t acc[3];
 #pragma unroll
-  for (int m = 0; m < 3; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < 3; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int tile_lo = seg * p.tiles_per_chunk;
   int tile_hi = tile_lo + p.tiles_per_chunk;
@@ -859,9 +858,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
   const long long out_plane = (long long)p.Ho * p.Wo;
   const int cbase = cb * 32;
 
-  f32x4 acc[9];
+  f32x4_t acc[9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const long long tile_lo = (long long)chunk * p.tiles_per_chunk;
   long long tile_hi = tile_lo + p.tiles_per_chunk;

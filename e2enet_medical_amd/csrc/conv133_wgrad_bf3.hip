@@ -27,20 +27,16 @@
 // staging waves) were measured against this form in rounds 3 / 4 (profiles/r04_kbench.txt, r04_pmc_sq_bf3.txt: 0.905 / 0.865 /
 // 0.83 ms on 64 -> 32 @128^3 x 2) and removed in round 5; what is left is v5 in two operand formats (NPC below).
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 
 // raw buffer loads (the clang builtin __builtin_amdgcn_raw_buffer_load_b128 of this toolchain lowers to a splatted dword load)
-__device__ float __attribute__((ext_vector_type(4))) llvm_raw_buffer_load_v4f32(int __attribute__((ext_vector_type(4))) rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-__device__ float llvm_raw_buffer_load_f32(int __attribute__((ext_vector_type(4))) rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
+__device__ e2e::f32x4_t llvm_raw_buffer_load_v4f32(e2e::i32x4_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ float llvm_raw_buffer_load_f32(e2e::i32x4_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef const f32x4_t __attribute__((address_space(1)))* gf4_p;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
+using namespace e2e;
 
 constexpr int TH = 4, TW = 32;
 constexpr int XROWS = TH + 2;
@@ -51,36 +47,28 @@ constexpr int XROWB = 64;
 __device__ __forceinline__ void split4(const float (&v)[4], u32x2_t& hi, u32x2_t& mid, u32x2_t& lo) {
   unsigned u[4], m[4], l[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    u[j] = __builtin_bit_cast(unsigned, v[j]);
-    const float r1 = v[j] - __builtin_bit_cast(float, u[j] & 0xffff0000u);          // exact
-    m[j] = __builtin_bit_cast(unsigned, r1);
-    const float r2 = r1 - __builtin_bit_cast(float, m[j] & 0xffff0000u);            // exact, <= 8 significant bits
-    l[j] = __builtin_bit_cast(unsigned, r2);
-  }
-  // v_perm_b32: bytes {S0, S1}; 0x07060302 = (S1 >> 16) | (S0 & 0xffff0000)
-  hi = u32x2_t{__builtin_amdgcn_perm(u[1], u[0], 0x07060302u), __builtin_amdgcn_perm(u[3], u[2], 0x07060302u)};
-  mid = u32x2_t{__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u)};
-  lo = u32x2_t{__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u)};
+  for (int j = 0; j < 4; ++j) split_bf3(v[j], u[j], m[j], l[j]);
+  hi = u32x2_t{pack_hi16(u[0], u[1]), pack_hi16(u[2], u[3])};
+  mid = u32x2_t{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
+  lo = u32x2_t{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
 }
-
-// fp16 two-piece split (round 5): v * 2^k = hi + lo + r with hi = rn16(v), lo = rn16(v - hi) (the subtraction is exact), 11 + 11
-// significant bits: |r| <= 2^-23 |v| while lo is a normal fp16 (|v| >= 2^-3 in scaled units), half a subnormal step (2^-25) below.
-// v_cvt_pk_f16_f32, two v_cvt_f32_f16 (one SDWA), v_pk_add_f32, v_cvt_pk_f16_f32: 5 instructions per two values (bf16x3: 11).
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+// the same in the fp16 two-piece form: convert-and-subtract (the kernels below), or FMA_MIX the form of K1m and the transposed
+// convs (the numerics gate only)
+template <bool FMA_MIX = false>
 __device__ __forceinline__ void split4h(const float (&v)[4], u32x2_t& hi, u32x2_t& lo) {
-  const f16x2_t h0 = __builtin_convertvector((f32x2_t{v[0], v[1]}), f16x2_t), h1 = __builtin_convertvector((f32x2_t{v[2], v[3]}), f16x2_t);
-  const f16x2_t l0 = __builtin_convertvector((f32x2_t{v[0] - (float)h0[0], v[1] - (float)h0[1]}), f16x2_t);
-  const f16x2_t l1 = __builtin_convertvector((f32x2_t{v[2] - (float)h1[0], v[3] - (float)h1[1]}), f16x2_t);
-  hi = u32x2_t{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
-  lo = u32x2_t{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
+  unsigned hw[2], lw[2];
+  if constexpr (FMA_MIX) {
+    split_f16x2_fma_mix(v[0], v[1], hw[0], lw[0]);
+    split_f16x2_fma_mix(v[2], v[3], hw[1], lw[1]);
+  } else {
+    split_f16x2_cvt_sub<2>(v, hw, lw);
+  }
+  hi = u32x2_t{hw[0], hw[1]};
+  lo = u32x2_t{lw[0], lw[1]};
 }
 
 // Channel stride 400 B (= 25 x 16, odd): the 16 lanes of a ds_read_b128 group (one 8-element k group, 16 channels) hit 16
 // distinct bank quads.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int CSTR2 = 400, SSTR2 = 32 * CSTR2;              // channel stride, piece stride (32 channels)
 static_assert(XROWS * XROWB + 16 == CSTR2 && TH * YROWB + 16 == CSTR2 && (CSTR2 / 16) % 2 == 1, "channel stride");
 
@@ -114,17 +102,10 @@ static_assert(XROWS * XROWB + 16 == CSTR2 && TH * YROWB + 16 == CSTR2 && (CSTR2 
 //        next row), input rows of 32 B, the same 400 B channel stride: same images, same pipeline, 5 + 4 + 2 pieces per wave.
 // NPC = 3: bf16 three-piece operands, six products per fp32 product.  NPC = 2 (round 5): fp16 two-piece operands, THREE products
 //        (lo*hi, hi*lo, hi*hi through v_mfma_f32_32x32x16_f16): 54 matrix instructions per tile instead of 108, two thirds of the
-//        LDS image, 5 instead of 11 conversion instructions per value pair.  fp16 has 5 exponent bits: dy (magnitudes of 1e-7 at
-//        full resolution) is pre-scaled by the exact power of two 2^k that puts max |dy| in [2^14, 2^15), max |dy| being what the
-//        producer of dy recorded (p.dy_absmax, e2e_in_lrelu_bwd); the slab is un-scaled on store.  The input side (activations
-//        after InstanceNorm + LeakyReLU, transposed-conv outputs) is pre-scaled by the power of two that puts a BOUND of |x| over
-//        the conv's input planes (p.x_absmax: e2e_conv133_input_ranges, from the parameters) in [2^14, 2^15) -- round 6; rounds 5's
-//        fixed 2^XSH = 8 (still what a NULL word means) turned |x| > 8188 into Inf -- folded into the lane's (scale, shift) pair;
-//        the lo piece of values 2^11 below the bound's scale is a subnormal fp16 (absolute error 2^-25 of the scaled range there
-//        instead of relative 2^-23: the negative half of every LeakyReLU output lives around 0.01).  Error against fp64 (same probe, K = 256 .. 262144, activation x heavy-tailed
-//        1e-7 gradients, all-positive operands): at or below the bf16x3 form and the fp32 FMA chain in every row; round-to-nearest
-//        splits (truncating ones are biased: 4e-4 of the result at K = 262144 with one-signed operands).
-constexpr int XSH = 3;
+//        LDS image, 5 instead of 11 conversion instructions per value pair (e2e_split.h: the form, its scales and its error).  dy
+//        is scaled from max |dy| as its producer recorded it (p.dy_absmax, e2e_in_lrelu_bwd), the input side from the bound of |x|
+//        over the conv's input planes (p.x_absmax, e2e_conv133_input_ranges; NULL: the fixed 2^XSH), folded into the lane's
+//        (scale, shift) pair; the slab is un-scaled on store.
 __device__ unsigned long long g_wg_clock[2];     // as g_mm_clock (conv133_mm.hip)
 template <int G, int NPC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv133_wgrad_bf3v5_kernel(e2e::WgBf3Params p) {
@@ -146,34 +127,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (tile_hi > p.tiles_per_n) tile_hi = p.tiles_per_n;
   const int ntiles = tile_hi - tile_lo;
   const unsigned long long clk_c0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-  f32x16 acc[9];
+  f32x16_t acc[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-  // fp16x2: dy scale 2^k from the recorded max |dy| (biased exponent E: k = 141 - E puts the max in [2^14, 2^15)); k clamped so
-  // that 2^k and 2^-(k + XSH) are normal numbers; a zero / denormal max takes E = 1, Inf / NaN propagate
-  // The input side: 2^kx from the bound of |x| the caller derived for this conv's input planes (p.x_absmax, round 6; without it the
-  // fixed 2^XSH).  The slab is un-scaled by the two exact factors 2^-k and 2^-kx (the sum of the exponents may leave the fp32 range).
+  // fp16x2: operand scales 2^k (dy) and 2^kx (input side); the slab is un-scaled by the two exact factors 2^-k and 2^-kx
   float ysc = 1.f, unsc = 1.f, unsc_x = 1.f, xsc = 1.f;
   if constexpr (NPC == 2) {
-    int k = 0, kx = XSH;
-    if (p.dy_absmax != nullptr) {
-      int E = (int)((__builtin_nontemporal_load(p.dy_absmax) >> 23) & 0xffu);
-      E = E < 1 ? 1 : E;
-      k = 141 - E;
-      k = k > 120 ? 120 : (k < -120 ? -120 : k);
-    }
-    if (p.x_absmax != nullptr) {
-      int E = (int)((__builtin_nontemporal_load(p.x_absmax) >> 23) & 0xffu);
-      E = E < 1 ? 1 : E;
-      kx = 141 - E;
-      kx = kx > 110 ? 110 : (kx < -110 ? -110 : kx);
-    }
-    ysc = __builtin_bit_cast(float, (unsigned)(127 + k) << 23);
-    unsc = __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
-    xsc = __builtin_bit_cast(float, (unsigned)(127 + kx) << 23);
-    unsc_x = __builtin_bit_cast(float, (unsigned)(127 - kx) << 23);
+    const int k = p.dy_absmax != nullptr ? scale_exp<LIM_DY>(__builtin_nontemporal_load(p.dy_absmax)) : 0;
+    const int kx = p.x_absmax != nullptr ? scale_exp<LIM_X>(__builtin_nontemporal_load(p.x_absmax)) : XSH;
+    ysc = pow2f(k);
+    unsc = pow2f(-k);
+    xsc = pow2f(kx);
+    unsc_x = pow2f(-kx);
   }
 
   if (ntiles > 0) {
@@ -308,19 +275,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto commit_h = [&](const int rs, const int k2, unsigned char* img) {
       unsigned char* dst = img + XBn + hdst[k2];
       if constexpr (NPC == 3) {
-        const float v = vh[rs][k2];
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        const float r1 = v - __builtin_bit_cast(float, u & 0xffff0000u);
-        const unsigned m = __builtin_bit_cast(unsigned, r1);
-        const float r2 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-        const unsigned l = __builtin_bit_cast(unsigned, r2);
+        unsigned u, m, l;
+        split_bf3(vh[rs][k2], u, m, l);
         *reinterpret_cast<unsigned short*>(dst) = (unsigned short)(u >> 16);
         *reinterpret_cast<unsigned short*>(dst + SSTR2) = (unsigned short)(m >> 16);
         *reinterpret_cast<unsigned short*>(dst + 2 * SSTR2) = (unsigned short)(l >> 16);
       } else {
-        const float v = vh[rs][k2] * ysc;
-        const _Float16 h = (_Float16)v;
-        const _Float16 l = (_Float16)(v - (float)h);
+        _Float16 h, l;
+        split_f16_cvt_sub(vh[rs][k2] * ysc, h, l);
         *reinterpret_cast<_Float16*>(dst) = h;
         *reinterpret_cast<_Float16*>(dst + SSTR2) = l;
       }
@@ -333,7 +295,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int b_off = fr * CSTR2 + (G ? 2 : 1) * wr * GXROWB + 8 * fh8 * 2;
     u32x4_t r_an[NPC];
     unsigned r_prev[NPC], r_next[NPC];
-    bf16x8 bq[2][NPC];
+    bf16x8_t bq[2][NPC];
     auto read_a = [&](const unsigned char* img, int half) {
 #pragma unroll
       for (int s = 0; s < NPC; ++s) {
@@ -343,9 +305,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         r_next[s] = *reinterpret_cast<const unsigned*>(ap + 16);
       }
     };
-    auto read_b = [&](const unsigned char* img, int half, int kh, bf16x8 (&b)[NPC]) {
+    auto read_b = [&](const unsigned char* img, int half, int kh, bf16x8_t (&b)[NPC]) {
 #pragma unroll
-      for (int s = 0; s < NPC; ++s) b[s] = *reinterpret_cast<const bf16x8*>(img + b_off + kh * GXROWB + half * BH + s * SSTR2);
+      for (int s = 0; s < NPC; ++s) b[s] = *reinterpret_cast<const bf16x8_t*>(img + b_off + kh * GXROWB + half * BH + s * SSTR2);
     };
 
     // ---- prologue: tile 0 committed, tile 1 in the registers of set 1 ----
@@ -376,7 +338,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       unsigned char* const imgn = lds + ((t & 1) ^ 1) * BUFn;
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
-        bf16x8 afr[3][NPC];                                   // [kw][piece]
+        bf16x8_t afr[3][NPC];                                 // [kw][piece]
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
           const int ph = half * 3 + kh, cur = ph & 1;
@@ -389,9 +351,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                          __builtin_amdgcn_alignbit(an[3], an[2], 16), __builtin_amdgcn_alignbit(r_next[s], an[3], 16)};
               const u32x4_t k2 = u32x4_t{__builtin_amdgcn_alignbit(an[0], r_prev[s], 16), __builtin_amdgcn_alignbit(an[1], an[0], 16),
                                          __builtin_amdgcn_alignbit(an[2], an[1], 16), __builtin_amdgcn_alignbit(an[3], an[2], 16)};
-              afr[0][s] = __builtin_bit_cast(bf16x8, k0);
-              afr[1][s] = __builtin_bit_cast(bf16x8, an);
-              afr[2][s] = __builtin_bit_cast(bf16x8, k2);
+              afr[0][s] = __builtin_bit_cast(bf16x8_t, k0);
+              afr[1][s] = __builtin_bit_cast(bf16x8_t, an);
+              afr[2][s] = __builtin_bit_cast(bf16x8_t, k2);
             }
           }
           if (ph == 5) {
@@ -427,7 +389,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           }
 #pragma unroll
           for (int kw = 0; kw < 3; ++kw) {
-            f32x16 a = acc[kh * 3 + kw];
+            f32x16_t a = acc[kh * 3 + kw];
             if constexpr (NPC == 3) {
               a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[kw][2], bq[cur][0], a, 0, 0, 0);
               a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[kw][1], bq[cur][1], a, 0, 0, 0);
@@ -436,9 +398,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
               a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[kw][0], bq[cur][1], a, 0, 0, 0);
               a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[kw][0], bq[cur][0], a, 0, 0, 0);
             } else {                                          // small terms first: lo*hi, hi*lo, then hi*hi
-              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[kw][1]), __builtin_bit_cast(f16x8, bq[cur][0]), a, 0, 0, 0);
-              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[kw][0]), __builtin_bit_cast(f16x8, bq[cur][1]), a, 0, 0, 0);
-              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, afr[kw][0]), __builtin_bit_cast(f16x8, bq[cur][0]), a, 0, 0, 0);
+              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, afr[kw][1]), __builtin_bit_cast(f16x8_t, bq[cur][0]), a, 0, 0, 0);
+              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, afr[kw][0]), __builtin_bit_cast(f16x8_t, bq[cur][1]), a, 0, 0, 0);
+              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, afr[kw][0]), __builtin_bit_cast(f16x8_t, bq[cur][0]), a, 0, 0, 0);
             }
             acc[kh * 3 + kw] = a;
           }
@@ -497,23 +459,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // ---- diagnostic: one 32 x 32 output block of a GEMM through the SAME split functions and product orders as the kernels above -----
-// D[m][n] = sum_k A[m][k] Bt[n][k]; mode 0 bf16 three-piece / six products, 1 fp16 two-piece / three products (Bt scaled from
-// *absmax_b like dy), 2 the fp32-input MFMA (an fp32 FMA chain).  One wave; the test holds each against an fp64 evaluation.
+// D[m][n] = sum_k A[m][k] Bt[n][k]; mode 0 bf16 three-piece / six products (K6b's and the transposed convs' bf16 form, the dense
+// conv), 1 fp16 two-piece convert-and-subtract / three products (K6b; Bt scaled from *absmax_b like dy), 2 the fp32-input MFMA (an
+// fp32 FMA chain), 3 as 1 with the fma-mix split (K1m and the transposed convs; K1m issues hi*lo before lo*hi).  One wave; the
+// test holds each against an fp64 evaluation.
 template <int MODE>
 __global__ __launch_bounds__(64) void diag_split_gemm_kernel(const float* __restrict__ A, const float* __restrict__ Bt, float* __restrict__ D, int K,
                                                              const unsigned* __restrict__ absmax_b) {
+  constexpr bool H2 = MODE == 1 || MODE == 3;
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  f32x16 acc;
+  f32x16_t acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   float ysc = 1.f, unsc = 1.f;
-  if (MODE == 1 && absmax_b != nullptr) {
-    int E = (int)((*absmax_b >> 23) & 0xffu);
-    E = E < 1 ? 1 : E;
-    int k = 141 - E;
-    k = k > 120 ? 120 : (k < -120 ? -120 : k);
-    ysc = __builtin_bit_cast(float, (unsigned)(127 + k) << 23);
-    unsc = __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
+  if (H2 && absmax_b != nullptr) {
+    const int k = scale_exp<LIM_DY>(*absmax_b);
+    ysc = pow2f(k);
+    unsc = pow2f(-k);
   }
   if (MODE == 2) {
     for (int k0 = 0; k0 < K; k0 += 2)
@@ -536,23 +498,23 @@ __global__ __launch_bounds__(64) void diag_split_gemm_kernel(const float* __rest
           split4(vb, p0, p1, p2);
           b[0][2 * q] = p0[0]; b[0][2 * q + 1] = p0[1]; b[1][2 * q] = p1[0]; b[1][2 * q + 1] = p1[1]; b[2][2 * q] = p2[0]; b[2][2 * q + 1] = p2[1];
         } else {
-          split4h(va, p0, p1);
+          split4h<MODE == 3>(va, p0, p1);
           a[0][2 * q] = p0[0]; a[0][2 * q + 1] = p0[1]; a[1][2 * q] = p1[0]; a[1][2 * q + 1] = p1[1];
-          split4h(vb, p0, p1);
+          split4h<MODE == 3>(vb, p0, p1);
           b[0][2 * q] = p0[0]; b[0][2 * q + 1] = p0[1]; b[1][2 * q] = p1[0]; b[1][2 * q + 1] = p1[1];
         }
       }
       if (MODE == 0) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[2]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]), __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[2]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[2]), __builtin_bit_cast(bf16x8_t, b[0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[1]), __builtin_bit_cast(bf16x8_t, b[1]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]), __builtin_bit_cast(bf16x8_t, b[2]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[1]), __builtin_bit_cast(bf16x8_t, b[0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]), __builtin_bit_cast(bf16x8_t, b[1]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[0]), __builtin_bit_cast(bf16x8_t, b[0]), acc, 0, 0, 0);
       } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[1]), __builtin_bit_cast(f16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[1]), __builtin_bit_cast(f16x8_t, b[0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[1]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[0]), acc, 0, 0, 0);
       }
     }
   }
@@ -569,11 +531,12 @@ void e2e::wgrad_clock_read(unsigned long long out[2], bool reset) {
 }
 
 extern "C" int e2e_diag_split_gemm(const float* A, const float* Bt, float* D, int K, int mode, const unsigned* absmax_b, void* stream) {
-  E2E_REQUIRE(A && Bt && D && K > 0 && K % 16 == 0 && mode >= 0 && mode <= 2, "diag_split_gemm: bad arguments");
+  E2E_REQUIRE(A && Bt && D && K > 0 && K % 16 == 0 && mode >= 0 && mode <= 3, "diag_split_gemm: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   if (mode == 0) hipLaunchKernelGGL(diag_split_gemm_kernel<0>, dim3(1), dim3(64), 0, st, A, Bt, D, K, absmax_b);
   else if (mode == 1) hipLaunchKernelGGL(diag_split_gemm_kernel<1>, dim3(1), dim3(64), 0, st, A, Bt, D, K, absmax_b);
-  else hipLaunchKernelGGL(diag_split_gemm_kernel<2>, dim3(1), dim3(64), 0, st, A, Bt, D, K, absmax_b);
+  else if (mode == 2) hipLaunchKernelGGL(diag_split_gemm_kernel<2>, dim3(1), dim3(64), 0, st, A, Bt, D, K, absmax_b);
+  else hipLaunchKernelGGL(diag_split_gemm_kernel<3>, dim3(1), dim3(64), 0, st, A, Bt, D, K, absmax_b);
   return e2e::check_launch("diag_split_gemm_kernel");
 }
 

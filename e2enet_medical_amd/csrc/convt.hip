@@ -9,12 +9,12 @@
 // re-reads of z / dy are L2 hits) with the weights as wave-uniform scalars and the DSFF liveness bits walked
 // with scalar bit ops.  The dense weight gradient (huge reduction over voxels) runs on the fp32 MFMA.
 #include "e2e_common.h"
+#include "e2e_split.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef const f32x4_t __attribute__((address_space(1)))* gf4_p;
+using namespace e2e;
 
 // flat voxel index inside one sample -> (d, h, w).  A sample has fewer than 2^31 voxels (checked by the entry points),
 // so this is 32-bit unsigned arithmetic: the 64-bit `%` and `/` the index types would imply cost ~100 vector
@@ -174,7 +174,6 @@ __global__ __launch_bounds__(256) void convT_dgrad_kernel(const float* __restric
 // (exact fp32 fma chain, so the sum is a plain fp32 accumulation like the reference's).  The reduction index is
 // the voxel: it lives inside the MFMA K dimension and in the loop, so no cross-lane reduction is needed.
 // Partial sums per chunk go to a slab; a second kernel adds the slabs in fixed order (deterministic).
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int WG_TPX = 64;                 // voxels staged per step
 constexpr int WG_ZS = WG_TPX + 2;          // channel stride in LDS, == 2 (mod 32): conflict-free A/B fragment reads
@@ -197,9 +196,9 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
   const int ch = wave & 1, oh = wave >> 1;
   const int Ho = H * kh, Wo = W * kw;
 
-  f32x4 acc[KT];
+  f32x4_t acc[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < KT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   for (int ti = 0; ti < tiles_per_chunk; ++ti) {
     const long long tile = (long long)chunk * tiles_per_chunk + ti;
@@ -292,9 +291,9 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
   const long long ospatial = spatial * KT;
   const int cbase = cg * NCB * 32;
 
-  f32x4 acc[KT];
+  f32x4_t acc[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < KT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const long long tile_lo = (long long)chunk * tiles_per_chunk;
   long long tile_hi = tile_lo + tiles_per_chunk;
@@ -431,51 +430,26 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
 // v2 is bound by its fp32 MFMAs (128 x 32 cycles per 64-voxel tile and wave, two waves per SIMD: 0.125 ms of a 0.25 ms
 // launch at 64 -> 32 @64^3).  Both operands are split into three bf16 pieces when they are staged ([piece][row][64 voxels]
 // bf16, row stride 144 B); the reduction dimension (voxels) is contiguous in both images, so an A / B fragment is one
-// ds_read_b128; 96 v_mfma_f32_16x16x32_bf16 x 16 cycles per tile and wave.  The split3 / pack_hi16 helpers and the data
-// gradient of the same scheme follow below (convT_dgrad_bf3_kernel); they are declared here.
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split3(float v, unsigned& h, unsigned& m, unsigned& l) {
-  h = __builtin_bit_cast(unsigned, v);
-  const float r1 = v - __builtin_bit_cast(float, h & 0xffff0000u);            // exact
-  m = __builtin_bit_cast(unsigned, r1);
-  const float r2 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);           // exact, <= 8 significant bits
-  l = __builtin_bit_cast(unsigned, r2);
-}
-// (S1 >> 16) | (S0 & 0xffff0000): the bf16 (truncated) pieces of two values in one word, `lo` in the low half
-__device__ __forceinline__ unsigned pack_hi16(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-
-// ---- round 6: the same three GEMMs with fp16 TWO-piece operands (NP = 2: three products per fp32 product instead of six; NP = 3
-// keeps the bf16 three-piece form).  x = hi + lo, hi = rn16(x), lo = rn16(x - hi): 11 + 11 significant bits, products lo*hi +
-// hi*lo + hi*hi through v_mfma_f32_16x16x32_f16, fp32 accumulation (conv133_mm.hip, conv133_wgrad_bf3.hip; numerics gate:
-// tests/test_gpu_ops.py::test_split_operand_products_vs_fp64).  fp16 has 5 exponent bits, so every operand is moved into range by
-// an exact power of two taken from a device word (bit pattern of a bound of max |operand|): the activations from the bound
-// e2e_conv133_input_ranges derives from the producer's InstanceNorm parameters, the weights from their measured maximum, dy from
-// max |dy of the consuming conv| x the L1 norm of that conv's weights over this tensor's channels.  Without the words a launch
-// stays on the bf16 form (8 exponent bits: no range to manage).
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_ct __attribute__((ext_vector_type(2)));
-typedef float f32x2_ct __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2_pair(float a, float b, unsigned& hw, unsigned& lw) {
-  const f16x2_ct h2 = __builtin_convertvector((f32x2_ct{a, b}), f16x2_ct);
-  hw = __builtin_bit_cast(unsigned, h2);
-  // lo = rn16(v - hi) as ONE mixed-precision FMA per value: fma(hi as f16, -1, v) is exact in fp32, rounded to fp16 into the low / high half
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(lw) : "v"(hw), "v"(a), "v"(b));
-}
+// ds_read_b128; 96 v_mfma_f32_16x16x32_bf16 x 16 cycles per tile and wave.  The forward and the data gradient of the same
+// scheme follow below.
+//
+// Round 6: the same three GEMMs with fp16 TWO-piece operands (NP = 2: three products per fp32 product instead of six, through
+// v_mfma_f32_16x16x32_f16; NP = 3 keeps the bf16 three-piece form).  Both forms and the operand scales: e2e_split.h.  The range
+// words: the activations' from the bound e2e_conv133_input_ranges derives from the producer's InstanceNorm parameters, the weights'
+// from their measured maximum, dy's from max |dy of the consuming conv| x the L1 norm of that conv's weights over this tensor's
+// channels.  Without the words a launch stays on the bf16 form.
 // the NP packed words (two values each: `a` in the low half) of a value pair, piece p at dst + p * pstride
 template <int NP>
 __device__ __forceinline__ void store_pair(unsigned char* dst, int pstride, float a, float b) {
   if constexpr (NP == 2) {
     unsigned hw, lw;
-    split2_pair(a, b, hw, lw);
+    split_f16x2_fma_mix(a, b, hw, lw);
     *reinterpret_cast<unsigned*>(dst) = hw;
     *reinterpret_cast<unsigned*>(dst + pstride) = lw;
   } else {
     unsigned ha, ma, la, hb, mb, lb;
-    split3(a, ha, ma, la);
-    split3(b, hb, mb, lb);
+    split_bf3(a, ha, ma, la);
+    split_bf3(b, hb, mb, lb);
     *reinterpret_cast<unsigned*>(dst) = pack_hi16(ha, hb);
     *reinterpret_cast<unsigned*>(dst + pstride) = pack_hi16(ma, mb);
     *reinterpret_cast<unsigned*>(dst + 2 * pstride) = pack_hi16(la, lb);
@@ -487,13 +461,13 @@ __device__ __forceinline__ void split_frag(const float (&v)[8], bf16x8_t (&out)[
   if constexpr (NP == 2) {
     unsigned hw[4], lw[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) split2_pair(v[2 * j], v[2 * j + 1], hw[j], lw[j]);
+    for (int j = 0; j < 4; ++j) split_f16x2_fma_mix(v[2 * j], v[2 * j + 1], hw[j], lw[j]);
     out[0] = __builtin_bit_cast(bf16x8_t, u32x4_t{hw[0], hw[1], hw[2], hw[3]});
     out[1] = __builtin_bit_cast(bf16x8_t, u32x4_t{lw[0], lw[1], lw[2], lw[3]});
   } else {
     unsigned h[8], m[8], l[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) split3(v[j], h[j], m[j], l[j]);
+    for (int j = 0; j < 8; ++j) split_bf3(v[j], h[j], m[j], l[j]);
     out[0] = __builtin_bit_cast(bf16x8_t, u32x4_t{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7])});
     out[1] = __builtin_bit_cast(bf16x8_t, u32x4_t{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7])});
     out[2] = __builtin_bit_cast(bf16x8_t, u32x4_t{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7])});
@@ -501,7 +475,7 @@ __device__ __forceinline__ void split_frag(const float (&v)[8], bf16x8_t (&out)[
 }
 // acc += A B rebuilt from the pieces: small terms first
 template <int NP>
-__device__ __forceinline__ f32x4 mma_pieces(const bf16x8_t (&a)[NP], const bf16x8_t (&b)[NP], f32x4 c) {
+__device__ __forceinline__ f32x4_t mma_pieces(const bf16x8_t (&a)[NP], const bf16x8_t (&b)[NP], f32x4_t c) {
   if constexpr (NP == 2) {
     const f16x8_t a0 = __builtin_bit_cast(f16x8_t, a[0]), a1 = __builtin_bit_cast(f16x8_t, a[1]);
     const f16x8_t b0 = __builtin_bit_cast(f16x8_t, b[0]), b1 = __builtin_bit_cast(f16x8_t, b[1]);
@@ -519,18 +493,13 @@ __device__ __forceinline__ f32x4 mma_pieces(const bf16x8_t (&a)[NP], const bf16x
   }
   return c;
 }
-// exponent k of the power of two that moves a tensor bounded by the product of the floats whose bit patterns are *wa and *wb (either
-// may be null = 1) into [2^14, 2^15): k = 141 - E, clamped to +-100 (2^k and 2^-k normal); a zero bound takes E = 1, Inf / NaN propagate
+// scale exponent of a tensor bounded by the product of the floats whose bit patterns are *wa and *wb (either may be null = 1)
 __device__ __forceinline__ int ct_scale_exp(const unsigned* wa, const unsigned* wb) {
   float b = 1.f;
   if (wa != nullptr) b *= __builtin_bit_cast(float, __builtin_nontemporal_load(wa));
   if (wb != nullptr) b *= __builtin_bit_cast(float, __builtin_nontemporal_load(wb));
-  int E = (int)((__builtin_bit_cast(unsigned, b) >> 23) & 0xffu);
-  E = E < 1 ? 1 : E;
-  const int k = 141 - E;
-  return k > 100 ? 100 : (k < -100 ? -100 : k);
+  return scale_exp<LIM_CT>(__builtin_bit_cast(unsigned, b));
 }
-__device__ __forceinline__ float ct_pow2(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
 
 // TPX = input voxels per tile: 64 (one 138 KB workgroup per CU) or, for KDH = 4, 32: two 77 KB workgroups per CU, one converting
 // and committing its tile while the other issues its matrix instructions (the phases of ONE workgroup are serial: commit, barrier,
@@ -556,7 +525,7 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
   __shared__ __attribute__((aligned(16))) unsigned char ds[NP * YP];     // [piece][tap][out channel][voxel]
   // fp16 two-piece form: operand scales 2^kx (activations) and 2^ky (dy), the slab un-scaled by the two exact factors
   const int kx = NP == 2 ? ct_scale_exp(x_word, nullptr) : 0, ky = NP == 2 ? ct_scale_exp(dy_word_a, dy_word_b) : 0;
-  const float xsc = ct_pow2(kx), ysc = ct_pow2(ky), unx = ct_pow2(-kx), uny = ct_pow2(-ky);
+  const float xsc = pow2f(kx), ysc = pow2f(ky), unx = pow2f(-kx), uny = pow2f(-ky);
 
   const int chunk = blockIdx.x;
   const int cg = blockIdx.y % cgroups, ob = blockIdx.y / cgroups;
@@ -570,9 +539,9 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
   const long long ospatial = spatial * KT;
   const int cbase = cg * NCB * 32;
 
-  f32x4 acc[KT];
+  f32x4_t acc[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < KT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const long long tile_lo = (long long)chunk * tiles_per_chunk;
   long long tile_hi = tile_lo + tiles_per_chunk;
@@ -978,9 +947,9 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
       commit(tile, o0);
       __syncthreads();
       if (tile + 1 < tile_hi) prefetch(tile + 1, o0);    // in flight during the MFMA phase
-      f32x4 acc[TV / 16];
+      f32x4_t acc[TV / 16];
 #pragma unroll
-      for (int b = 0; b < TV / 16; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < TV / 16; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
       const float* bp = ds + lk * TS + li;
       // B fragments in groups of G k-steps, two register sets: the LDS reads of group g + 1 are in flight while the
       // MFMAs of group g issue (left to the compiler this loop was read -> wait -> 2 MFMAs, one LDS round trip per k-step)
@@ -1053,7 +1022,7 @@ __global__ __launch_bounds__(256, 2) void convT_fwd_bf3_kernel(const float* __re
   constexpr int NRD = K / 64;                           // staging rounds: 256 threads x (2 channels x 4 voxels)
   __shared__ __attribute__((aligned(16))) unsigned char zs[NP * PSZ];
   const int kx = NP == 2 ? ct_scale_exp(x_word, nullptr) : 0, kwt = NP == 2 ? ct_scale_exp(w_word, nullptr) : 0;
-  const float xsc = ct_pow2(kx), wsc = ct_pow2(kwt), unx = ct_pow2(-kx), unw = ct_pow2(-kwt);
+  const float xsc = pow2f(kx), wsc = pow2f(kwt), unx = pow2f(-kx), unw = pow2f(-kwt);
 
   const long long spatial = (long long)D * H * W;
   const long long tiles_per_n = spatial / TV;
@@ -1138,11 +1107,11 @@ __global__ __launch_bounds__(256, 2) void convT_fwd_bf3_kernel(const float* __re
     commit();
     __syncthreads();
     if (tile + 1 < tile_hi) prefetch(tile + 1);          // in flight during the matrix phase
-    f32x4 acc[2][NTW];
+    f32x4_t acc[2][NTW];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     // A fragment: voxel 16 mt + li, channels 32 kb + 8 lk .. + 7
     const unsigned char* ap = zs + li * RS + lk * 16;
 #pragma unroll
@@ -1167,7 +1136,7 @@ __global__ __launch_bounds__(256, 2) void convT_fwd_bf3_kernel(const float* __re
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int nt = 0; nt < NTW; ++nt) {
-        f32x4 a = acc[mt][nt];
+        f32x4_t a = acc[mt][nt];
         if (NP == 2) a = a * unx * unw;
         const float s0 = odd ? a[0] : a[2], s1 = odd ? a[1] : a[3];
         // quad_perm [1, 0, 3, 2]: swap with the neighbouring lane
@@ -1204,7 +1173,7 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
   constexpr int NUY = OC * KDH * (TV / 2) / 256;       // float4 loads per thread per tile
   __shared__ __attribute__((aligned(16))) unsigned char ds[NP * PSZ];
   const int kwt = NP == 2 ? ct_scale_exp(w_word, nullptr) : 0, ky = NP == 2 ? ct_scale_exp(dy_word_a, dy_word_b) : 0;
-  const float wsc = ct_pow2(kwt), ysc = ct_pow2(ky), unw = ct_pow2(-kwt), uny = ct_pow2(-ky);
+  const float wsc = pow2f(kwt), ysc = pow2f(ky), unw = pow2f(-kwt), uny = pow2f(-ky);
 
   const long long spatial = (long long)D * H * W;
   const long long tiles_per_n = spatial / TV;          // (W % 32 == 0: a tile is 32 consecutive voxels of one row)
@@ -1296,9 +1265,9 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
           dstp[b][r] = dx + ((long long)n * Cin + (c < Cin ? c : 0)) * spatial + vbase + b * 16 + li;
           old[b][r] = rmw ? *dstp[b][r] : 0.f;
         }
-      f32x4 acc[TV / 16];
+      f32x4_t acc[TV / 16];
 #pragma unroll
-      for (int b = 0; b < TV / 16; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < TV / 16; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
       // B fragment: voxel 16 b + li, k = 32 kb + 8 lk .. + 7
       const unsigned char* bp = ds + li * S + lk * 16;
       bf16x8_t bf[2][TV / 16][NP];

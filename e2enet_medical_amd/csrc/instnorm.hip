@@ -2,6 +2,7 @@
 // Reference semantics: nn.InstanceNorm3d(eps=1e-5, affine=True, instance statistics in train and eval) followed
 // by nn.LeakyReLU(0.01) (unetpp_d.py:99-100,111); backward = autograd of the same.
 #include "e2e_common.h"
+#include "e2e_split.h"
 
 namespace {
 
@@ -65,10 +66,9 @@ __global__ __launch_bounds__(256) void in_finalize_kernel(const double* __restri
 #ifndef IN_BWD_VARIANT
 #define IN_BWD_VARIANT 1      // A/B builds (tools/scratch/r06_k7.sh, profiles/r06_k7_ab.txt): 1 two chunks per iteration in the apply pass (+1.5 %), 2 nontemporal loads of y there (its last use: no effect)
 #endif
-typedef float fvec4 __attribute__((ext_vector_type(4)));
-#define IN_LD(p) (*reinterpret_cast<const fvec4*>(p))
+#define IN_LD(p) (*reinterpret_cast<const e2e::f32x4_t*>(p))
 #if IN_BWD_VARIANT & 2
-#define IN_LDY(p) __builtin_nontemporal_load(reinterpret_cast<const fvec4*>(p))
+#define IN_LDY(p) __builtin_nontemporal_load(reinterpret_cast<const e2e::f32x4_t*>(p))
 #else
 #define IN_LDY(p) IN_LD(p)
 #endif
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(float* __restrict__ d
   // two chunks per iteration: four loads in flight per thread
   if (vec) {
     for (; i + stride < spatial; i += 2 * stride) {
-      const fvec4 a0 = IN_LD(dzp + i), q0 = IN_LDY(yp + i), a1 = IN_LD(dzp + i + stride), q1 = IN_LDY(yp + i + stride);
-      fvec4 o0, o1;
+      const e2e::f32x4_t a0 = IN_LD(dzp + i), q0 = IN_LDY(yp + i), a1 = IN_LD(dzp + i + stride), q1 = IN_LDY(yp + i + stride);
+      e2e::f32x4_t o0, o1;
       float part = 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -200,16 +200,16 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(float* __restrict__ d
 #pragma unroll
       for (int k = 0; k < 4; ++k) { part += o1[k]; amax = fmaxf(amax, fabsf(o1[k])); }
       acc += part;
-      *reinterpret_cast<fvec4*>(dzp + i) = o0;
-      *reinterpret_cast<fvec4*>(dzp + i + stride) = o1;
+      *reinterpret_cast<e2e::f32x4_t*>(dzp + i) = o0;
+      *reinterpret_cast<e2e::f32x4_t*>(dzp + i + stride) = o1;
     }
   }
 #endif
   for (; i < spatial; i += stride) {
     float dv[4], yv[4], o[4];
     if (vec) {
-      const fvec4 a = IN_LD(dzp + i);
-      const fvec4 q = IN_LDY(yp + i);
+      const e2e::f32x4_t a = IN_LD(dzp + i);
+      const e2e::f32x4_t q = IN_LDY(yp + i);
       dv[0] = a[0]; dv[1] = a[1]; dv[2] = a[2]; dv[3] = a[3];
       yv[0] = q[0]; yv[1] = q[1]; yv[2] = q[2]; yv[3] = q[3];
     } else {

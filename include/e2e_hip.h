@@ -241,9 +241,11 @@ int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, float* dw, vo
                       const unsigned* x_absmax, void* stream);
 
 /* Diagnostic (the numerics gate of the split-operand matrix paths, tests/test_gpu_ops.py): D[32][32] = A[32][K] Bt[32][K]^T through the
- * split functions and product orders of the matrix-pipe kernels.  mode 0: bf16 three-piece operands, six products; 1: fp16 two-piece
- * operands, three products, Bt pre-scaled by the power of two derived from *absmax_b (NULL: unscaled) exactly as dy is in
- * e2e_conv133_wgrad; 2: fp32-input MFMA (an fp32 FMA chain).  K % 16 == 0.  No reference counterpart (torch computes in fp32). */
+ * split functions of csrc/e2e_split.h and the product orders of the matrix-pipe kernels.  mode 0: bf16 three-piece operands, six
+ * products (the bf16 weight gradient K6b, the bf16 transposed convs, the dense conv K1d); 1: fp16 two-piece operands split by
+ * convert-and-subtract, three products, Bt pre-scaled by the power of two derived from *absmax_b (NULL: unscaled) exactly as dy is
+ * in e2e_conv133_wgrad (the fp16 weight gradient K6b); 2: fp32-input MFMA (an fp32 FMA chain: the fp32 kernels); 3: as 1 with the
+ * fma-mix split (K1m, the fp16 transposed convs).  K % 16 == 0.  No reference counterpart (torch computes in fp32). */
 int e2e_diag_split_gemm(const float* A, const float* Bt, float* D, int K, int mode, const unsigned* absmax_b, void* stream);
 
 /* Diagnostic: the shader clock the hot kernels ran at.  Workgroup 0 of every launch of family 0 (K1m, conv133_mm) / 1 (the

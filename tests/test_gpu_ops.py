@@ -620,11 +620,13 @@ def test_conv133_wgrad_h2_and_bf3_vs_fp64(tag, B, src_desc, cout, dims):
 @pytest.mark.parametrize("dist", ["uniform", "act_x_grad", "positive"])
 def test_split_operand_products_vs_fp64(K, dist):
     """The numerics gate of the matrix-pipe paths (round 5: moved here from tools/scratch/bf3_numerics.hip): a product rebuilt
-    from bf16 three-piece operands (six products) and from fp16 two-piece operands (three products, the gradient-like operand
-    scaled from its max) through the library's own split functions, against fp64, beside the fp32-input MFMA (a plain fp32 FMA
-    chain = what an fp32 kernel computes).  Bars: rms error / sum |a b| no more than 1.5x the fp32 chain's (measured 0.6-1.1x;
-    the accumulation in one fp32 chain dominates all three) and, for the fp16 form the hot kernels use, no bias beyond it on
-    one-signed operands (the bf16 form has one there: see below)."""
+    from split operands through the library's own split functions (csrc/e2e_split.h), against fp64, beside the fp32-input MFMA.
+    Modes: "bf16x3" bf16 three-piece operands, six products (the bf16 weight gradient K6b, the bf16 transposed convs, the dense
+    conv K1d); "fp16x2" fp16 two-piece operands split by convert-and-subtract, three products, the gradient-like operand scaled
+    from its max (the fp16 weight gradient K6b); "fp32" a plain fp32 FMA chain (what an fp32 kernel computes); "fp16x2_fma" the
+    same as "fp16x2" with the fma-mix split (K1m, the fp16 transposed convs).  Bars: rms error / sum |a b| no more than 1.5x the
+    fp32 chain's (measured 0.6-1.1x; the accumulation in one fp32 chain dominates all of them) and, for the fp16 forms the hot
+    kernels use, no bias beyond it on one-signed operands (the bf16 form has one there: see below)."""
     from e2enet_medical_amd._lib import lib
     g = torch.Generator().manual_seed(11 + K)
     if dist == "uniform":
@@ -640,15 +642,18 @@ def test_split_operand_products_vs_fp64(K, dist):
     mag = a.double().abs() @ b.double().abs().t()
     ad, bd = a.cuda(), b.cuda()
     word = _absmax_word(bd)
-    out = {}
-    for mode, name in ((0, "bf16x3"), (1, "fp16x2"), (2, "fp32")):
+    out, res = {}, {}
+    for mode, name in ((0, "bf16x3"), (1, "fp16x2"), (2, "fp32"), (3, "fp16x2_fma")):
         d = torch.empty((32, 32), device="cuda")
         lib().diag_split_gemm(ad.data_ptr(), bd.data_ptr(), d.data_ptr(), K, mode, word.data_ptr(), 0)
-        err = (d.cpu().double() - ref) / mag
+        res[name] = d.cpu()
+        err = (res[name].double() - ref) / mag
         out[name] = (float(err.pow(2).mean().sqrt()), float(err.mean()), float(err.abs().max()))
         assert torch.isfinite(d).all()
     print("K %d %s: rms / mean / max of err / sum|ab|: %s" % (K, dist, out))
-    for name in ("bf16x3", "fp16x2"):
+    # the two fp16 split forms round the same exact difference: the same pieces, the same products
+    assert torch.equal(res["fp16x2"], res["fp16x2_fma"])
+    for name in ("bf16x3", "fp16x2", "fp16x2_fma"):
         if name == "bf16x3" and dist == "positive":
             # one-signed operands grow ONE fp32 accumulator monotonically; the bf16 third pieces' products (2^-16 of a product)
             # fall below half an ulp of it once it holds ~2^8 products and are lost one by one: a bias of -2^-17 = -7.6e-6 of the
