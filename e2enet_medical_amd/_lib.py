@@ -151,6 +151,10 @@ SIGNATURES = {
     "e2e_dc_ce_grad": (I, [P, P, P, F, I, F, P, P, I, I, LL, P]),
     "e2e_dc_ce_fold_batch": (I, [P, I, I, P]),
     "e2e_online_eval_counts": (I, [P, P, P, I, I, LL, P]),
+    "e2e_dc_bce_reduce": (I, [P, P, P, P, I, I, LL, P]),
+    "e2e_dc_bce_grad": (I, [P, P, P, P, F, I, F, P, P, I, I, LL, P]),
+    "e2e_online_eval_regions": (I, [P, P, P, P, I, I, LL, P]),
+    "e2e_seg_to_regions": (I, [P, P, P, I, I, LL, P]),
     "e2e_ds_target_gather": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "e2e_grad_sqnorm": (I, [P, I, P, P]),
     "e2e_sgd_clip_mask_step": (I, [P, I, P, F, F, F, F, I, I, P]),

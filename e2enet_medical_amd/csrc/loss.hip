@@ -262,7 +262,7 @@ extern "C" int e2e_dc_ce_grad(const float* logits, const float* target, const vo
 
 extern "C" int e2e_dc_ce_fold_batch(void* acc, int B, int K, void* stream) {
   E2E_REQUIRE(acc, "dc_ce_fold_batch: null pointer");
-  E2E_REQUIRE(B > 0 && K > 1 && K <= KMAX, "dc_ce_fold_batch: need 2 <= K <= 32");
+  E2E_REQUIRE(B > 0 && K >= 1 && K <= KMAX, "dc_ce_fold_batch: need 1 <= K <= 32");     // (K = 1: a single region, K8r)
   hipLaunchKernelGGL(dc_ce_fold_batch_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, (double*)acc, B, K);
   return e2e::check_launch("dc_ce_fold_batch_kernel");
 }
@@ -277,6 +277,386 @@ extern "C" int e2e_online_eval_counts(const float* logits, const float* target, 
   DISPATCH_LK(K, hipLaunchKernelGGL((online_eval_kernel<KB>), grid, dim3(256), 0, st, logits, target,
                                     (unsigned long long*)counts, K, spatial));
   return e2e::check_launch("online_eval_kernel");
+}
+
+// ---- K8r: sigmoid + soft-Dice + binary cross-entropy over overlapping label regions (gfx950) ----
+// Reference: DC_and_BCE_loss (dice_loss.py:362-387) = BCEWithLogitsLoss() + SoftDiceLoss(sigmoid, batch_dice, do_bg=True,
+// smooth), the loss of nnUNetTrainerV2BraTSRegions.  Every region r is a binary problem of its own: p = sigmoid(l_r),
+// y_r in {0, 1}.  acc layout as K8: [B][R][3] (tp, fp, fn) followed by one BCE sum, so e2e_dc_ce_fold_batch serves it too.
+// Targets come in two forms (template LABELS):
+//   true : a [B,1,spatial] label map and one word per region, bit t of words[r] = "label t belongs to region r"; y_r is
+//          formed on load and no R-channel target exists in HBM (ConvertSegmentationToRegionsTransform, custom_transforms.py:96-123,
+//          fused: labels outside [0, 32) or not whole numbers belong to no region, as in its `seg == l` loop)
+//   false: a [B,R,spatial] multi-hot float tensor, y = (value >= 0.5)
+// Both forms run the same arithmetic in the same order on the same y, so their results agree bit for bit.
+// A thread owns groups of four consecutive voxels (one dwordx4 per plane where the planes are 16-byte aligned, four guarded
+// dword loads otherwise -- the order of the sums does not depend on which), flushes its fp32 partials to fp64 every 8 groups
+// = 32 voxels, then wave sum, block sum and one fp64 atomic per block and accumulator, as K8.
+namespace {
+struct Quad { float v[4]; };
+
+template <bool VEC>
+__device__ __forceinline__ Quad load_quad(const float* __restrict__ row, long long v0, long long spatial, float fill) {
+  Quad q;
+  if (VEC) {                                 // spatial % 4 == 0: the whole group is inside the plane
+    const float4 t = *reinterpret_cast<const float4*>(row + v0);
+    q.v[0] = t.x; q.v[1] = t.y; q.v[2] = t.z; q.v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q.v[j] = (v0 + j < spatial) ? row[v0 + j] : fill;
+  }
+  return q;
+}
+
+__device__ __forceinline__ unsigned label_bit(float f) {
+  const int t = (int)f;
+  return ((unsigned)t < 32u && (float)t == f) ? (1u << t) : 0u;
+}
+
+// y of the four voxels of a group for region r: bit j of the result
+template <bool LABELS, bool VEC>
+__device__ __forceinline__ unsigned region_hits(const float* __restrict__ tgt, const unsigned lbits[4], unsigned word, int r,
+                                                long long v0, long long spatial) {
+  unsigned y = 0;
+  if (LABELS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y |= (lbits[j] & word) ? (1u << j) : 0u;
+  } else {
+    const Quad t = load_quad<VEC>(tgt + (long long)r * spatial, v0, spatial, 0.f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y |= (t.v[j] >= 0.5f) ? (1u << j) : 0u;
+  }
+  return y;
+}
+
+// p = sigmoid(l) and sp = log1p(exp(-|l|)), the softplus tail of BCEWithLogits, from one exponential and one division.
+// log1p(e) = log(u) + (e - (u - 1)) / u with u = fl(1 + e): the second term restores what the rounding of 1 + e lost, so the
+// sum keeps log1pf's precision where e is tiny (measured on 2 x 3 x 128^3: log1pf itself cost a third of the reduction)
+__device__ __forceinline__ float sigmoid_parts(float l, float& sp) {
+  const float e = expf(-fabsf(l));            // in (0, 1]: no overflow at any logit
+  const float u = 1.f + e;
+  const float inv = 1.f / u;
+  sp = logf(u) + (e - (u - 1.f)) * inv;
+  return l >= 0.f ? inv : e * inv;
+}
+
+template <int RB, bool LABELS, bool VEC>
+__global__ __launch_bounds__(256) void dc_bce_reduce_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                            const unsigned* __restrict__ words, double* __restrict__ acc, int R,
+                                                            long long spatial) {
+  const int n = blockIdx.y;
+  const float* lp = logits + (long long)n * R * spatial;
+  const float* tg = target + (long long)n * (LABELS ? 1 : R) * spatial;
+  unsigned wd[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) wd[r] = (LABELS && r < R) ? words[r] : 0u;
+  float tp[RB], fp[RB], fn[RB];
+  double dtp[RB], dfp[RB], dfn[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) { tp[r] = 0.f; fp[r] = 0.f; fn[r] = 0.f; dtp[r] = 0.0; dfp[r] = 0.0; dfn[r] = 0.0; }
+  double bce = 0.0;
+  int it = 0;
+  const long long groups = (spatial + 3) >> 2;
+  for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long long)gridDim.x * 256) {
+    const long long v0 = gi << 2;
+    unsigned lbits[4] = {0u, 0u, 0u, 0u};
+    unsigned valid = 15u;
+    if (!VEC) valid = (spatial - v0 >= 4) ? 15u : ((1u << (int)(spatial - v0)) - 1u);
+    if (LABELS) {
+      const Quad t = load_quad<VEC>(tg, v0, spatial, -1.f);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lbits[j] = label_bit(t.v[j]);
+    }
+    float bsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      if (r < R) {
+        const Quad l = load_quad<VEC>(lp + (long long)r * spatial, v0, spatial, 0.f);
+        const unsigned y = region_hits<LABELS, VEC>(tg, lbits, wd[r], r, v0, spatial);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (valid & (1u << j)) {
+            float sp;
+            const float p = sigmoid_parts(l.v[j], sp);
+            const bool hit = (y >> j) & 1u;
+            // BCEWithLogits, stable form: max(l, 0) - l y + log1p(exp(-|l|))
+            bsum += fmaxf(l.v[j], 0.f) - (hit ? l.v[j] : 0.f) + sp;
+            if (hit) { tp[r] += p; fn[r] += 1.f - p; }
+            else fp[r] += p;
+          }
+        }
+      }
+    }
+    bce += (double)bsum;
+    if ((++it & 7) == 0) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        dtp[r] += tp[r]; dfp[r] += fp[r]; dfn[r] += fn[r];
+        tp[r] = 0.f; fp[r] = 0.f; fn[r] = 0.f;
+      }
+    }
+  }
+  __shared__ double sh[4][3 * RB + 1];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    const double a = e2e::wave_sum_d(dtp[r] + (double)tp[r]);
+    const double b = e2e::wave_sum_d(dfp[r] + (double)fp[r]);
+    const double c = e2e::wave_sum_d(dfn[r] + (double)fn[r]);
+    if (lane == 0) { sh[wave][3 * r] = a; sh[wave][3 * r + 1] = b; sh[wave][3 * r + 2] = c; }
+  }
+  bce = e2e::wave_sum_d(bce);
+  if (lane == 0) sh[wave][3 * RB] = bce;
+  __syncthreads();
+  if (threadIdx.x < 3 * R) {
+    const int i = threadIdx.x;
+    atomicAdd(&acc[(long long)n * R * 3 + i], sh[0][i] + sh[1][i] + sh[2][i] + sh[3][i]);
+  }
+  if (threadIdx.x == 255) atomicAdd(&acc[(long long)gridDim.y * R * 3], sh[0][3 * RB] + sh[1][3 * RB] + sh[2][3 * RB] + sh[3][3 * RB]);
+}
+
+// gradient: dlogit_r = weight * [ (p_r - y_r) / (B * R * spatial) + p_r (1 - p_r) g_r ],
+// g_r = dDiceLoss/dp_r = y_r ? -(2*Dn - N)/(Dn^2 M) : N/(Dn^2 M),  N = 2tp + s, Dn = 2tp + fp + fn + s + 1e-8,
+// M = number of dice terms (batch_dice: R, else B*R): every region counts, there is no background to drop.
+// A region absent from a sample (smooth = 0) has N = 0: dc = 0 and g = 0 on all its voxels (y = 0 everywhere), all finite.
+template <int RB, bool LABELS, bool VEC>
+__global__ __launch_bounds__(256) void dc_bce_grad_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                          const unsigned* __restrict__ words, const double* __restrict__ acc,
+                                                          float weight, int batch_dice, float smooth, float* __restrict__ dlogits,
+                                                          float* __restrict__ loss_out, int B, int R, long long spatial) {
+  const int n = blockIdx.y;
+  __shared__ float g_hit[RB], g_miss[RB];
+  if (threadIdx.x < RB) {
+    const int r = threadIdx.x;
+    float gh = 0.f, gm = 0.f;
+    if (r < R) {
+      double tp = 0, fp = 0, fn = 0;
+      if (batch_dice) {
+        for (int b = 0; b < B; ++b) {
+          tp += acc[((long long)b * R + r) * 3]; fp += acc[((long long)b * R + r) * 3 + 1]; fn += acc[((long long)b * R + r) * 3 + 2];
+        }
+      } else {
+        tp = acc[((long long)n * R + r) * 3]; fp = acc[((long long)n * R + r) * 3 + 1]; fn = acc[((long long)n * R + r) * 3 + 2];
+      }
+      const double N = 2 * tp + smooth, Dn = 2 * tp + fp + fn + smooth + 1e-8;
+      const double M = batch_dice ? (double)R : (double)B * R;
+      gh = (float)(-(2 * Dn - N) / (Dn * Dn) / M);
+      gm = (float)(N / (Dn * Dn) / M);
+    }
+    g_hit[r] = gh;
+    g_miss[r] = gm;
+  }
+  if (blockIdx.x == 0 && n == 0 && threadIdx.x == 0) {
+    // loss value: weight * (mean BCE - mean dice)
+    double dsum = 0.0;
+    if (batch_dice) {
+      for (int r = 0; r < R; ++r) {
+        double tp = 0, fp = 0, fn = 0;
+        for (int b = 0; b < B; ++b) {
+          tp += acc[((long long)b * R + r) * 3]; fp += acc[((long long)b * R + r) * 3 + 1]; fn += acc[((long long)b * R + r) * 3 + 2];
+        }
+        dsum += (2 * tp + smooth) / (2 * tp + fp + fn + smooth + 1e-8);
+      }
+      dsum /= (double)R;
+    } else {
+      for (int i = 0; i < B * R; ++i) {
+        const double tp = acc[(long long)i * 3], fp = acc[(long long)i * 3 + 1], fn = acc[(long long)i * 3 + 2];
+        dsum += (2 * tp + smooth) / (2 * tp + fp + fn + smooth + 1e-8);
+      }
+      dsum /= (double)B * R;
+    }
+    const double bce = acc[(long long)B * R * 3] / ((double)B * (double)R * (double)spatial);
+    *loss_out += (float)(weight * (bce - dsum));
+  }
+  __syncthreads();
+  if (dlogits == nullptr) return;                      // value only (validation batches)
+  const float inv_cnt = 1.f / ((float)B * (float)R * (float)spatial);
+  const float* lp = logits + (long long)n * R * spatial;
+  float* dp = dlogits + (long long)n * R * spatial;
+  const float* tg = target + (long long)n * (LABELS ? 1 : R) * spatial;
+  unsigned wd[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) wd[r] = (LABELS && r < R) ? words[r] : 0u;
+  const long long groups = (spatial + 3) >> 2;
+  for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long long)gridDim.x * 256) {
+    const long long v0 = gi << 2;
+    unsigned lbits[4] = {0u, 0u, 0u, 0u};
+    if (LABELS) {
+      const Quad t = load_quad<VEC>(tg, v0, spatial, -1.f);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lbits[j] = label_bit(t.v[j]);
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      if (r < R) {
+        const Quad l = load_quad<VEC>(lp + (long long)r * spatial, v0, spatial, 0.f);
+        const unsigned y = region_hits<LABELS, VEC>(tg, lbits, wd[r], r, v0, spatial);
+        float d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float sp;
+          const float p = sigmoid_parts(l.v[j], sp);
+          const bool hit = (y >> j) & 1u;
+          d[j] = weight * ((p - (hit ? 1.f : 0.f)) * inv_cnt + p * (1.f - p) * (hit ? g_hit[r] : g_miss[r]));
+        }
+        float* row = dp + (long long)r * spatial;
+        if (VEC) {
+          *reinterpret_cast<float4*>(row + v0) = make_float4(d[0], d[1], d[2], d[3]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (v0 + j < spatial) row[v0 + j] = d[j];
+        }
+      }
+    }
+  }
+}
+
+// online evaluation of a region model (reference nnUNetTrainerV2BraTSRegions.run_online_evaluation, :168-189): hard tp / fp / fn
+// per region of sigmoid(l) > 0.5 against y, summed over the batch.  sigmoid(l) > 0.5 <=> l > 0 (a logit of exactly 0 is a
+// negative); the sign is tested, so the count does not hang on the last ulp of an exponential.
+template <int RB, bool LABELS, bool VEC>
+__global__ __launch_bounds__(256) void online_eval_regions_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                                  const unsigned* __restrict__ words,
+                                                                  unsigned long long* __restrict__ counts, int R, long long spatial) {
+  __shared__ unsigned int h[RB][3];
+  for (int i = threadIdx.x; i < 3 * RB; i += 256) (&h[0][0])[i] = 0u;
+  __syncthreads();
+  const int n = blockIdx.y;
+  const float* lp = logits + (long long)n * R * spatial;
+  const float* tg = target + (long long)n * (LABELS ? 1 : R) * spatial;
+  unsigned wd[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) wd[r] = (LABELS && r < R) ? words[r] : 0u;
+  unsigned c[RB];                                      // packed per-thread counts: tp | fp << 10 | fn << 20 (at most 4 * 128 each)
+#pragma unroll
+  for (int r = 0; r < RB; ++r) c[r] = 0u;
+  int it = 0;
+  const long long groups = (spatial + 3) >> 2;
+  for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long long)gridDim.x * 256) {
+    const long long v0 = gi << 2;
+    unsigned lbits[4] = {0u, 0u, 0u, 0u};
+    unsigned valid = 15u;
+    if (!VEC) valid = (spatial - v0 >= 4) ? 15u : ((1u << (int)(spatial - v0)) - 1u);
+    if (LABELS) {
+      const Quad t = load_quad<VEC>(tg, v0, spatial, -1.f);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lbits[j] = label_bit(t.v[j]);
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      if (r < R) {
+        const Quad l = load_quad<VEC>(lp + (long long)r * spatial, v0, spatial, 0.f);
+        const unsigned y = region_hits<LABELS, VEC>(tg, lbits, wd[r], r, v0, spatial) & valid;
+        unsigned pos = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pos |= (l.v[j] > 0.f) ? (1u << j) : 0u;
+        pos &= valid;
+        c[r] += __popc(pos & y) + (__popc(pos & ~y) << 10) + (__popc(~pos & y) << 20);
+      }
+    }
+    if ((++it & 127) == 0) {                           // 128 groups: a field holds at most 512 < 1024
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        if (r < R && c[r]) {
+          if (c[r] & 1023u) atomicAdd(&h[r][0], c[r] & 1023u);
+          if ((c[r] >> 10) & 1023u) atomicAdd(&h[r][1], (c[r] >> 10) & 1023u);
+          if (c[r] >> 20) atomicAdd(&h[r][2], c[r] >> 20);
+        }
+        c[r] = 0u;
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    if (r < R && c[r]) {
+      if (c[r] & 1023u) atomicAdd(&h[r][0], c[r] & 1023u);
+      if ((c[r] >> 10) & 1023u) atomicAdd(&h[r][1], (c[r] >> 10) & 1023u);
+      if (c[r] >> 20) atomicAdd(&h[r][2], c[r] >> 20);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * R; i += 256)
+    if ((&h[0][0])[i]) atomicAdd(&counts[i], (unsigned long long)(&h[0][0])[i]);
+}
+
+// ConvertSegmentationToRegionsTransform (custom_transforms.py:96-123) for callers who want its output: label map
+// [B,1,spatial] -> multi-hot [B,R,spatial] float 0/1
+__global__ __launch_bounds__(256) void seg_to_regions_kernel(const float* __restrict__ seg, const unsigned* __restrict__ words,
+                                                             float* __restrict__ out, int R, long long spatial) {
+  const int n = blockIdx.y;
+  const float* sp = seg + (long long)n * spatial;
+  float* op = out + (long long)n * R * spatial;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < spatial; v += (long long)gridDim.x * 256) {
+    const unsigned bit = label_bit(sp[v]);
+    for (int r = 0; r < R; ++r) op[(long long)r * spatial + v] = (bit & words[r]) ? 1.f : 0.f;
+  }
+}
+
+inline bool quad_aligned(const void* a, const void* b, const void* c, long long spatial) {
+  return (spatial & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
+}
+}  // namespace
+
+// region count -> register block, target form and load width -> template instance
+#define DISPATCH_REGIONS(R, labels, vec, ...)                                        \
+  DISPATCH_LK(R, {                                                                   \
+    constexpr int RB = KB;                                                           \
+    if (labels) {                                                                    \
+      if (vec) { constexpr bool LABELS = true, VEC = true; __VA_ARGS__; }            \
+      else { constexpr bool LABELS = true, VEC = false; __VA_ARGS__; }               \
+    } else {                                                                         \
+      if (vec) { constexpr bool LABELS = false, VEC = true; __VA_ARGS__; }           \
+      else { constexpr bool LABELS = false, VEC = false; __VA_ARGS__; }              \
+    }                                                                                \
+  })
+
+extern "C" int e2e_dc_bce_reduce(const float* logits, const float* target, const unsigned* region_words, void* acc, int B, int R,
+                                 long long spatial, void* stream) {
+  E2E_REQUIRE(logits && target && acc, "dc_bce_reduce: null pointer");
+  E2E_REQUIRE(B > 0 && R >= 1 && R <= KMAX && spatial > 0, "dc_bce_reduce: need 1 <= R <= 32");
+  hipStream_t st = (hipStream_t)stream;
+  e2e::zero_async(acc, (size_t)e2e_loss_ws_bytes(B, R), st);
+  dim3 grid(loss_blocks(spatial), B);
+  const bool labels = region_words != nullptr, vec = quad_aligned(logits, target, nullptr, spatial);
+  DISPATCH_REGIONS(R, labels, vec, hipLaunchKernelGGL((dc_bce_reduce_kernel<RB, LABELS, VEC>), grid, dim3(256), 0, st, logits, target,
+                                                      region_words, (double*)acc, R, spatial));
+  return e2e::check_launch("dc_bce_reduce_kernel");
+}
+
+extern "C" int e2e_dc_bce_grad(const float* logits, const float* target, const unsigned* region_words, const void* acc,
+                               float weight, int batch_dice, float smooth, float* dlogits, float* loss_out, int B, int R,
+                               long long spatial, void* stream) {
+  E2E_REQUIRE(logits && target && acc && loss_out, "dc_bce_grad: null pointer");
+  E2E_REQUIRE(B > 0 && R >= 1 && R <= KMAX && spatial > 0, "dc_bce_grad: need 1 <= R <= 32");
+  dim3 grid(dlogits ? loss_blocks(spatial) : 1u, dlogits ? B : 1);
+  const bool labels = region_words != nullptr, vec = quad_aligned(logits, target, dlogits, spatial);
+  DISPATCH_REGIONS(R, labels, vec, hipLaunchKernelGGL((dc_bce_grad_kernel<RB, LABELS, VEC>), grid, dim3(256), 0, (hipStream_t)stream,
+                                                      logits, target, region_words, (const double*)acc, weight, batch_dice, smooth,
+                                                      dlogits, loss_out, B, R, spatial));
+  return e2e::check_launch("dc_bce_grad_kernel");
+}
+
+extern "C" int e2e_online_eval_regions(const float* logits, const float* target, const unsigned* region_words, long long* counts,
+                                       int B, int R, long long spatial, void* stream) {
+  E2E_REQUIRE(logits && target && counts, "online_eval_regions: null pointer");
+  E2E_REQUIRE(B > 0 && R >= 1 && R <= KMAX && spatial > 0, "online_eval_regions: need 1 <= R <= 32");
+  hipStream_t st = (hipStream_t)stream;
+  e2e::zero_async(counts, (size_t)R * 3 * sizeof(long long), st);
+  dim3 grid(loss_blocks(spatial), B);
+  const bool labels = region_words != nullptr, vec = quad_aligned(logits, target, nullptr, spatial);
+  DISPATCH_REGIONS(R, labels, vec, hipLaunchKernelGGL((online_eval_regions_kernel<RB, LABELS, VEC>), grid, dim3(256), 0, st, logits,
+                                                      target, region_words, (unsigned long long*)counts, R, spatial));
+  return e2e::check_launch("online_eval_regions_kernel");
+}
+
+extern "C" int e2e_seg_to_regions(const float* seg, const unsigned* region_words, float* out, int B, int R, long long spatial,
+                                  void* stream) {
+  E2E_REQUIRE(seg && region_words && out, "seg_to_regions: null pointer");
+  E2E_REQUIRE(B > 0 && R >= 1 && R <= KMAX && spatial > 0, "seg_to_regions: need 1 <= R <= 32");
+  hipLaunchKernelGGL(seg_to_regions_kernel, dim3(loss_blocks(spatial), B), dim3(256), 0, (hipStream_t)stream, seg, region_words, out,
+                     R, spatial);
+  return e2e::check_launch("seg_to_regions_kernel");
 }
 
 

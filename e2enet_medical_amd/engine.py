@@ -766,6 +766,8 @@ class Engine:
         self.maps_generation = 0           # bumped when the liveness tables are replaced (their pointers are baked into a graph)
         self._sparse_jobs = None           # pack-job table of the load-balanced convs (rebuilt with the kernel maps)
         self._tgt_static = None
+        self._tgt_static_regions = {}      # (head, multi-hot?) -> staging buffer of a region target (graph replay)
+        self._region_words_dev = {}        # region words -> their device copy
         self._mm_tables = {}               # directions -> (dispatch key, device job table, njobs, max elems)
         self._mm_packed = {}               # direction -> weights key its packed buffers were built from
         self._range_table = None           # (device job table, njobs) of e2e_conv133_input_ranges
@@ -1264,11 +1266,13 @@ class Engine:
                                        device=self.device)
             self.loss_val = torch.zeros(1, dtype=torch.float32, device=self.device)
 
-    def _loss(self, targets, weights, batch_dice, smooth, with_grad):
+    def _loss(self, targets, weights, batch_dice, smooth, with_grad, regions=None):
         L = lib()
         self._loss_buffers()
         self.loss_val.zero_()
         k = self.cfg.num_classes
+        if regions is not None:
+            return self._loss_regions(targets, weights, batch_dice, smooth, with_grad, regions)
         for i, h in enumerate(self.heads):
             wgt = float(weights[i]) if i < len(weights) else 0.0
             if wgt == 0.0 or not h.active:
@@ -1288,10 +1292,64 @@ class Engine:
                          h.src.spatial, _stream())
         return self.loss_val
 
-    def loss_backward(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5):
+    # ---- overlapping label regions (reference nnUNetTrainerV2BraTSRegions: DC_and_BCE_loss over sigmoid heads) ----
+    def _region_words(self, regions):
+        """regions: one int per head channel, bit t = "label t belongs to this region" (custom_transforms.region_words).
+        Returns (the words as a tuple, their device copy)."""
+        words = tuple(int(w) & 0xFFFFFFFF for w in regions)
+        if len(words) != self.cfg.num_classes:
+            raise ValueError("%d regions for a network with %d output channels" % (len(words), self.cfg.num_classes))
+        cache = self._region_words_dev
+        dev = cache.get(words)
+        if dev is None:
+            dev = cache[words] = torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32,
+                                              device=self.device)
+        return words, dev
+
+    def _region_form(self, t, spatial):
+        """True: `t` is a multi-hot [B,R,...] target; False: a [B,1,...] label map.  One channel is always a label map."""
+        r = self.cfg.num_classes
+        if t.numel() == self.batch * spatial:
+            return False
+        if r > 1 and t.numel() == self.batch * r * spatial:
+            return True
+        raise ValueError("region target of %d elements: expected a label map [%d,1,...] or a multi-hot tensor [%d,%d,...] over %d "
+                         "voxels" % (t.numel(), self.batch, self.batch, r, spatial))
+
+    def _loss_regions(self, targets, weights, batch_dice, smooth, with_grad, regions):
+        L = lib()
+        r = self.cfg.num_classes
+        _, words = self._region_words(regions)
+        for i, h in enumerate(self.heads):
+            wgt = float(weights[i]) if i < len(weights) else 0.0
+            if wgt == 0.0 or not h.active:
+                if with_grad:
+                    h.out.grad.zero_()
+                continue
+            t = targets[i]
+            wp = None if self._region_form(t, h.src.spatial) else words.data_ptr()
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            L.dc_bce_reduce(h.out.data.data_ptr(), t.data_ptr(), wp, self.loss_ws.data_ptr(), self.batch, r, h.src.spatial,
+                            _stream())
+            if batch_dice and self.batch_dice_hook is not None:
+                L.dc_ce_fold_batch(self.loss_ws.data_ptr(), self.batch, r, _stream())
+                self.batch_dice_hook(self.loss_ws[:3 * r])
+            L.dc_bce_grad(h.out.data.data_ptr(), t.data_ptr(), wp, self.loss_ws.data_ptr(), wgt, 1 if batch_dice else 0,
+                          smooth, h.out.grad.data_ptr() if with_grad else None, self.loss_val.data_ptr(), self.batch, r,
+                          h.src.spatial, _stream())
+        return self.loss_val
+
+    def loss_backward(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5,
+                      regions=None):
         """Deep-supervision Dice+CE loss (reference MultipleOutputLoss2(DC_and_CE_loss), deep_supervision.py:31-43)
-        and the full backward pass.  targets[i]: [B,1,...] float labels at scale i.  Returns the device loss scalar."""
+        and the full backward pass.  targets[i]: [B,1,...] float labels at scale i.  Returns the device loss scalar.
+
+        regions (one word per head channel, see custom_transforms.region_words): the heads are sigmoid region outputs and the
+        loss is MultipleOutputLoss2(DC_and_BCE_loss) (dice_loss.py:362-387).  targets[i] is then the same [B,1,...] label map
+        (the region targets are formed from it on load) or, with more than one region, a multi-hot [B,R,...] tensor."""
         self.prepare_backward()
+        if regions is not None:
+            return self._loss_backward_regions(targets, weights, batch_dice, smooth, regions)
         if not self._graph_ok():
             self._loss(targets, weights, batch_dice, smooth, True)
             self.backward(None)
@@ -1312,17 +1370,56 @@ class Engine:
         self._run(("lossbwd", wkey, bool(batch_dice), float(smooth), active), body)
         return self.loss_val
 
-    def loss_value(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5):
+    def _loss_backward_regions(self, targets, weights, batch_dice, smooth, regions):
+        words, _ = self._region_words(regions)
+        if not self._graph_ok():
+            self._loss(targets, weights, batch_dice, smooth, True, regions=regions)
+            self.backward(None)
+            return self.loss_val
+        # graph replay: as above, with staging buffers per target form; the loss kind, the region words and the target forms are
+        # part of the key, so a softmax graph and a region graph of one engine never replay each other
+        n = min(len(targets), len(self.heads))
+        forms = tuple(self._region_form(targets[i], self.heads[i].src.spatial) for i in range(n))
+        stage = self._tgt_static_regions
+        static = []
+        for i in range(n):
+            buf = stage.get((i, forms[i]))
+            if buf is None:
+                ch = self.cfg.num_classes if forms[i] else 1
+                buf = stage[(i, forms[i])] = torch.empty((self.batch, ch) + tuple(self.heads[i].out.shape[2:]), dtype=torch.float32,
+                                                         device=self.device)
+            buf.copy_(targets[i].reshape(buf.shape))
+            static.append(buf)
+        wkey = tuple(float(weights[i]) if i < len(weights) else 0.0 for i in range(len(self.heads)))
+        active = tuple(h.active for h in self.heads)
+
+        def body():
+            self._loss(static, weights, batch_dice, smooth, True, regions=regions)
+            self.backward(None)
+        self._run(("lossbwd", "dc_bce", words, forms, wkey, bool(batch_dice), float(smooth), active), body)
+        return self.loss_val
+
+    def loss_value(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5, regions=None):
         """The same loss without gradients (validation batches, reference nnUNetTrainer_simple.py:980-988)."""
+        if regions is not None:
+            return self._loss(targets, weights, batch_dice, smooth, False, regions=regions)
         return self._loss(targets, weights, batch_dice, smooth, False)
 
-    def online_eval_counts(self, target: torch.Tensor) -> torch.Tensor:
+    def online_eval_counts(self, target: torch.Tensor, regions=None) -> torch.Tensor:
         """Hard tp/fp/fn voxel counts [K, 3] (int64, device) of the full-resolution prediction against `target`
-        (reference run_online_evaluation, nnUNetTrainer_simple.py:373-405)."""
+        (reference run_online_evaluation, nnUNetTrainer_simple.py:373-405).  With `regions`: per region of sigmoid(logit) > 0.5
+        (nnUNetTrainerV2BraTSRegions.py:168-189); `target` is a label map or a multi-hot tensor as in loss_backward."""
         h = self.heads[0]
         k = self.cfg.num_classes
         if self._eval_counts is None:
             self._eval_counts = torch.zeros((k, 3), dtype=torch.int64, device=self.device)
+        if regions is not None:
+            _, words = self._region_words(regions)
+            wp = None if self._region_form(target, h.src.spatial) else words.data_ptr()
+            assert target.is_cuda and target.dtype == torch.float32 and target.is_contiguous()
+            lib().online_eval_regions(h.out.data.data_ptr(), target.data_ptr(), wp, self._eval_counts.data_ptr(), self.batch, k,
+                                      h.src.spatial, _stream())
+            return self._eval_counts
         assert target.is_cuda and target.dtype == torch.float32 and target.numel() == self.batch * h.src.spatial
         lib().online_eval_counts(h.out.data.data_ptr(), target.data_ptr(), self._eval_counts.data_ptr(), self.batch, k,
                                  h.src.spatial, _stream())

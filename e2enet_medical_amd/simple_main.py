@@ -61,6 +61,16 @@ def build_parser():
     return parser
 
 
+def select_trainer_class(network_trainer):
+    """the reference forces nnUNetTrainer_simple whatever --network_trainer says (simple_main.py:145); the one other trainer of
+    this package, the region trainer nnUNetTrainerV2BraTSRegions, is selected by its name"""
+    if network_trainer == 'nnUNetTrainerV2BraTSRegions':
+        from .training.network_training.competitions_with_custom_Trainers.BraTS2020.nnUNetTrainerV2BraTSRegions import \
+            nnUNetTrainerV2BraTSRegions
+        return nnUNetTrainerV2BraTSRegions
+    return nnUNetTrainer_simple
+
+
 def load_pretrained_weights(network, fname, verbose=False):
     """reference e2enet/run/load_pretrained_weights.py: copy every checkpoint tensor whose name and shape match the network
     (segmentation heads may differ between tasks and are skipped)."""
@@ -89,7 +99,7 @@ def main(argv=None):
         fold = int(fold)
     plans_file, output_folder_name, dataset_directory, batch_dice, stage, trainer_class = \
         get_default_configuration(network, task, args.network_trainer, args.p)
-    trainer_class = nnUNetTrainer_simple                                                 # simple_main.py:145
+    trainer_class = select_trainer_class(args.network_trainer)
     trainer = trainer_class(plans_file, fold, output_folder=output_folder_name, dataset_directory=dataset_directory,
                             batch_dice=batch_dice, stage=stage, unpack_data=not args.use_compressed_data,
                             deterministic=args.deterministic, fp16=not args.fp32, Tconv=args.Tconv,

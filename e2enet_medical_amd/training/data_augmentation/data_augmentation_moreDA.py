@@ -377,8 +377,15 @@ def get_moreDA_augmentation(dataloader_train, dataloader_val, patch_size, params
     """Same signature as the reference (:41-46).  Returns (train generator, validation generator); the validation chain is
     RemoveLabel + target down-sampling only (:152-172)."""
     assert params.get('mirror') is None, "old version of params, use new keyword do_mirror"
-    if soft_ds or regions is not None:
-        raise NotImplementedError("soft deep-supervision targets / region targets are not built")
+    if soft_ds:
+        raise NotImplementedError("soft deep-supervision targets are not built")
+    to_regions = None
+    if regions is not None:
+        # reference :142-143 / :181-182: ConvertSegmentationToRegionsTransform(regions, 'target', 'target') in front of the
+        # deep-supervision down-sampling.  That down-sampling is a nearest-neighbour gather, so converting every gathered scale
+        # gives the same multi-hot targets
+        from .custom_transforms import ConvertSegmentationToRegionsTransform
+        to_regions = ConvertSegmentationToRegionsTransform(regions, 'target', 'target')
     seed = None if seeds_train is None else int(np.asarray(seeds_train).reshape(-1)[0])
     aug = DeviceAugmenter(patch_size, params, border_val_seg, order_seg, order_data, deep_supervision_scales, seed)
 
@@ -394,4 +401,7 @@ def get_moreDA_augmentation(dataloader_train, dataloader_val, patch_size, params
                          int(np.prod(seg.shape[2:])), _stream())            # RemoveLabelTransform(-1, 0)
         tgt = downsample_seg_for_ds_transform2(seg, deep_supervision_scales, order=0) if deep_supervision_scales is not None else seg
         return {"data": data, "target": tgt}
+    if to_regions is not None:
+        return (_DeviceGenerator(dataloader_train, lambda data, seg=None: to_regions(**aug(data, seg))),
+                _DeviceGenerator(dataloader_val, lambda data, seg: to_regions(**val_fn(data, seg))))
     return _DeviceGenerator(dataloader_train, aug), _DeviceGenerator(dataloader_val, val_fn)

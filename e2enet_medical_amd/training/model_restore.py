@@ -7,17 +7,30 @@ import torch
 join, isdir = os.path.join, os.path.isdir
 
 
-def restore_model(pkl_file, checkpoint=None, train=False, fp16=None):
-    """reference :44-99: instantiate the trainer named in ``<checkpoint>.pkl`` with its saved constructor arguments.  The only
-    trainer of this package is ``nnUNetTrainer_simple`` (simple_main.py:145 forces it in the reference as well); a pickle naming
-    another class raises."""
+def trainer_classes():
+    """name -> class of the trainers this package provides"""
     from .network_training.nnUNetTrainer_simple import nnUNetTrainer_simple
+    from .network_training.competitions_with_custom_Trainers.BraTS2020.nnUNetTrainerV2BraTSRegions import \
+        nnUNetTrainerV2BraTSRegions
+    return {c.__name__: c for c in (nnUNetTrainer_simple, nnUNetTrainerV2BraTSRegions)}
+
+
+def recursive_find_python_class(name):
+    """the trainer class called ``name`` or None (the reference walks its training folder, model_restore.py:23-41)"""
+    return trainer_classes().get(name)
+
+
+def restore_model(pkl_file, checkpoint=None, train=False, fp16=None):
+    """reference :44-99: instantiate the trainer named in ``<checkpoint>.pkl`` with its saved constructor arguments.  The trainers
+    of this package are ``nnUNetTrainer_simple`` (simple_main.py:145 forces it in the reference as well) and the region trainer
+    ``nnUNetTrainerV2BraTSRegions``; a pickle naming another class raises."""
     with open(pkl_file, 'rb') as f:
         info = pickle.load(f)
-    if info['name'] != nnUNetTrainer_simple.__name__:
+    trainer_class = recursive_find_python_class(info['name'])
+    if trainer_class is None:
         raise RuntimeError("Could not find the model trainer specified in checkpoint: %r (this package provides %s).\n"
-                           "Debug info: \ncheckpoint file: %s" % (info['name'], nnUNetTrainer_simple.__name__, checkpoint))
-    trainer = nnUNetTrainer_simple(*info['init'])
+                           "Debug info: \ncheckpoint file: %s" % (info['name'], ", ".join(sorted(trainer_classes())), checkpoint))
+    trainer = trainer_class(*info['init'])
     if info.get('e2e_base_num_features') is not None:
         # (the reference hard-codes width 48, nnUNetTrainer_simple.py:296; a trainer of this package that was given another width
         #  records it next to its constructor arguments)

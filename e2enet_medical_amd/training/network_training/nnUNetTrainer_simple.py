@@ -277,9 +277,9 @@ class nnUNetTrainer_simple(object):
                     self.print_to_log_file("WARNING: synthetic_data=True: training on seeded Gaussian noise and random labels "
                                            "(benchmarks and smoke tests only)")
                     self.tr_gen = SyntheticGenerator(self.batch_size, self.num_input_channels, self.patch_size,
-                                                     self.num_classes, scales, seed=0, device=dev)
+                                                     self._num_labels(), scales, seed=0, device=dev)
                     self.val_gen = SyntheticGenerator(self.batch_size, self.num_input_channels, self.patch_size,
-                                                      self.num_classes, scales, seed=1, device=dev)
+                                                      self._num_labels(), scales, seed=1, device=dev)
                 else:
                     raise FileNotFoundError(
                         "no preprocessed data under %r (dataset_directory / plans['data_identifier'] + '_stage%s', reference "
@@ -347,6 +347,19 @@ class nnUNetTrainer_simple(object):
             "non-zero deep-supervision loss weight beyond the network's %d heads" % n
         return min(n, len(self.deep_supervision_scales))
 
+    def _num_labels(self):
+        """how many integer labels a target holds (the network's output channels; a region trainer has other numbers)"""
+        return self.num_classes
+
+    def _engine_loss_kwargs(self):
+        """further arguments of Engine.loss_backward / loss_value for this trainer's loss (a subclass with another loss
+        configuration overrides this: smooth, regions)"""
+        return {}
+
+    def _validation_extra(self, cases, summary_file):
+        """called by validate() behind aggregate_scores with its cases [(prediction, ground truth, prediction file, ground-truth
+        file)] and the summary.json it wrote; a subclass adds its own rows"""
+
     def _rank(self):
         """(rank, world, group) of the data-parallel job; (0, 1, None) for a single process"""
         import torch.distributed as dist
@@ -412,7 +425,7 @@ class nnUNetTrainer_simple(object):
             eng.batch_dice_hook = parallel.batch_dice_allreduce(group)
         eng.forward(data, deep_supervision=True)
         if do_backprop:
-            loss = eng.loss_backward(target, self.ds_loss_weights, batch_dice=self.batch_dice)
+            loss = eng.loss_backward(target, self.ds_loss_weights, batch_dice=self.batch_dice, **self._engine_loss_kwargs())
             if dp is not None:
                 dp.finish()                                     # gradients averaged over the replicas (clip norm sees these)
             if self._fused is None:
@@ -427,7 +440,7 @@ class nnUNetTrainer_simple(object):
                     mask.set_gradients(eng.grads, self._fused._sq, self._fused.max_norm)
                 mask.step(masks_already_applied=True)
         else:
-            loss = eng.loss_value(target, self.ds_loss_weights, batch_dice=self.batch_dice)
+            loss = eng.loss_value(target, self.ds_loss_weights, batch_dice=self.batch_dice, **self._engine_loss_kwargs())
         if run_online_evaluation:
             self.run_online_evaluation([h.out.data for h in eng.heads], target, _engine=eng)
         if self.prefetch_batches:
@@ -956,6 +969,7 @@ class nnUNetTrainer_simple(object):
                                   json_description="" if grids == {"original"} else
                                   "scored on the network's grid against the preprocessed labels (no readable ground-truth volume)",
                                   json_author="Fabian", json_task=task)
+        self._validation_extra(cases, join(output_folder, "summary.json"))
         if run_postprocessing_on_folds:
             self.print_to_log_file("validate: determine_postprocessing (connected-component search, e2enet/postprocessing) is outside "
                                    "the MI355X hot path and was skipped; run it with the reference package on %s" % output_folder)

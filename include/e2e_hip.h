@@ -345,13 +345,44 @@ int e2e_dc_ce_grad(const float* logits, const float* target, const void* acc, fl
 /* dlogits may be NULL: loss value only (validation batches, nnUNetTrainer_simple.py:980-988).  A label outside [0, K)
  * turns the loss NaN (torch's CrossEntropyLoss raises).
  * Data-parallel batch dice (reference nnUNetTrainerV2_DDP.py:263-268 all-gathers the per-sample dice numerators and
- * denominators): e2e_dc_ce_fold_batch folds acc's [B][K][3] rows into row 0 (rows 1.. zeroed); the host all-reduces the
+ * denominators): e2e_dc_ce_fold_batch folds acc's [B][K][3] rows into row 0 (rows 1.. zeroed, K >= 1); the host all-reduces the
  * 3*K doubles of row 0 over the ranks (RCCL) between e2e_dc_ce_reduce and e2e_dc_ce_grad(batch_dice = 1).           */
 int e2e_dc_ce_fold_batch(void* acc, int B, int K, void* stream);
 /* Online evaluation of a validation batch (nnUNetTrainer_simple.py:373-405): hard tp / fp / fn voxel counts of
  * argmax(softmax(logits)) against the target per class, summed over the batch.  counts [K][3] int64 (zeroed by callee). */
 int e2e_online_eval_counts(const float* logits, const float* target, long long* counts, int B, int K,
                            long long spatial, void* stream);
+
+/* ---- K8r: sigmoid + soft-Dice + binary cross-entropy over overlapping label regions -----
+ * Replaces: DC_and_BCE_loss (dice_loss.py:362-387) = BCEWithLogitsLoss() + SoftDiceLoss(sigmoid, batch_dice, do_bg=True,
+ * smooth) for one deep-supervision scale, the loss of nnUNetTrainerV2BraTSRegions; 1 <= R <= 32 regions, which may overlap.
+ *   logits  [B,R,spatial];  acc as K8: [B,R,3]+[1] fp64 (tp,fp,fn ; BCE sum), e2e_loss_ws_bytes(B, R), zeroed by the callee;
+ *           e2e_dc_ce_fold_batch(acc, B, R) serves the data-parallel batch dice as for K8
+ *   target, region_words: two forms of the same targets, which give bit-identical results on equivalent inputs
+ *     region_words != NULL: target is the [B,1,spatial] float label map and region_words a device uint32[R], bit t of
+ *           word r = "label t belongs to region r"; y_r = (word[r] >> t) & 1 is formed on load and no R-channel target is
+ *           written or read (ConvertSegmentationToRegionsTransform, custom_transforms.py:96-123, fused).  Labels outside
+ *           [0, 32) and values that are not whole numbers belong to no region, as in the reference's `seg == l` loop
+ *     region_words == NULL: target is a multi-hot [B,R,spatial] float tensor, y = (value >= 0.5)
+ *   loss = mean over B*R*spatial of [max(l,0) - l y + log1p(exp(-|l|))] - mean over the M dice terms of
+ *          (2tp + smooth) / (2tp + fp + fn + smooth + 1e-8), M = B*R (batch_dice: R); finite at |l| = 100 and for a region
+ *          absent from a sample with smooth = 0 (dc = 0, zero dice gradient)
+ *   loss_out: *loss_out += weight * loss;   dlogits [B,R,spatial] = weight * dL/dlogits, NULL = loss value only
+ *   Planes whose pointers and spatial size allow it are read as dwordx4; the order of the sums does not depend on that.   */
+int e2e_dc_bce_reduce(const float* logits, const float* target, const unsigned* region_words, void* acc, int B, int R,
+                      long long spatial, void* stream);
+int e2e_dc_bce_grad(const float* logits, const float* target, const unsigned* region_words, const void* acc, float weight,
+                    int batch_dice, float smooth, float* dlogits, float* loss_out, int B, int R, long long spatial,
+                    void* stream);
+/* Online evaluation of a region model (nnUNetTrainerV2BraTSRegions.py:168-189): hard tp / fp / fn voxel counts per region of
+ * sigmoid(l) > 0.5 against y, summed over the batch; both target forms.  The kernel tests l > 0, the same predicate (a logit
+ * of exactly 0 is a negative).  counts [R][3] int64 (zeroed by callee).                                                    */
+int e2e_online_eval_regions(const float* logits, const float* target, const unsigned* region_words, long long* counts, int B,
+                            int R, long long spatial, void* stream);
+/* ConvertSegmentationToRegionsTransform (custom_transforms.py:96-123): seg [B,1,spatial] float labels -> out [B,R,spatial]
+ * float 0/1 through the region words (see above).                                                                        */
+int e2e_seg_to_regions(const float* seg, const unsigned* region_words, float* out, int B, int R, long long spatial,
+                       void* stream);
 
 /* Deep-supervision targets (the loss-side end of the input feed): reference
  * e2enet/training/data_augmentation/downsampling.py:87-107 (downsample_seg_for_ds_transform2, order 0) resizes the label

@@ -798,9 +798,94 @@ def gen_dataloader():
     np.savez_compressed(os.path.join(OUT, "dataloader.npz"), **out)
 
 
+# ----------------------------------------------------------------------------- region targets (nnUNetTrainerV2BraTSRegions)
+def _ref_regions():
+    """the reference's region transform, loss and region table (the transform's base class comes from batchgenerators, absent
+    here: one more stub)"""
+    at = types.ModuleType('batchgenerators.transforms.abstract_transforms')
+    at.AbstractTransform = type('AbstractTransform', (object,), {})
+    sys.modules.setdefault('batchgenerators.transforms', types.ModuleType('batchgenerators.transforms'))
+    sys.modules['batchgenerators.transforms.abstract_transforms'] = at
+    from e2enet.training.data_augmentation.custom_transforms import ConvertSegmentationToRegionsTransform
+    from e2enet.training.loss_functions.dice_loss import DC_and_BCE_loss, get_tp_fp_fn_tn
+    regions = {"whole tumor": (1, 2, 3), "tumor core": (2, 3), "enhancing tumor": (3,)}      # get_brats_regions()
+    return ConvertSegmentationToRegionsTransform, DC_and_BCE_loss, get_tp_fp_fn_tn, regions
+
+
+def _ds_weights5():
+    w = np.array([1 / (2 ** i) for i in range(5)])
+    w[-1] = 0
+    return w / w.sum()
+
+
+def gen_regions_loss():
+    """MultipleOutputLoss2(DC_and_BCE_loss) on four scales of seeded logits against BraTS region targets; label 3 is removed
+    from sample 0, so its 'enhancing tumor' dice term has an absent region."""
+    Convert, DC_and_BCE_loss, get_tp_fp_fn_tn, regions = _ref_regions()
+    r = len(regions)
+    shapes = [(2, r, 8, 12, 10), (2, r, 4, 6, 5), (2, r, 2, 3, 5), (2, r, 1, 3, 5)]
+    labels = [seeded_labels((s[0], 1) + s[2:], 4, seed=60 + i) for i, s in enumerate(shapes)]
+    for l in labels:
+        l[0][l[0] == 3] = 0
+    conv = Convert(regions, 'target', 'target')
+    multihot = [conv(target=l.numpy())['target'] for l in labels]
+    w = _ds_weights5()
+    out = {"ds_weights": w, "region_labels": np.array([list(v) + [-1] * (3 - len(v)) for v in regions.values()], dtype=np.int8)}
+    for i in range(len(shapes)):
+        out["labels%d" % i] = labels[i].numpy().astype(np.int8)
+        out["multihot%d" % i] = multihot[i].astype(np.uint8)
+    for tag, batch_dice, smooth in (("sample", False, 0.), ("batch", True, 1e-5)):
+        res = {}
+        for dt in (torch.float32, torch.float64):
+            logits = [seeded_input(s, seed=50 + i).mul(2.0).to(dt).requires_grad_(True) for i, s in enumerate(shapes)]
+            tg = [torch.from_numpy(m).to(dt) for m in multihot]
+            loss_fn = MultipleOutputLoss2(DC_and_BCE_loss({}, {'batch_dice': batch_dice, 'do_bg': True, 'smooth': smooth}), w)
+            loss = loss_fn(logits, tg)
+            loss.backward()
+            res[dt] = (loss.item(), [l.grad.clone() for l in logits])
+        out[tag + "_loss"] = np.float64(res[torch.float32][0])
+        out[tag + "_loss_fp64"] = np.float64(res[torch.float64][0])        # (how far the fp32 run above lies from exact)
+        for i, g in enumerate(res[torch.float32][1]):
+            out[tag + "_g%d" % i] = g.numpy()
+        print("  %s: |loss32 - loss64| = %.3g, max |g32 - g64| = %.3g" % (
+            tag, abs(res[torch.float32][0] - res[torch.float64][0]),
+            max(float((a.double() - b).abs().max()) for a, b in zip(*[res[d][1] for d in (torch.float32, torch.float64)]))))
+    full = seeded_input(shapes[0], seed=50).mul(2.0)
+    hard = (torch.sigmoid(full) > 0.5).float()
+    tp, fp, fn, _ = get_tp_fp_fn_tn(hard, torch.from_numpy(multihot[0]).float(), axes=(0, 2, 3, 4))
+    out["hard_tp_fp_fn"] = np.stack([tp.numpy(), fp.numpy(), fn.numpy()], 1).astype(np.int64)
+    np.savez_compressed(os.path.join(OUT, "regions_loss.npz"), **out)
+
+
+def gen_net_tiny_regions():
+    """gen_net_tiny's network (k = 3 = number of BraTS regions: its logits are net_tiny.npz's) under the region loss of the
+    reference's trainer: DC_and_BCE_loss({}, batch_dice=False, do_bg=True, smooth=0) on multi-hot targets of labels 0..3."""
+    Convert, DC_and_BCE_loss, _, regions = _ref_regions()
+    net = build_ref_net(TINY["patch"], TINY["cin"], TINY["base"], TINY["k"], TINY["pools"], TINY["max_feat"])
+    shapes = load_closed_form(net)
+    x = seeded_input((2, TINY["cin"]) + TINY["patch"], seed=21)
+    outs = net(x)
+    conv = Convert(regions, 'target', 'target')
+    targets = [torch.from_numpy(conv(target=seeded_labels((o.shape[0], 1) + tuple(o.shape[2:]), 4, seed=30 + i).numpy())['target']).float()
+               for i, o in enumerate(outs)]
+    w = _ds_weights5()
+    loss = MultipleOutputLoss2(DC_and_BCE_loss({}, {'batch_dice': False, 'do_bg': True, 'smooth': 0}), w)(outs, targets)
+    loss.backward()
+    out = {"loss": np.float64(loss.item()), "ds_weights": w}
+    names = list(shapes.keys())
+    out["names"] = np.array(names)
+    out["grad_l2"] = np.array([net.get_parameter(n).grad.double().norm().item() for n in names])
+    for n in ("conv_blocks_context.0.blocks.0.conv.weight", "loc0.4.1.blocks.0.conv.weight", "up2.1.weight",
+              "seg_outputs.0.weight", "loc3.0.0.blocks.0.instnorm.weight", "conv_blocks_context.5.1.blocks.0.conv.bias",
+              "loc0.0.0.blocks.0.conv.weight"):
+        out["grad::" + n] = net.get_parameter(n).grad.numpy()
+    np.savez_compressed(os.path.join(OUT, "net_tiny_regions.npz"), **out)
+
+
 ALL = dict(dataloader=gen_dataloader, export=gen_export, shift=gen_shift, block=gen_block, net=gen_net_tiny, sparse=gen_net_sparse_tiny, net64=gen_net64,
            hippo=gen_net_hippo, amos=gen_net_amos, w48=gen_net_w48,
-           variants=gen_net_variants, nodff=gen_net_nodff, masks=gen_masks, grad_growth=gen_grad_growth, evaluator=gen_evaluator, loss=gen_loss, sliding=gen_sliding, dice=gen_dice, init=gen_init)
+           variants=gen_net_variants, nodff=gen_net_nodff, masks=gen_masks, grad_growth=gen_grad_growth, evaluator=gen_evaluator, loss=gen_loss, sliding=gen_sliding, dice=gen_dice, init=gen_init,
+           regions_loss=gen_regions_loss, net_regions=gen_net_tiny_regions)
 
 if __name__ == "__main__":
     torch.set_num_threads(8)
