@@ -765,8 +765,7 @@ class Engine:
         self._graph_seen = set()           # keys that ran eagerly once (lazy allocations done)
         self.maps_generation = 0           # bumped when the liveness tables are replaced (their pointers are baked into a graph)
         self._sparse_jobs = None           # pack-job table of the load-balanced convs (rebuilt with the kernel maps)
-        self._tgt_static = None
-        self._tgt_static_regions = {}      # (head, multi-hot?) -> staging buffer of a region target (graph replay)
+        self._tgt_static = {}              # (head, channels) -> staging buffer of a loss target (graph replay)
         self._region_words_dev = {}        # region words -> their device copy
         self._mm_tables = {}               # directions -> (dispatch key, device job table, njobs, max elems)
         self._mm_packed = {}               # direction -> weights key its packed buffers were built from
@@ -1267,12 +1266,14 @@ class Engine:
             self.loss_val = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     def _loss(self, targets, weights, batch_dice, smooth, with_grad, regions=None):
+        """K8 (softmax Dice+CE) over the heads, or with `regions` K8r (sigmoid Dice+BCE): the same two launches per head,
+        K8r's take the region words pointer (None: multi-hot target) after the target."""
         L = lib()
         self._loss_buffers()
         self.loss_val.zero_()
         k = self.cfg.num_classes
-        if regions is not None:
-            return self._loss_regions(targets, weights, batch_dice, smooth, with_grad, regions)
+        reduce, grad = (L.dc_ce_reduce, L.dc_ce_grad) if regions is None else (L.dc_bce_reduce, L.dc_bce_grad)
+        words = None if regions is None else self._region_words(regions)[1]
         for i, h in enumerate(self.heads):
             wgt = float(weights[i]) if i < len(weights) else 0.0
             if wgt == 0.0 or not h.active:
@@ -1280,16 +1281,14 @@ class Engine:
                     h.out.grad.zero_()
                 continue
             t = targets[i]
-            assert t.is_cuda and t.dtype == torch.float32 and t.numel() == self.batch * h.src.spatial
-            L.dc_ce_reduce(h.out.data.data_ptr(), t.data_ptr(), self.loss_ws.data_ptr(), self.batch, k, h.src.spatial,
-                           _stream())
+            wp = self._target_words(t, h.src.spatial, words)
+            reduce(h.out.data.data_ptr(), t.data_ptr(), *wp, self.loss_ws.data_ptr(), self.batch, k, h.src.spatial, _stream())
             if batch_dice and self.batch_dice_hook is not None:
                 # data-parallel batch dice (reference nnUNetTrainerV2_DDP.py:263-268): global tp/fp/fn over all ranks
                 L.dc_ce_fold_batch(self.loss_ws.data_ptr(), self.batch, k, _stream())
                 self.batch_dice_hook(self.loss_ws[:3 * k])
-            L.dc_ce_grad(h.out.data.data_ptr(), t.data_ptr(), self.loss_ws.data_ptr(), wgt, 1 if batch_dice else 0,
-                         smooth, h.out.grad.data_ptr() if with_grad else None, self.loss_val.data_ptr(), self.batch, k,
-                         h.src.spatial, _stream())
+            grad(h.out.data.data_ptr(), t.data_ptr(), *wp, self.loss_ws.data_ptr(), wgt, 1 if batch_dice else 0, smooth,
+                 h.out.grad.data_ptr() if with_grad else None, self.loss_val.data_ptr(), self.batch, k, h.src.spatial, _stream())
         return self.loss_val
 
     # ---- overlapping label regions (reference nnUNetTrainerV2BraTSRegions: DC_and_BCE_loss over sigmoid heads) ----
@@ -1316,28 +1315,15 @@ class Engine:
         raise ValueError("region target of %d elements: expected a label map [%d,1,...] or a multi-hot tensor [%d,%d,...] over %d "
                          "voxels" % (t.numel(), self.batch, self.batch, r, spatial))
 
-    def _loss_regions(self, targets, weights, batch_dice, smooth, with_grad, regions):
-        L = lib()
-        r = self.cfg.num_classes
-        _, words = self._region_words(regions)
-        for i, h in enumerate(self.heads):
-            wgt = float(weights[i]) if i < len(weights) else 0.0
-            if wgt == 0.0 or not h.active:
-                if with_grad:
-                    h.out.grad.zero_()
-                continue
-            t = targets[i]
-            wp = None if self._region_form(t, h.src.spatial) else words.data_ptr()
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-            L.dc_bce_reduce(h.out.data.data_ptr(), t.data_ptr(), wp, self.loss_ws.data_ptr(), self.batch, r, h.src.spatial,
-                            _stream())
-            if batch_dice and self.batch_dice_hook is not None:
-                L.dc_ce_fold_batch(self.loss_ws.data_ptr(), self.batch, r, _stream())
-                self.batch_dice_hook(self.loss_ws[:3 * r])
-            L.dc_bce_grad(h.out.data.data_ptr(), t.data_ptr(), wp, self.loss_ws.data_ptr(), wgt, 1 if batch_dice else 0,
-                          smooth, h.out.grad.data_ptr() if with_grad else None, self.loss_val.data_ptr(), self.batch, r,
-                          h.src.spatial, _stream())
-        return self.loss_val
+    def _target_words(self, t, spatial, words):
+        """Checks the target `t` of a head of `spatial` voxels; returns what a launch passes after the target pointer: nothing
+        for softmax (words None), else the region words pointer, None for a multi-hot target."""
+        if words is None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.numel() == self.batch * spatial
+            return ()
+        wp = None if self._region_form(t, spatial) else words.data_ptr()
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        return (wp,)
 
     def loss_backward(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5,
                       regions=None):
@@ -1348,62 +1334,38 @@ class Engine:
         loss is MultipleOutputLoss2(DC_and_BCE_loss) (dice_loss.py:362-387).  targets[i] is then the same [B,1,...] label map
         (the region targets are formed from it on load) or, with more than one region, a multi-hot [B,R,...] tensor."""
         self.prepare_backward()
-        if regions is not None:
-            return self._loss_backward_regions(targets, weights, batch_dice, smooth, regions)
+        words = None if regions is None else self._region_words(regions)[0]
         if not self._graph_ok():
-            self._loss(targets, weights, batch_dice, smooth, True)
+            self._loss(targets, weights, batch_dice, smooth, True, regions)
             self.backward(None)
             return self.loss_val
-        # graph replay: the targets are staged into buffers of this plan (their pointers are part of the graph)
-        if self._tgt_static is None:
-            self._tgt_static = [torch.empty((self.batch, 1) + tuple(h.out.shape[2:]), dtype=torch.float32, device=self.device)
-                                for h in self.heads]
+        # graph replay: the targets are staged into buffers of this plan (their pointers are part of the graph), one per head
+        # and channel count.  The loss kind, the region words and the target forms (multi-hot?) are part of the key, so a
+        # softmax graph and a region graph of one engine never replay each other.
         n = min(len(targets), len(self.heads))
-        for i in range(n):
-            self._tgt_static[i].copy_(targets[i].reshape(self._tgt_static[i].shape))
-        wkey = tuple(float(weights[i]) if i < len(weights) else 0.0 for i in range(len(self.heads)))
-        active = tuple(h.active for h in self.heads)
-
-        def body():
-            self._loss(self._tgt_static, weights, batch_dice, smooth, True)
-            self.backward(None)
-        self._run(("lossbwd", wkey, bool(batch_dice), float(smooth), active), body)
-        return self.loss_val
-
-    def _loss_backward_regions(self, targets, weights, batch_dice, smooth, regions):
-        words, _ = self._region_words(regions)
-        if not self._graph_ok():
-            self._loss(targets, weights, batch_dice, smooth, True, regions=regions)
-            self.backward(None)
-            return self.loss_val
-        # graph replay: as above, with staging buffers per target form; the loss kind, the region words and the target forms are
-        # part of the key, so a softmax graph and a region graph of one engine never replay each other
-        n = min(len(targets), len(self.heads))
-        forms = tuple(self._region_form(targets[i], self.heads[i].src.spatial) for i in range(n))
-        stage = self._tgt_static_regions
+        forms = tuple(regions is not None and self._region_form(targets[i], self.heads[i].src.spatial) for i in range(n))
         static = []
         for i in range(n):
-            buf = stage.get((i, forms[i]))
+            ch = self.cfg.num_classes if forms[i] else 1
+            buf = self._tgt_static.get((i, ch))
             if buf is None:
-                ch = self.cfg.num_classes if forms[i] else 1
-                buf = stage[(i, forms[i])] = torch.empty((self.batch, ch) + tuple(self.heads[i].out.shape[2:]), dtype=torch.float32,
-                                                         device=self.device)
+                buf = self._tgt_static[(i, ch)] = torch.empty((self.batch, ch) + tuple(self.heads[i].out.shape[2:]),
+                                                              dtype=torch.float32, device=self.device)
             buf.copy_(targets[i].reshape(buf.shape))
             static.append(buf)
         wkey = tuple(float(weights[i]) if i < len(weights) else 0.0 for i in range(len(self.heads)))
         active = tuple(h.active for h in self.heads)
 
         def body():
-            self._loss(static, weights, batch_dice, smooth, True, regions=regions)
+            self._loss(static, weights, batch_dice, smooth, True, regions)
             self.backward(None)
-        self._run(("lossbwd", "dc_bce", words, forms, wkey, bool(batch_dice), float(smooth), active), body)
+        self._run(("lossbwd", "dc_ce" if regions is None else "dc_bce", words, forms, wkey, bool(batch_dice), float(smooth), active),
+                  body)
         return self.loss_val
 
     def loss_value(self, targets: Sequence[torch.Tensor], weights: Sequence[float], batch_dice=False, smooth=1e-5, regions=None):
         """The same loss without gradients (validation batches, reference nnUNetTrainer_simple.py:980-988)."""
-        if regions is not None:
-            return self._loss(targets, weights, batch_dice, smooth, False, regions=regions)
-        return self._loss(targets, weights, batch_dice, smooth, False)
+        return self._loss(targets, weights, batch_dice, smooth, False, regions)
 
     def online_eval_counts(self, target: torch.Tensor, regions=None) -> torch.Tensor:
         """Hard tp/fp/fn voxel counts [K, 3] (int64, device) of the full-resolution prediction against `target`
@@ -1413,16 +1375,9 @@ class Engine:
         k = self.cfg.num_classes
         if self._eval_counts is None:
             self._eval_counts = torch.zeros((k, 3), dtype=torch.int64, device=self.device)
-        if regions is not None:
-            _, words = self._region_words(regions)
-            wp = None if self._region_form(target, h.src.spatial) else words.data_ptr()
-            assert target.is_cuda and target.dtype == torch.float32 and target.is_contiguous()
-            lib().online_eval_regions(h.out.data.data_ptr(), target.data_ptr(), wp, self._eval_counts.data_ptr(), self.batch, k,
-                                      h.src.spatial, _stream())
-            return self._eval_counts
-        assert target.is_cuda and target.dtype == torch.float32 and target.numel() == self.batch * h.src.spatial
-        lib().online_eval_counts(h.out.data.data_ptr(), target.data_ptr(), self._eval_counts.data_ptr(), self.batch, k,
-                                 h.src.spatial, _stream())
+        count = lib().online_eval_counts if regions is None else lib().online_eval_regions
+        wp = self._target_words(target, h.src.spatial, None if regions is None else self._region_words(regions)[1])
+        count(h.out.data.data_ptr(), target.data_ptr(), *wp, self._eval_counts.data_ptr(), self.batch, k, h.src.spatial, _stream())
         return self._eval_counts
 
     # ------------------------------------------------------------------------------------------ accounting

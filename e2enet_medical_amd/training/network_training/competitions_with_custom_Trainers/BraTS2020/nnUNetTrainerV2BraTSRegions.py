@@ -17,12 +17,10 @@ The ``_Dice``, ``_BN`` and ``_DDP`` variants of the reference are not built.
 import json
 
 import numpy as np
-import torch
 from torch import nn
 
-from ....._lib import lib
 from .....evaluation.region_based_evaluation import evaluate_case, get_brats_regions
-from ....data_augmentation.custom_transforms import region_label_sets, region_words, words_tensor
+from ....data_augmentation.custom_transforms import region_label_sets, region_words
 from ....loss_functions.dice_loss import DC_and_BCE_loss
 from ...nnUNetTrainer_simple import nnUNetTrainer_simple
 
@@ -54,42 +52,17 @@ class nnUNetTrainerV2BraTSRegions(nnUNetTrainer_simple):
     def _engine_loss_kwargs(self):
         return {'smooth': self.loss_smooth, 'regions': region_words(self.regions)}
 
-    def run_online_evaluation(self, output, target, _engine=None):
-        """reference :168-189: hard tp/fp/fn per region of sigmoid(output) > 0.5 (HIP kernel e2e_online_eval_regions); all R
-        regions are reported, there is no background entry to drop."""
-        words = region_words(self.regions)
-        if _engine is not None:
-            counts = _engine.online_eval_counts(target[0], regions=words)
-        else:
-            logits, tgt = output[0], target[0]
-            if getattr(self.network, "conv_variant", "133") != "133":
-                logits, tgt = self.network.to_engine_layout(logits), self.network.to_engine_layout(tgt)
-            logits, tgt = logits.float().contiguous(), tgt.float().contiguous()
-            if not logits.is_cuda:
-                raise RuntimeError("run_online_evaluation (MI355X) needs GPU tensors: there is no CPU fallback")
-            b, r = logits.shape[:2]
-            spatial = logits[0, 0].numel()
-            if r != len(words):
-                raise ValueError("%d output channels for %d regions" % (r, len(words)))
-            if tgt.numel() == b * spatial:
-                wp = words_tensor(words, logits.device)
-            elif r > 1 and tgt.numel() == b * r * spatial:
-                wp = None
-            else:
-                raise ValueError("target must be a label map [B,1,...] or multi-hot [B,%d,...] over the logits' voxels" % r)
-            counts = torch.zeros((r, 3), dtype=torch.int64, device=logits.device)
-            lib().online_eval_regions(logits.data_ptr(), tgt.data_ptr(), None if wp is None else wp.data_ptr(), counts.data_ptr(),
-                                      b, r, spatial, torch.cuda.current_stream().cuda_stream)
-        dp_on, group = self._data_parallel()
-        if dp_on:
-            import torch.distributed as dist
-            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-        c = counts.cpu().numpy().astype(np.float32)
-        tp_hard, fp_hard, fn_hard = c[:, 0], c[:, 1], c[:, 2]
-        self.online_eval_foreground_dc.append(list((2 * tp_hard) / (2 * tp_hard + fp_hard + fn_hard + 1e-8)))
-        self.online_eval_tp.append(list(tp_hard))
-        self.online_eval_fp.append(list(fp_hard))
-        self.online_eval_fn.append(list(fn_hard))
+    def _online_eval_regions(self):
+        return region_words(self.regions)
+
+    def _online_eval_multi_hot(self, tgt, b, r, spatial):
+        if r != len(self.regions):
+            raise ValueError("%d output channels for %d regions" % (r, len(self.regions)))
+        if tgt.numel() == b * spatial:
+            return False
+        if r > 1 and tgt.numel() == b * r * spatial:
+            return True
+        raise ValueError("target must be a label map [B,1,...] or multi-hot [B,%d,...] over the logits' voxels" % r)
 
     def _validation_extra(self, cases, summary_file):
         """reference :155-166 runs evaluate_regions over the exported folder; here the Dice per region of every case and the

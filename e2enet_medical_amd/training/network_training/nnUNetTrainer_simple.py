@@ -492,16 +492,29 @@ class nnUNetTrainer_simple(object):
         target = [torch.as_tensor(t).float().to(dev, non_blocking=True).contiguous() for t in target]
         return data, target
 
+    def _online_eval_regions(self):
+        """region words of the online evaluation (a region trainer overrides this); None: softmax classes, of which the
+        background row is not reported"""
+        return None
+
+    def _online_eval_multi_hot(self, tgt, b, k, spatial):
+        """Checks a foreign target against [b, k, spatial] logits.  True: it holds one 0/1 channel per output (region trainers)."""
+        assert tgt.numel() == b * spatial, "target must hold one label per voxel of the logits"
+        return False
+
     def run_online_evaluation(self, output, target, _engine=None):
         """reference :371-405: hard tp/fp/fn per foreground class of the full-resolution prediction, summed over the
         batch (HIP kernel e2e_online_eval_counts; under data parallelism summed over the ranks as
-        nnUNetTrainerV2_DDP.py:303-305 does)."""
+        nnUNetTrainerV2_DDP.py:303-305 does).  With region words (reference nnUNetTrainerV2BraTSRegions.py:168-189): per region
+        of sigmoid(output) > 0.5 (e2e_online_eval_regions); all regions are reported, there is no background entry to drop."""
+        words = self._online_eval_regions()
         if _engine is not None:
-            counts = _engine.online_eval_counts(target[0])
+            counts = _engine.online_eval_counts(target[0], regions=words)
         else:
             # the reference's public signature (foreign logits [B, K, ...] + labels): counted straight from those tensors,
             # no activation plan is built for them
             from ..._lib import lib
+            from ..data_augmentation.custom_transforms import words_tensor
             logits, tgt = output[0], target[0]
             if getattr(self.network, "conv_variant", "133") != "133":
                 logits, tgt = self.network.to_engine_layout(logits), self.network.to_engine_layout(tgt)
@@ -510,15 +523,20 @@ class nnUNetTrainer_simple(object):
                 raise RuntimeError("run_online_evaluation (MI355X) needs GPU tensors: there is no CPU fallback")
             b, k = logits.shape[:2]
             spatial = logits[0, 0].numel()
-            assert tgt.numel() == b * spatial, "target must hold one label per voxel of the logits"
+            multi_hot = self._online_eval_multi_hot(tgt, b, k, spatial)
             counts = torch.zeros((k, 3), dtype=torch.int64, device=logits.device)
-            lib().online_eval_counts(logits.data_ptr(), tgt.data_ptr(), counts.data_ptr(), b, k, spatial,
-                                     torch.cuda.current_stream().cuda_stream)
+            stream = torch.cuda.current_stream().cuda_stream
+            if words is None:
+                lib().online_eval_counts(logits.data_ptr(), tgt.data_ptr(), counts.data_ptr(), b, k, spatial, stream)
+            else:
+                wd = None if multi_hot else words_tensor(words, logits.device)
+                lib().online_eval_regions(logits.data_ptr(), tgt.data_ptr(), None if wd is None else wd.data_ptr(),
+                                          counts.data_ptr(), b, k, spatial, stream)
         dp_on, group = self._data_parallel()
         if dp_on:
             import torch.distributed as dist
             dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-        c = counts.cpu().numpy().astype(np.float32)[1:]          # foreground classes
+        c = counts.cpu().numpy().astype(np.float32)[1 if words is None else 0:]
         tp_hard, fp_hard, fn_hard = c[:, 0], c[:, 1], c[:, 2]
         self.online_eval_foreground_dc.append(list((2 * tp_hard) / (2 * tp_hard + fp_hard + fn_hard + 1e-8)))
         self.online_eval_tp.append(list(tp_hard))
