@@ -1054,31 +1054,12 @@ inline TileSel pick(int Ho, int Wo, bool strided) {
   return {8, 4, 4};
 }
 
-inline void plan(WgParams& p, TileSel ts, int pairs, int* nchunks, int target_wgs = 1024) {
+inline void set_tile_grid(WgParams& p, TileSel ts) {
   p.tiles_x = e2e::cdiv(p.Wo, ts.tw);
   p.tiles_y = e2e::cdiv(p.Ho, ts.th);
   p.tiles_d = e2e::cdiv(p.Do, ts.nd);
   p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
   p.total_tiles = (long long)p.tiles_per_n * p.B;
-  long long want = target_wgs / (pairs > 0 ? pairs : 1);
-  if (want < 1) want = 1;
-  long long tpc = e2e::cdivll(p.total_tiles, want);
-  if (tpc < 4) tpc = 4;
-  if (tpc > p.total_tiles) tpc = p.total_tiles;
-  p.tiles_per_chunk = (int)tpc;
-  *nchunks = (int)e2e::cdivll(p.total_tiles, tpc);
-}
-
-template <int SH, int SW, int ND, int TH, int TW>
-int launch(const WgParams& p, int nchunks, int pairs, hipStream_t st) {
-  hipLaunchKernelGGL((conv133_wgrad_kernel<SH, SW, ND, TH, TW>), dim3(nchunks, pairs), dim3(256), 0, st, p);
-  return e2e::check_launch("conv133_wgrad_kernel");
-}
-
-template <int ND, int TH, int TW, int NCB>
-int launch_v2(const WgParams& p, int nchunks, int pairs, hipStream_t st) {
-  hipLaunchKernelGGL((conv133_wgrad_v2_kernel<ND, TH, TW, NCB>), dim3(nchunks, pairs), dim3(256 * NCB), 0, st, p);
-  return e2e::check_launch("conv133_wgrad_v2_kernel");
 }
 
 // v2 applies to stride-1 (in plane) convs whose rows are multiples of 4 floats
@@ -1090,149 +1071,140 @@ inline int v2_ncb(int Cin, int Ho, int Wo) {      // 8x8 planes: the (4,8,8) til
 }
 
 // v3 (double-buffered 4 x 32 tiles): stride-1 planes at least 32 wide whose rows are multiples of 4 floats
-inline bool use_v3(int Cin, int Hi, int Wi, int sh, int sw) {
-  return sh == 1 && sw == 1 && (Wi % 4) == 0 && Wi >= 32 && Hi > 16;
-}
+inline bool use_v3(int Hi, int Wi, int sh, int sw) { return sh == 1 && sw == 1 && (Wi % 4) == 0 && Wi >= 32 && Hi > 16; }
 // block shape of a v3 workgroup: 32 out x 64 in channels, or 64 out x 32 in.  The wide-out shape stages less (the
 // halo'd input tile is the expensive half) and pads fewer input channels (Cin = 160: three 64-blocks waste a sixth of
 // the MFMAs, five 32-blocks none): 160 -> 64 @64^3 runs at 122 instead of 97 TFLOP/s.
-inline bool v3_wide_out(int Cin, int Cout) {
-  (void)Cin;
-  return Cout >= 64 && (Cout % 64) <= 0;
-}
+inline bool v3_wide_out(int Cout) { return Cout >= 64 && (Cout % 64) <= 0; }
 inline bool v3_ksplit(int Cin, int Cout) { return Cin <= 32 && Cout <= 32; }   // one 32 x 32 block: split the tile rows
-inline int v3_pairs(int Cin, int Cout) {
-  if (v3_ksplit(Cin, Cout)) return 1;
-  return v3_wide_out(Cin, Cout) ? e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 64) : e2e::cdiv(Cin, 64) * e2e::cdiv(Cout, 32);
-}
-// chunks never cross a batch item: `segs` runs of tiles_per_chunk tiles per item; returns the number of chunks
-inline int plan_v3(WgParams& p, int pairs) {
-  p.tiles_x = e2e::cdiv(p.Wo, 32);
-  p.tiles_y = e2e::cdiv(p.Ho, 4);
-  p.tiles_d = p.Do;
-  p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-  p.total_tiles = (long long)p.tiles_per_n * p.B;
-  const int target = 256;
-  long long want = target / (pairs > 0 ? pairs : 1);        // one workgroup per CU, equal work each; fewer chunks = fewer slabs to reduce
-  if (want < p.B) want = p.B;
-  int segs = (int)(want / p.B);
-  int tpc = e2e::cdiv(p.tiles_per_n, segs);
-  if (tpc < 8) tpc = 8;
-  if (tpc > p.tiles_per_n) tpc = p.tiles_per_n;
-  segs = e2e::cdiv(p.tiles_per_n, tpc);
-  p.tiles_per_chunk = tpc;
-  p.cblocks_segs = segs;
-  return segs * p.B;
-}
 
-// conv133_wgrad_bf3.hip (bf16 / fp16 matrix pipe, fp32-exact split operands): the shapes v3 serves; E2E_WG_BF3=0 keeps the
-// fp32-MFMA kernels (forced-path tests, A/B runs).  32 x 32 channel blocks, chunks planned like v3's.
-inline bool use_bf3(int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  static const int on = getenv("E2E_WG_BF3") ? atoi(getenv("E2E_WG_BF3")) : 1;
+// conv133_wgrad_bf3.hip (bf16 / fp16 matrix pipe, fp32-exact split operands), 32 x 32 channel blocks: the shapes v3 serves on
+// 4 x 32-pixel tiles and, since round 4, planes 16..31 voxels wide on 8 x 16-pixel tiles (conv133_wgrad_bf3v5_kernel<1>; they ran
+// on the fp32 MFMA v2 kernel).  E2E_WG_BF3=0 keeps the fp32-MFMA kernels (forced-path tests, A/B runs).
+inline int wg_bf3_env() { static const int v = getenv("E2E_WG_BF3") ? atoi(getenv("E2E_WG_BF3")) : 1; return v; }
+inline bool bf3_serves(int Cin, int Cout, int Di, int Hi, int Wi, int sd) {
   const long long Do = (Di - 1) / sd + 1;                    // the kernel addresses with 32-bit element offsets inside one batch item
   const bool fits32 = (long long)Di * Hi * Wi < (1ll << 29) && (long long)Cout * Do * Hi * Wi < (1ll << 29);
-  return on && Cin > 4 && fits32 && use_v3(Cin, Hi, Wi, sh, sw);
+  return wg_bf3_env() && Cin > 4 && fits32;
+}
+inline bool use_bf3(int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
+  return bf3_serves(Cin, Cout, Di, Hi, Wi, sd) && use_v3(Hi, Wi, sh, sw);
+}
+inline bool use_bf3_w16(int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
+  return bf3_serves(Cin, Cout, Di, Hi, Wi, sd) && sh == 1 && sw == 1 && (Wi % 4) == 0 && Wi >= 16 && Wi < 32 && Hi >= 8;
 }
 // fp16 two-piece operands (round 5) where the caller hands over max |dy|; E2E_WG_H2=0 keeps the bf16 three-piece form (A/B runs)
 inline int wg_h2_env() { static const int v = getenv("E2E_WG_H2") ? atoi(getenv("E2E_WG_H2")) : 1; return v; }
-inline int bf3_pairs(int Cin, int Cout) { return e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 32); }
-// planes 16..31 voxels wide: the same kernel on 8 x 16-pixel tiles (conv133_wgrad_bf3v5_kernel<1>; round 4, they ran on the fp32
-// MFMA v2 kernel); E2E_WG_BF3=0 keeps v2.  32-bit element offsets inside one batch item (as v5).
-inline bool use_bf3_w16(int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  static const int bf3 = getenv("E2E_WG_BF3") ? atoi(getenv("E2E_WG_BF3")) : 1;
-  const long long Do = (Di - 1) / sd + 1;
-  return bf3 && Cin > 4 && sh == 1 && sw == 1 && (Wi % 4) == 0 && Wi >= 16 && Wi < 32 && Hi >= 8 &&
-         (long long)Di * Hi * Wi < (1ll << 29) && (long long)Cout * Do * Hi * Wi < (1ll << 29);
-}
-inline int plan_w16(WgParams& p, int pairs) {
-  p.tiles_x = e2e::cdiv(p.Wo, 16);
-  p.tiles_y = e2e::cdiv(p.Ho, 8);
-  p.tiles_d = p.Do;
-  p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-  p.total_tiles = (long long)p.tiles_per_n * p.B;
-  long long want = 256 / (pairs > 0 ? pairs : 1);            // one workgroup per CU
-  if (want < p.B) want = p.B;
-  int segs = (int)(want / p.B);
-  int tpc = e2e::cdiv(p.tiles_per_n, segs);
-  if (tpc < 4) tpc = 4;
-  if (tpc > p.tiles_per_n) tpc = p.tiles_per_n;
-  segs = e2e::cdiv(p.tiles_per_n, tpc);
-  p.tiles_per_chunk = tpc;
-  p.cblocks_segs = segs;
-  return segs * p.B;
-}
 
 // network input layer (Cin <= 4): stride 1, rows multiples of 4 floats, planes at least one 8 x 32 tile
 inline bool use_smallc(int Cin, int Hi, int Wi, int sh, int sw) {
   return Cin <= 4 && sh == 1 && sw == 1 && (Wi % 4) == 0 && Wi >= 32 && Hi >= 8;
 }
-inline int plan_smallc(WgParams& p, int pairs) {        // returns the number of workgroup chunks (slabs = 2 x that)
-  p.tiles_x = e2e::cdiv(p.Wo, 32);
-  p.tiles_y = e2e::cdiv(p.Ho, 8);
-  p.tiles_d = p.Do;
-  p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-  p.total_tiles = (long long)p.tiles_per_n * p.B;
-  long long want = 1024 / (pairs > 0 ? pairs : 1);          // 4 workgroups per CU
-  if (want < p.B) want = p.B;
-  int segs = (int)(want / p.B);
-  int tpc = e2e::cdiv(p.tiles_per_n, segs);
-  if (tpc < 4) tpc = 4;
-  if (tpc > p.tiles_per_n) tpc = p.tiles_per_n;
-  segs = e2e::cdiv(p.tiles_per_n, tpc);
-  p.tiles_per_chunk = tpc;
-  p.cblocks_segs = segs;
-  return segs * p.B;
-}
 
 // stride-(2,2) pipelined kernel: needs 16-byte aligned input rows and output planes at least one tile wide
 inline bool use_s2(int Wi, int Wo, int sh, int sw) { return sh == 2 && sw == 2 && (Wi % 4) == 0 && (Wo % 4) == 0 && Wo >= 16; }
-inline int s2_chunks(long long total_tiles, int pairs, int* tpc_out) {
-  long long want = 512 / (pairs > 0 ? pairs : 1);
-  if (want < 1) want = 1;
-  long long tpc = e2e::cdivll(total_tiles, want);
-  if (tpc < 8) tpc = 8;
-  if (tpc > total_tiles) tpc = total_tiles;
-  *tpc_out = (int)tpc;
-  return (int)e2e::cdivll(total_tiles, tpc);
+
+// What e2e_conv133_wgrad_ws_bytes and e2e_conv133_wgrad share: the launch writes `slabs` slabs of Cout x Cin x 9 floats into a
+// workspace that carries no size, so the size query is this plan's slab count and nothing else.
+enum WgPath { WG_S2, WG_SMALLC, WG_BF3, WG_V3, WG_BF3_W16, WG_V2, WG_V1 };
+enum V3Form { V3_WIDE_IN, V3_WIDE_OUT, V3_KSPLIT };   // <2,1,1>: 32 out x 64 in, <1,2,1>: 64 out x 32 in, <1,1,2>: 32 x 32, tile rows split
+struct WgPlan {
+  WgPath path;
+  WgParams p;          // shape, tile grid, chunks, channel blocks; the pointers are added at launch
+  int chunks, pairs;   // launch grid
+  int slabs;           // slabs the main kernel writes = slabs the reduction reads
+  TileSel ts;          // v1, v2: tile of the kernel template
+  int ncb;             // v2: 32-channel input blocks per workgroup
+  V3Form v3;
+  int geom;            // bf3: WgBf3Params::geom
+};
+
+inline WgPlan plan_wgrad(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
+  WgPlan pl{};
+  WgParams& p = pl.p;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd;
+  p.Do = (Di - 1) / sd + 1; p.Ho = (Hi - 1) / sh + 1; p.Wo = (Wi - 1) / sw + 1;
+  const int cb32 = e2e::cdiv(Cin, 32), ob32 = e2e::cdiv(Cout, 32);
+  if (use_s2(Wi, p.Wo, sh, sw)) {
+    pl.path = WG_S2;
+    p.cblocks = cb32;
+    pl.pairs = cb32 * ob32;
+    set_tile_grid(p, {1, 4, 16});
+    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 8, &p.tiles_per_chunk);
+  } else if (use_smallc(Cin, Hi, Wi, sh, sw)) {
+    pl.path = WG_SMALLC;
+    pl.pairs = ob32;
+    set_tile_grid(p, {1, 8, 32});
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 1024, 4, &p.tiles_per_chunk, &p.cblocks_segs);   // 4 workgroups per CU
+    pl.slabs = 2 * pl.chunks;
+  } else if (use_bf3(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
+    pl.path = WG_BF3;
+    p.cblocks = cb32;
+    pl.pairs = cb32 * ob32;
+    set_tile_grid(p, {1, 4, 32});
+    // one workgroup per CU, equal work each; fewer chunks = fewer slabs to reduce
+    pl.slabs = pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.cblocks_segs);
+  } else if (use_v3(Hi, Wi, sh, sw)) {
+    pl.path = WG_V3;
+    pl.v3 = v3_ksplit(Cin, Cout) ? V3_KSPLIT : (v3_wide_out(Cout) ? V3_WIDE_OUT : V3_WIDE_IN);
+    p.cblocks = pl.v3 == V3_KSPLIT ? 1 : (pl.v3 == V3_WIDE_OUT ? cb32 : e2e::cdiv(Cin, 64));
+    pl.pairs = p.cblocks * (pl.v3 == V3_WIDE_OUT ? e2e::cdiv(Cout, 64) : ob32);
+    set_tile_grid(p, {1, 4, 32});
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.cblocks_segs);   // as bf3
+    pl.slabs = pl.v3 == V3_KSPLIT ? 2 * pl.chunks : pl.chunks;   // two row-half slabs per workgroup
+  } else if (use_bf3_w16(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
+    pl.path = WG_BF3_W16;
+    pl.geom = 1;
+    p.cblocks = cb32;
+    pl.pairs = cb32 * ob32;
+    set_tile_grid(p, {1, 8, 16});
+    pl.slabs = pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 4, &p.tiles_per_chunk, &p.cblocks_segs);   // one workgroup per CU
+  } else if (use_v2(Hi, Wi, sh, sw)) {
+    pl.path = WG_V2;
+    pl.ts = pick(p.Ho, p.Wo, false);
+    pl.ncb = v2_ncb(Cin, p.Ho, p.Wo);
+    p.cblocks = e2e::cdiv(Cin, 32 * pl.ncb);
+    pl.pairs = p.cblocks * ob32;
+    set_tile_grid(p, pl.ts);
+    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 4, &p.tiles_per_chunk);
+  } else {
+    pl.path = WG_V1;
+    pl.ts = pick(p.Ho, p.Wo, sh != 1 || sw != 1);
+    p.cblocks = cb32;
+    pl.pairs = cb32 * ob32;
+    set_tile_grid(p, pl.ts);
+    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 1024, 4, &p.tiles_per_chunk);
+  }
+  return pl;
+}
+
+template <int SH, int SW, int ND, int TH, int TW>
+void launch(const WgParams& p, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((conv133_wgrad_kernel<SH, SW, ND, TH, TW>), grid, dim3(256), 0, st, p);
+}
+
+template <int ND, int TH, int TW, int NCB>
+void launch_v2(const WgParams& p, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((conv133_wgrad_v2_kernel<ND, TH, TW, NCB>), grid, dim3(256 * NCB), 0, st, p);
 }
 
 template <int SH, int SW>
-int dispatch_strided(const WgParams& p, TileSel ts, int nchunks, int pairs, hipStream_t st) {
-  if (ts.nd == 1) return launch<SH, SW, 1, 8, 16>(p, nchunks, pairs, st);
-  if (ts.nd == 2) return launch<SH, SW, 2, 8, 8>(p, nchunks, pairs, st);
-  return launch<SH, SW, 8, 4, 4>(p, nchunks, pairs, st);
+void launch_strided(const WgParams& p, TileSel ts, dim3 grid, hipStream_t st) {
+  if (ts.nd == 1) launch<SH, SW, 1, 8, 16>(p, grid, st);
+  else if (ts.nd == 2) launch<SH, SW, 2, 8, 8>(p, grid, st);
+  else launch<SH, SW, 8, 4, 4>(p, grid, st);
 }
 
 }  // namespace
 
+int e2e::reduce_slabs(const float* slab, float* dw, long long numel, int nslabs, hipStream_t st) {
+  hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, slab, dw, numel, nslabs);
+  return e2e::check_launch("wgrad_slab_reduce_kernel");
+}
+
 extern "C" long long e2e_conv133_wgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh,
                                                 int sw) {
-  WgParams p{};
-  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd;
-  p.Do = (Di - 1) / sd + 1; p.Ho = (Hi - 1) / sh + 1; p.Wo = (Wi - 1) / sw + 1;
-  int nchunks;
-  if (use_s2(Wi, p.Wo, sh, sw)) {
-    const int pairs = e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 32);
-    p.tiles_x = e2e::cdiv(p.Wo, 16); p.tiles_y = e2e::cdiv(p.Ho, 4); p.tiles_d = p.Do;
-    p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-    p.total_tiles = (long long)p.tiles_per_n * B;
-    nchunks = s2_chunks(p.total_tiles, pairs, &p.tiles_per_chunk);
-  } else if (use_smallc(Cin, Hi, Wi, sh, sw)) {
-    nchunks = 2 * plan_smallc(p, e2e::cdiv(Cout, 32));
-  } else if (use_bf3(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
-    nchunks = plan_v3(p, bf3_pairs(Cin, Cout));
-  } else if (use_v3(Cin, Hi, Wi, sh, sw)) {
-    nchunks = plan_v3(p, v3_pairs(Cin, Cout)) * (v3_ksplit(Cin, Cout) ? 2 : 1);
-  } else if (use_bf3_w16(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
-    nchunks = plan_w16(p, bf3_pairs(Cin, Cout));
-  } else if (use_v2(Hi, Wi, sh, sw)) {
-    const int pairs = e2e::cdiv(Cin, 32 * v2_ncb(Cin, p.Ho, p.Wo)) * e2e::cdiv(Cout, 32);
-    plan(p, pick(p.Ho, p.Wo, false), pairs, &nchunks, 512);
-  } else {
-    const int pairs = e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 32);
-    plan(p, pick(p.Ho, p.Wo, sh != 1 || sw != 1), pairs, &nchunks);
-  }
-  return (long long)nchunks * Cout * Cin * 9 * (long long)sizeof(float);
+  return (long long)plan_wgrad(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw).slabs * Cout * Cin * 9 * (long long)sizeof(float);
 }
 
 extern "C" int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, float* dw, void* ws, int B, int Cin,
@@ -1241,125 +1213,62 @@ extern "C" int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, fl
   E2E_REQUIRE(chans && dy && dw && ws, "conv133_wgrad: null pointer");
   E2E_REQUIRE((sd == 1 || sd == 2) && (sh == 1 || sh == 2) && (sw == 1 || sw == 2), "conv133_wgrad: stride must be 1 or 2");
   hipStream_t st = (hipStream_t)stream;
-  WgParams p{};
-  p.dbg = 0;
+  const WgPlan pl = plan_wgrad(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
+  WgParams p = pl.p;
   p.chans = chans; p.dy = dy; p.slab = reinterpret_cast<float*>(ws);
-  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd;
-  p.Do = (Di - 1) / sd + 1; p.Ho = (Hi - 1) / sh + 1; p.Wo = (Wi - 1) / sw + 1;
-  const bool strided = sh != 1 || sw != 1;
-  const TileSel ts = pick(p.Ho, p.Wo, strided);
-  int nchunks;
-  int rc;
-  const long long numel = (long long)Cout * Cin * 9;
-  if (use_s2(Wi, p.Wo, sh, sw)) {
-    p.cblocks = e2e::cdiv(Cin, 32);
-    const int pairs = p.cblocks * e2e::cdiv(Cout, 32);
-    p.tiles_x = e2e::cdiv(p.Wo, 16); p.tiles_y = e2e::cdiv(p.Ho, 4); p.tiles_d = p.Do;
-    p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-    p.total_tiles = (long long)p.tiles_per_n * B;
-    nchunks = s2_chunks(p.total_tiles, pairs, &p.tiles_per_chunk);
-    e2e::note_kernel("conv133_wgrad_s2 chunks=%d pairs=%d", nchunks, pairs);
-    hipLaunchKernelGGL(conv133_wgrad_s2_kernel, dim3(nchunks, pairs), dim3(256), 0, st, p);
-    rc = e2e::check_launch("conv133_wgrad_s2_kernel");
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
+  const TileSel ts = pl.ts;
+  const dim3 grid(pl.chunks, pl.pairs);
+  int rc = E2E_OK;
+  switch (pl.path) {
+    case WG_S2:
+      e2e::note_kernel("conv133_wgrad_s2 chunks=%d pairs=%d", pl.chunks, pl.pairs);
+      hipLaunchKernelGGL(conv133_wgrad_s2_kernel, grid, dim3(256), 0, st, p);
+      break;
+    case WG_SMALLC:
+      e2e::note_kernel("conv133_wgrad_smallc chunks=%d pairs=%d", pl.chunks, pl.pairs);
+      hipLaunchKernelGGL(conv133_wgrad_smallc_kernel, grid, dim3(256), 0, st, p);
+      break;
+    case WG_BF3:
+    case WG_BF3_W16: {
+      e2e::WgBf3Params q{};
+      q.chans = chans; q.dy = dy; q.slab = p.slab;
+      q.B = B; q.Cin = Cin; q.Cout = Cout; q.Di = Di; q.Hi = Hi; q.Wi = Wi; q.Do = p.Do; q.sd = sd;
+      q.tiles_x = p.tiles_x; q.tiles_y = p.tiles_y; q.tiles_per_n = p.tiles_per_n; q.tiles_per_chunk = p.tiles_per_chunk;
+      q.segs = p.cblocks_segs; q.cblocks = p.cblocks; q.geom = pl.geom;
+      q.h2 = wg_h2_env() && dy_absmax != nullptr; q.dy_absmax = dy_absmax; q.x_absmax = x_absmax;
+      e2e::note_kernel("conv133_wgrad_%s%s chunks=%d pairs=%d", q.h2 ? "h2" : "bf3", pl.geom ? "w16" : "", pl.chunks, pl.pairs);
+      rc = e2e::launch_wgrad_bf3(q, pl.chunks, pl.pairs, st);
+      break;
+    }
+    case WG_V3:
+      e2e::note_kernel("conv133_wgrad_v3<%s> chunks=%d pairs=%d", pl.v3 == V3_KSPLIT ? "1,1,2" : (pl.v3 == V3_WIDE_OUT ? "1,2,1" : "2,1,1"), pl.chunks, pl.pairs);
+      if (pl.v3 == V3_KSPLIT) hipLaunchKernelGGL((conv133_wgrad_v3_kernel<1, 1, 2>), grid, dim3(512), 0, st, p);
+      else if (pl.v3 == V3_WIDE_OUT) hipLaunchKernelGGL((conv133_wgrad_v3_kernel<1, 2, 1>), grid, dim3(512), 0, st, p);
+      else hipLaunchKernelGGL((conv133_wgrad_v3_kernel<2, 1, 1>), grid, dim3(512), 0, st, p);
+      break;
+    case WG_V2:
+      e2e::note_kernel("conv133_wgrad_v2<%d,%d,%d,%d> chunks=%d pairs=%d", ts.nd, ts.th, ts.tw, pl.ncb, pl.chunks, pl.pairs);
+      if (ts.tw == 32) { if (pl.ncb == 2) launch_v2<1, 8, 32, 2>(p, grid, st); else launch_v2<1, 8, 32, 1>(p, grid, st); }
+      else if (ts.tw == 16) { if (pl.ncb == 2) launch_v2<1, 16, 16, 2>(p, grid, st); else launch_v2<1, 16, 16, 1>(p, grid, st); }
+      else launch_v2<4, 8, 8, 1>(p, grid, st);
+      break;
+    case WG_V1:
+      e2e::note_kernel("conv133_wgrad_v1<%d,%d,%d,%d,%d> chunks=%d pairs=%d", sh, sw, ts.nd, ts.th, ts.tw, pl.chunks, pl.pairs);
+      if (sh == 1 && sw == 1) {
+        if (ts.tw == 32) launch<1, 1, 1, 8, 32>(p, grid, st);
+        else if (ts.tw == 16) launch<1, 1, 1, 16, 16>(p, grid, st);
+        else if (ts.tw == 8) launch<1, 1, 4, 8, 8>(p, grid, st);
+        else launch<1, 1, 16, 4, 4>(p, grid, st);
+      } else if (sh == 2 && sw == 2) {
+        launch_strided<2, 2>(p, ts, grid, st);
+      } else if (sh == 1 && sw == 2) {
+        launch_strided<1, 2>(p, ts, grid, st);
+      } else {
+        launch_strided<2, 1>(p, ts, grid, st);
+      }
+      break;
   }
-  if (use_smallc(Cin, Hi, Wi, sh, sw)) {
-    const int pairs = e2e::cdiv(Cout, 32);
-    const int wgs = plan_smallc(p, pairs);
-    nchunks = 2 * wgs;
-    e2e::note_kernel("conv133_wgrad_smallc chunks=%d pairs=%d", wgs, pairs);
-    hipLaunchKernelGGL(conv133_wgrad_smallc_kernel, dim3(wgs, pairs), dim3(256), 0, st, p);
-    rc = e2e::check_launch("conv133_wgrad_smallc_kernel");
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
-  }
-  if (use_bf3(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
-    const int pairs = bf3_pairs(Cin, Cout);
-    nchunks = plan_v3(p, pairs);
-    e2e::WgBf3Params q{};
-    q.chans = chans; q.dy = dy; q.slab = p.slab;
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.Di = Di; q.Hi = Hi; q.Wi = Wi; q.Do = p.Do; q.sd = sd;
-    q.tiles_x = p.tiles_x; q.tiles_y = p.tiles_y; q.tiles_per_n = p.tiles_per_n; q.tiles_per_chunk = p.tiles_per_chunk;
-    q.segs = p.cblocks_segs; q.cblocks = e2e::cdiv(Cin, 32);
-    q.h2 = wg_h2_env() && dy_absmax != nullptr; q.dy_absmax = dy_absmax; q.x_absmax = x_absmax;
-    e2e::note_kernel("conv133_wgrad_%s chunks=%d pairs=%d", q.h2 ? "h2" : "bf3", nchunks, pairs);
-    rc = e2e::launch_wgrad_bf3(q, nchunks, pairs, st);
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
-  }
-  if (use_v3(Cin, Hi, Wi, sh, sw)) {
-    const bool wide = v3_wide_out(Cin, Cout);
-    p.cblocks = wide ? e2e::cdiv(Cin, 32) : e2e::cdiv(Cin, 64);
-    const int pairs = v3_pairs(Cin, Cout);
-    nchunks = plan_v3(p, pairs);
-    e2e::note_kernel("conv133_wgrad_v3<%s> chunks=%d pairs=%d", v3_ksplit(Cin, Cout) ? "1,1,2" : (wide ? "1,2,1" : "2,1,1"), nchunks, pairs);
-    if (v3_ksplit(Cin, Cout)) {
-      p.cblocks = 1;
-      hipLaunchKernelGGL((conv133_wgrad_v3_kernel<1, 1, 2>), dim3(nchunks, pairs), dim3(512), 0, st, p);
-      nchunks *= 2;                                      // two row-half slabs per workgroup
-    } else if (wide) hipLaunchKernelGGL((conv133_wgrad_v3_kernel<1, 2, 1>), dim3(nchunks, pairs), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((conv133_wgrad_v3_kernel<2, 1, 1>), dim3(nchunks, pairs), dim3(512), 0, st, p);
-    rc = e2e::check_launch("conv133_wgrad_v3_kernel");
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
-  }
-  if (use_bf3_w16(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
-    const int pairs = bf3_pairs(Cin, Cout);
-    nchunks = plan_w16(p, pairs);
-    e2e::WgBf3Params q{};
-    q.chans = chans; q.dy = dy; q.slab = p.slab;
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.Di = Di; q.Hi = Hi; q.Wi = Wi; q.Do = p.Do; q.sd = sd;
-    q.tiles_x = p.tiles_x; q.tiles_y = p.tiles_y; q.tiles_per_n = p.tiles_per_n; q.tiles_per_chunk = p.tiles_per_chunk;
-    q.segs = p.cblocks_segs; q.cblocks = e2e::cdiv(Cin, 32); q.geom = 1;
-    q.h2 = wg_h2_env() && dy_absmax != nullptr; q.dy_absmax = dy_absmax; q.x_absmax = x_absmax;
-    e2e::note_kernel("conv133_wgrad_%sw16 chunks=%d pairs=%d", q.h2 ? "h2" : "bf3", nchunks, pairs);
-    rc = e2e::launch_wgrad_bf3(q, nchunks, pairs, st);
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
-  }
-  if (use_v2(Hi, Wi, sh, sw)) {
-    const int ncb = v2_ncb(Cin, p.Ho, p.Wo);
-    p.cblocks = e2e::cdiv(Cin, 32 * ncb);
-    const int pairs = p.cblocks * e2e::cdiv(Cout, 32);
-    plan(p, ts, pairs, &nchunks, 512);
-    e2e::note_kernel("conv133_wgrad_v2<%d,%d,%d,%d> chunks=%d pairs=%d", ts.nd == 1 ? 1 : 4, ts.nd == 1 ? (ts.tw == 32 ? 8 : 16) : 8, ts.nd == 1 ? ts.tw : 8, ts.nd == 1 ? ncb : 1, nchunks, pairs);
-    if (ts.nd == 1 && ts.tw == 32) rc = ncb == 2 ? launch_v2<1, 8, 32, 2>(p, nchunks, pairs, st) : launch_v2<1, 8, 32, 1>(p, nchunks, pairs, st);
-    else if (ts.nd == 1) rc = ncb == 2 ? launch_v2<1, 16, 16, 2>(p, nchunks, pairs, st) : launch_v2<1, 16, 16, 1>(p, nchunks, pairs, st);
-    else rc = launch_v2<4, 8, 8, 1>(p, nchunks, pairs, st);
-    if (rc != E2E_OK) return rc;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                       nchunks);
-    return e2e::check_launch("wgrad_slab_reduce_kernel");
-  }
-  p.cblocks = e2e::cdiv(Cin, 32);
-  const int pairs = p.cblocks * e2e::cdiv(Cout, 32);
-  plan(p, ts, pairs, &nchunks);
-  e2e::note_kernel("conv133_wgrad_v1<%d,%d,%d,%d,%d> chunks=%d pairs=%d", sh, sw, ts.nd, ts.th, ts.tw, nchunks, pairs);
-  if (!strided) {
-    if (ts.nd == 1 && ts.tw == 32) rc = launch<1, 1, 1, 8, 32>(p, nchunks, pairs, st);
-    else if (ts.nd == 1) rc = launch<1, 1, 1, 16, 16>(p, nchunks, pairs, st);
-    else if (ts.nd == 4) rc = launch<1, 1, 4, 8, 8>(p, nchunks, pairs, st);
-    else rc = launch<1, 1, 16, 4, 4>(p, nchunks, pairs, st);
-  } else if (sh == 2 && sw == 2) {
-    rc = dispatch_strided<2, 2>(p, ts, nchunks, pairs, st);
-  } else if (sh == 1 && sw == 2) {
-    rc = dispatch_strided<1, 2>(p, ts, nchunks, pairs, st);
-  } else {
-    rc = dispatch_strided<2, 1>(p, ts, nchunks, pairs, st);
-  }
+  if (rc == E2E_OK) rc = e2e::check_launch("conv133_wgrad");    // (the split-operand launcher has checked its own launch already)
   if (rc != E2E_OK) return rc;
-  hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, p.slab, dw, numel,
-                     nchunks);
-  return e2e::check_launch("wgrad_slab_reduce_kernel");
+  return e2e::reduce_slabs(p.slab, dw, (long long)Cout * Cin * 9, pl.slabs, st);
 }

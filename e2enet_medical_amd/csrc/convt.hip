@@ -1298,41 +1298,6 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
   }
 }
 
-
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out,
-                                                          long long numel, int nchunks) {
-  // out[e] = sum_k slab[k][e]: 4 waves x 4 independent running sums per element, combined in a fixed order
-  // (deterministic); the serial one-thread-per-element loop over up to 512 slabs was latency bound
-  __shared__ float part[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long long e = (long long)blockIdx.x * 64 + lane;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (e < numel) {
-    for (int k = w; k < nchunks; k += 16) {
-      s0 += slab[(long long)k * numel + e];
-      if (k + 4 < nchunks) s1 += slab[(long long)(k + 4) * numel + e];
-      if (k + 8 < nchunks) s2 += slab[(long long)(k + 8) * numel + e];
-      if (k + 12 < nchunks) s3 += slab[(long long)(k + 12) * numel + e];
-    }
-  }
-  part[w][lane] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (w == 0 && e < numel) out[e] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-}
-
-inline int wgrad_chunks(long long total_tiles, int pairs, int* tiles_per_chunk, int per_cu = 1) {
-  // aim at ~256 workgroups (one 84 KB workgroup per CU, equal work each; per_cu = 2: 512) and keep the slabs few: every chunk is
-  // a slab the reduction has to read (1024 chunks cost 14 % more on the 64 -> 32 @64^3 layer); at least 8 tiles per chunk
-  const int target = 256;
-  long long want = (long long)target * per_cu / (pairs > 0 ? pairs : 1);
-  if (want < 1) want = 1;
-  long long tpc = e2e::cdivll(total_tiles, want);
-  if (tpc < 8) tpc = 8;
-  if (tpc > total_tiles) tpc = total_tiles;
-  *tiles_per_chunk = (int)tpc;
-  return (int)e2e::cdivll(total_tiles, tpc);
-}
-
 }  // namespace
 
 #define DISPATCH_KT(KTV, ...)                  \
@@ -1350,6 +1315,8 @@ static int check_k(int kd, int kh, int kw) {
 
 // fp16 two-piece operands (round 6) where the caller hands over the range words; E2E_CT_H2=0 keeps the bf16 three-piece form
 static int ct_h2_env() { static const int v = getenv("E2E_CT_H2") ? atoi(getenv("E2E_CT_H2")) : 1; return v; }
+// E2E_CT_BF3=0 keeps the round-2 kernels (gather forward, fp32-MFMA gradients) instead of the split-operand matrix-pipe ones
+static int ct_bf3_env() { static const int v = getenv("E2E_CT_BF3") ? atoi(getenv("E2E_CT_BF3")) : 1; return v; }
 
 extern "C" int e2e_convT_fwd(const float* x, const float* scale, const float* shift, float slope, const float* w,
                              const unsigned* live, float* y, int B, int Cin, int Cout, int D, int H, int W, int kd,
@@ -1361,9 +1328,8 @@ extern "C" int e2e_convT_fwd(const float* x, const float* scale, const float* sh
   hipStream_t st = (hipStream_t)stream;
   const long long spatial = (long long)D * H * W;
   const int kt = kd * kh * kw;
-  static const int use_bf3 = getenv("E2E_CT_BF3") ? atoi(getenv("E2E_CT_BF3")) : 1;
   const int kdh = kd * kh;
-  if (use_bf3 && kw == 2 && (kdh == 2 || kdh == 4) && W % 32 == 0 && Cin <= 256 && (spatial / 32) * B >= 256) {
+  if (ct_bf3_env() && kw == 2 && (kdh == 2 || kdh == 4) && W % 32 == 0 && Cin <= 256 && (spatial / 32) * B >= 256) {
     const int nkb = Cin <= 64 ? 2 : (Cin <= 128 ? 4 : 8);
     const int cols_per_wg = 4 * (8 / nkb) * 16;
     const int cgroups = e2e::cdiv(Cout * kt, cols_per_wg);
@@ -1407,10 +1373,6 @@ extern "C" int e2e_convT_fwd(const float* x, const float* scale, const float* sh
   return e2e::check_launch("convT_fwd_kernel");
 }
 
-static int dg_min_tiles() {
-  return 256;                                               // 256 tiles (16^3 x 2) still win over the gather kernel, 64 do not
-}
-
 extern "C" int e2e_convT_dgrad(const float* dy, const float* w, const unsigned* live_t, float* dx, int accumulate,
                                int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw, const unsigned* w_absmax,
                                const unsigned* dy_bound_a, const unsigned* dy_bound_b, void* stream) {
@@ -1420,9 +1382,8 @@ extern "C" int e2e_convT_dgrad(const float* dy, const float* w, const unsigned* 
   hipStream_t st = (hipStream_t)stream;
   const long long spatial = (long long)D * H * W;
   // v3 / v4 (dense GEMM on the matrix cores) for the large planes; E2E_CT_BF3=0 keeps the fp32 matrix instructions (v3)
-  const int no_v3 = 0;
-  static const int use_bf3 = getenv("E2E_CT_BF3") ? atoi(getenv("E2E_CT_BF3")) : 1;
-  if (!no_v3 && kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0 && e2e::cdivll(spatial, 32) * B >= dg_min_tiles()) {
+  const int min_tiles = 256;                                // 256 tiles (16^3 x 2) still win over the gather kernel, 64 do not
+  if (kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0 && e2e::cdivll(spatial, 32) * B >= min_tiles) {
     const long long total_tiles = e2e::cdivll(spatial, 32) * B;
     const int cgroups = e2e::cdiv(Cin, 64);
     const int target = 512;                                 // two 4-wave workgroups fit a CU (218 VGPRs): exactly one round (768: 0.174 -> 0.203 ms)
@@ -1431,7 +1392,7 @@ extern "C" int e2e_convT_dgrad(const float* dy, const float* w, const unsigned* 
     int tpw = (int)e2e::cdivll(total_tiles, wgs);
     if (tpw < 4) tpw = 4;
     dim3 grid((unsigned)e2e::cdivll(total_tiles, tpw), cgroups);
-    if (use_bf3 && W % 32 == 0) {
+    if (ct_bf3_env() && W % 32 == 0) {
       const bool h2 = ct_h2_env() && w_absmax != nullptr && dy_bound_a != nullptr;
       e2e::note_kernel("convT_dgrad_%s<%d> wgs=%u cgroups=%d tiles_per_wg=%d", h2 ? "h2" : "bf3", kd * kh, grid.x, cgroups, tpw);
 #define LAUNCH_D3(KDH, NP) hipLaunchKernelGGL((convT_dgrad_bf3_kernel<KDH, NP>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, \
@@ -1465,21 +1426,35 @@ extern "C" int e2e_convT_dgrad(const float* dy, const float* w, const unsigned* 
   return e2e::check_launch("convT_dgrad_kernel");
 }
 
-// (32-voxel tiles of the bf16x3 weight gradient, two workgroups per CU, were measured SLOWER than one workgroup per CU with 64-voxel
-// tiles on every level but the 8^3 one -- 0.215 -> 0.27 ms at 64 -> 32 @64^3, profiles/r04_convt_wgrad_tiles.txt -- and removed in
-// round 5)
-static bool convT_use_v2(int D, int H, int W, int kd, int kh, int kw) {
-  return kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && ((long long)D * H * W) % 4 == 0;
+// What e2e_convT_wgrad_ws_bytes and e2e_convT_wgrad share: the launch writes `slabs` slabs of Cin x Cout x kt floats into a
+// workspace that carries no size, so the size query is this plan's slab count and nothing else.
+enum CtWgPath { CT_WG_V1, CT_WG_V2, CT_WG_BF3 };
+struct CtWgPlan {
+  CtWgPath path;
+  int ncb;               // 32-channel input blocks per workgroup
+  int cgroups, pairs;    // input-channel groups; launch grid y
+  int tiles_per_chunk;
+  int slabs;             // launch grid x = slabs the main kernel writes = slabs the reduction reads
+};
+static CtWgPlan plan_convT_wgrad(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw) {
+  CtWgPlan pl{};
+  const long long spatial = (long long)D * H * W;
+  const bool mfma = kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0;
+  pl.path = !mfma ? CT_WG_V1 : (ct_bf3_env() ? CT_WG_BF3 : CT_WG_V2);
+  pl.ncb = (mfma && Cin > 32) ? 2 : 1;
+  pl.cgroups = e2e::cdiv(Cin, 32 * pl.ncb);
+  pl.pairs = pl.cgroups * e2e::cdiv(Cout, 32);
+  // aim at ~256 workgroups (one 84 KB workgroup per CU, equal work each) and keep the slabs few: every chunk is a slab the
+  // reduction has to read (1024 chunks cost 14 % more on the 64 -> 32 @64^3 layer); at least 8 tiles per chunk
+  // (32-voxel tiles of the bf16x3 weight gradient, two workgroups per CU, were measured SLOWER than one workgroup per CU with
+  // 64-voxel tiles on every level but the 8^3 one -- 0.215 -> 0.27 ms at 64 -> 32 @64^3, profiles/r04_convt_wgrad_tiles.txt --
+  // and removed in round 5)
+  pl.slabs = e2e::split_tiles(e2e::cdivll(spatial, WG_TPX) * B, pl.pairs, 256, 8, &pl.tiles_per_chunk);
+  return pl;
 }
-static int convT_v2_ncb(int Cin) { return Cin > 32 ? 2 : 1; }
 
 extern "C" long long e2e_convT_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw) {
-  const long long total_tiles = e2e::cdivll((long long)D * H * W, WG_TPX) * B;
-  int tpc;
-  int pairs = e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 32);
-  if (convT_use_v2(D, H, W, kd, kh, kw)) pairs = e2e::cdiv(Cin, 32 * convT_v2_ncb(Cin)) * e2e::cdiv(Cout, 32);
-  int nchunks = wgrad_chunks(total_tiles, pairs, &tpc);
-  return (long long)nchunks * Cin * Cout * kd * kh * kw * (long long)sizeof(float);
+  return (long long)plan_convT_wgrad(B, Cin, Cout, D, H, W, kd, kh, kw).slabs * Cin * Cout * kd * kh * kw * (long long)sizeof(float);
 }
 
 extern "C" int e2e_convT_wgrad(const float* x, const float* scale, const float* shift, float slope, const float* dy,
@@ -1489,23 +1464,15 @@ extern "C" int e2e_convT_wgrad(const float* x, const float* scale, const float* 
   E2E_REQUIRE(check_k(kd, kh, kw), "convT_wgrad: kernel must be in {1,2}^3");
   E2E_REQUIRE((long long)D * H * W * kd * kh * kw < (1ll << 31), "convT_wgrad: a sample must have fewer than 2^31 output voxels");
   hipStream_t st = (hipStream_t)stream;
-  const long long total_tiles = e2e::cdivll((long long)D * H * W, WG_TPX) * B;
-  int tpc;
-  const int kt = kd * kh * kw;
+  const CtWgPlan pl = plan_convT_wgrad(B, Cin, Cout, D, H, W, kd, kh, kw);
+  const int kt = kd * kh * kw, kdh = kd * kh, ncb = pl.ncb, tpc = pl.tiles_per_chunk, cgroups = pl.cgroups;
   float* slab = reinterpret_cast<float*>(ws);
-  const long long numel_all = (long long)Cin * Cout * kt;
-  if (convT_use_v2(D, H, W, kd, kh, kw)) {
-    const int ncb = convT_v2_ncb(Cin);
-    const int cgroups = e2e::cdiv(Cin, 32 * ncb);
-    const int pairs2 = cgroups * e2e::cdiv(Cout, 32);
-    const int nch = wgrad_chunks(total_tiles, pairs2, &tpc);
-    dim3 grid2(nch, pairs2);
-    const int kdh = kd * kh;
-    static const int use_bf3 = getenv("E2E_CT_BF3") ? atoi(getenv("E2E_CT_BF3")) : 1;
-    if (use_bf3) {
+  const dim3 grid(pl.slabs, pl.pairs);
+  switch (pl.path) {
+    case CT_WG_BF3: {
       const bool h2 = ct_h2_env() && x_absmax != nullptr && dy_bound_a != nullptr;
-      e2e::note_kernel("convT_wgrad_%s<%d,%d> chunks=%d pairs=%d", h2 ? "h2" : "bf3", kdh, ncb, nch, pairs2);
-#define LAUNCH_B3(KDH, NCB, TPX, NP) hipLaunchKernelGGL((convT_wgrad_bf3_kernel<KDH, NCB, TPX, NP>), grid2, dim3(256 * NCB), 0, st, x, scale, shift, \
+      e2e::note_kernel("convT_wgrad_%s<%d,%d> chunks=%d pairs=%d", h2 ? "h2" : "bf3", kdh, ncb, pl.slabs, pl.pairs);
+#define LAUNCH_B3(KDH, NCB, TPX, NP) hipLaunchKernelGGL((convT_wgrad_bf3_kernel<KDH, NCB, TPX, NP>), grid, dim3(256 * NCB), 0, st, x, scale, shift, \
                                                         slope, dy, slab, B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups, x_absmax, dy_bound_a, dy_bound_b)
       if (h2) {
         if (kdh == 4) { if (ncb == 2) LAUNCH_B3(4, 2, 64, 2); else LAUNCH_B3(4, 1, 64, 2); }
@@ -1515,25 +1482,23 @@ extern "C" int e2e_convT_wgrad(const float* x, const float* scale, const float* 
         else { if (ncb == 2) LAUNCH_B3(2, 2, 64, 3); else LAUNCH_B3(2, 1, 64, 3); }
       }
 #undef LAUNCH_B3
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel_all, 64)), dim3(256), 0, st, slab, dw, numel_all, nch);
-      return e2e::check_launch("convT_wgrad_bf3");
+      break;
     }
-    e2e::note_kernel("convT_wgrad_v2<%d,%d> chunks=%d pairs=%d", kdh, ncb, nch, pairs2);
-#define LAUNCH_V2(KDH, NCB) hipLaunchKernelGGL((convT_wgrad_v2_kernel<KDH, NCB>), grid2, dim3(256 * NCB), 0, st, x, scale, shift, \
+    case CT_WG_V2:
+      e2e::note_kernel("convT_wgrad_v2<%d,%d> chunks=%d pairs=%d", kdh, ncb, pl.slabs, pl.pairs);
+#define LAUNCH_V2(KDH, NCB) hipLaunchKernelGGL((convT_wgrad_v2_kernel<KDH, NCB>), grid, dim3(256 * NCB), 0, st, x, scale, shift, \
                                                slope, dy, slab, B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups)
-    if (kdh == 4) { if (ncb == 2) LAUNCH_V2(4, 2); else LAUNCH_V2(4, 1); }
-    else { if (ncb == 2) LAUNCH_V2(2, 2); else LAUNCH_V2(2, 1); }
+      if (kdh == 4) { if (ncb == 2) LAUNCH_V2(4, 2); else LAUNCH_V2(4, 1); }
+      else { if (ncb == 2) LAUNCH_V2(2, 2); else LAUNCH_V2(2, 1); }
 #undef LAUNCH_V2
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel_all, 64)), dim3(256), 0, st, slab, dw, numel_all, nch);
-    return e2e::check_launch("convT_wgrad_v2");
+      break;
+    case CT_WG_V1:
+      e2e::note_kernel("convT_wgrad_v1<%d> chunks=%d pairs=%d", kt, pl.slabs, pl.pairs);
+      DISPATCH_KT(kt, hipLaunchKernelGGL((convT_wgrad_kernel<KT>), grid, dim3(256), 0, st, x, scale, shift, slope, dy, slab, B,
+                                         Cin, Cout, D, H, W, kd, kh, kw, tpc, pl.slabs));
+      break;
   }
-  const int pairs = e2e::cdiv(Cin, 32) * e2e::cdiv(Cout, 32);
-  const int nchunks = wgrad_chunks(total_tiles, pairs, &tpc);
-  dim3 grid(nchunks, pairs);
-  e2e::note_kernel("convT_wgrad_v1<%d> chunks=%d pairs=%d", kt, nchunks, pairs);
-  DISPATCH_KT(kt, hipLaunchKernelGGL((convT_wgrad_kernel<KT>), grid, dim3(256), 0, st, x, scale, shift, slope, dy, slab, B,
-                                     Cin, Cout, D, H, W, kd, kh, kw, tpc, nchunks));
-  const long long numel = (long long)Cin * Cout * kt;
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)e2e::cdivll(numel, 64)), dim3(256), 0, st, slab, dw, numel, nchunks);
-  return e2e::check_launch("convT_wgrad");
+  const int rc = e2e::check_launch("convT_wgrad");
+  if (rc != E2E_OK) return rc;
+  return e2e::reduce_slabs(slab, dw, (long long)Cin * Cout * kt, pl.slabs, st);
 }

@@ -526,11 +526,11 @@ def test_conv133_wgrad_alternative_paths_forced(env):
     maximum gets), E2E_WG_BF3=0 the fp32-MFMA kernels.  E2E_CONV_MM=0: forward / data gradient of the 16 x 32 tile class on the
     round-4 kernels (sparse plan walk, bf16x3 dense kernel) instead of conv133_mm_kernel; E2E_MM_GRID=8: that kernel as eight
     persistent workgroups (long item runs per workgroup: every pipeline transition).  The knobs are read once per process: run the
-    operator cases again in a child process."""
+    operator cases and the workspace-bound cases again in a child process."""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k",
-                        "test_conv133_fwd_bwd", "-p", "no:cacheprovider"],
+                        "test_conv133_fwd_bwd or test_wgrad_stays_inside_the_workspace_it_asked_for", "-p", "no:cacheprovider"],
                        env=dict(os.environ, **env), capture_output=True, text=True, timeout=900,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
@@ -614,6 +614,91 @@ def test_conv133_wgrad_h2_and_bf3_vs_fp64(tag, B, src_desc, cout, dims):
     # a dy of zeros (dead branch) and a dy with one huge entry: finite, exact zero / dominated by that entry
     z, _ = run(torch.zeros_like(dy), True)
     assert torch.equal(z, torch.zeros_like(z))
+
+
+def _wg_split(w16=False):
+    """dispatch note of the split-operand conv weight gradient handed both range words"""
+    return "conv133_wgrad_%s%s " % ("h2" if os.environ.get("E2E_WG_H2", "1") != "0" else "bf3", "w16" if w16 else "")
+
+
+_WG_BF3_ON = os.environ.get("E2E_WG_BF3", "1") != "0"
+_CT_SPLIT = ("convT_wgrad_v2<" if os.environ.get("E2E_CT_BF3", "1") == "0" else
+             "convT_wgrad_h2<" if os.environ.get("E2E_CT_H2", "1") != "0" else "convT_wgrad_bf3<")
+
+WGRAD_WS_CASES = [
+    # (family, B, Cin, Cout, (D,H,W), stride | kernel, dispatch note by default, with E2E_WG_BF3=0)
+    ("conv", 1, 35, 40, (6, 32, 64), (2, 2, 2), "conv133_wgrad_s2 ", "conv133_wgrad_s2 "),
+    ("conv", 2, 3, 40, (3, 20, 36), (1, 1, 1), "conv133_wgrad_smallc ", "conv133_wgrad_smallc "),
+    ("conv", 2, 20, 24, (2, 20, 36), (1, 1, 1), _wg_split(), "conv133_wgrad_v3<1,1,2> "),       # one 32 x 32 block: two slabs per workgroup
+    ("conv", 1, 40, 64, (3, 20, 36), (1, 1, 1), _wg_split(), "conv133_wgrad_v3<1,2,1> "),
+    ("conv", 2, 90, 70, (2, 20, 36), (1, 1, 1), _wg_split(), "conv133_wgrad_v3<2,1,1> "),
+    ("conv", 1, 40, 33, (4, 24, 16), (1, 1, 1), _wg_split(True), "conv133_wgrad_v2<1,16,16,2> "),
+    ("conv", 2, 4, 9, (2, 20, 28), (1, 1, 1), "conv133_wgrad_v2<1,8,32,1> ", "conv133_wgrad_v2<1,8,32,1> "),
+    ("conv", 1, 40, 33, (3, 12, 12), (1, 1, 1), "conv133_wgrad_v2<1,16,16,2> ", "conv133_wgrad_v2<1,16,16,2> "),
+    ("conv", 1, 40, 33, (5, 8, 8), (1, 1, 1), "conv133_wgrad_v2<4,8,8,1> ", "conv133_wgrad_v2<4,8,8,1> "),
+    ("conv", 2, 13, 9, (4, 9, 11), (1, 1, 1), "conv133_wgrad_v1<1,1,1,16,16> ", "conv133_wgrad_v1<1,1,1,16,16> "),
+    ("conv", 2, 10, 12, (5, 18, 10), (1, 2, 2), "conv133_wgrad_v1<2,2,2,8,8> ", "conv133_wgrad_v1<2,2,2,8,8> "),     # <sh, sw, tile>
+    ("convT", 2, 40, 24, (4, 8, 8), (2, 2, 2), _CT_SPLIT, _CT_SPLIT),
+    ("convT", 1, 9, 5, (3, 6, 8), (2, 2, 1), "convT_wgrad_v1<4> ", "convT_wgrad_v1<4> "),        # kw == 1
+    ("convT", 2, 40, 33, (3, 5, 7), (2, 2, 2), "convT_wgrad_v1<8> ", "convT_wgrad_v1<8> "),      # odd W
+]
+
+
+@pytest.mark.parametrize("case", WGRAD_WS_CASES)
+def test_wgrad_stays_inside_the_workspace_it_asked_for(case):
+    """The weight-gradient entry points take a bare workspace pointer; what keeps the main kernel inside it is that the size query
+    and the launch follow one plan.  One shape per path of both families: the workspace is exactly the queried bytes, followed in
+    the same allocation by 1 MiB of guard words (ordinary memory: nothing faults even if a plan were wrong).  The guard must come
+    back untouched, dw must equal the dw of a roomy workspace bit for bit, and the dispatch note must name the path the case was
+    chosen for (test_conv133_wgrad_alternative_paths_forced runs this again with E2E_WG_BF3=0: v3 in its three forms, v2 on
+    16-wide planes)."""
+    from e2enet_medical_amd.engine import ConvOp, UpOp
+    from e2enet_medical_amd._lib import lib
+    family, B, cin, cout, dims, sk, note_default, note_fp32 = case
+    L = lib()
+    src = _make_act((B, cin) + dims, True, 90)
+    xmax = float(_act_value(src).abs().max())
+    if family == "conv":
+        e = _eng_stub({"blk.conv.weight": torch.zeros(cout, cin, 1, 3, 3), "blk.conv.bias": torch.zeros(cout),
+                       "blk.instnorm.weight": torch.ones(cout), "blk.instnorm.bias": torch.zeros(cout)})
+        op = ConvOp(e, "blk", [src], cout, sk)
+        op.set_input_range(xmax)
+        dy = seeded_input((B, cout) + op.out_dims, seed=91).cuda()
+        word = _absmax_word(dy)
+        nbytes = int(L.conv133_wgrad_ws_bytes(B, cin, cout, *dims, *sk))
+        dw_shape = (cout, cin, 1, 3, 3)
+
+        def run(ws_ptr, dw):
+            L.conv133_wgrad(op.chans.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws_ptr, B, cin, cout, *dims, *sk, word.data_ptr(),
+                            op.x_absmax_ptr(), 0)
+    else:
+        e = _eng_stub({"up.weight": torch.zeros((cin, cout) + sk)})
+        op = UpOp(e, "up.weight", src, cout, sk)
+        op.set_ranges(xmax, 1.0, 1.0)
+        dy = seeded_input(tuple(op.out.shape), seed=91).cuda()
+        word = _absmax_word(dy)
+        nbytes = int(L.convT_wgrad_ws_bytes(B, cin, cout, *dims, *sk))
+        dw_shape = (cin, cout) + sk
+
+        def run(ws_ptr, dw):
+            L.convT_wgrad(src.data.data_ptr(), src.scale.data_ptr(), src.shift.data_ptr(), 0.01, dy.data_ptr(), dw.data_ptr(), ws_ptr,
+                          B, cin, cout, *dims, *sk, op._w(0), word.data_ptr(), op._w(2), 0)
+    assert nbytes > 0 and nbytes % 4 == 0
+    sentinel, guard_words = 0x5A5A5A5A, (1 << 20) // 4
+    buf = torch.full((nbytes // 4 + guard_words,), sentinel, dtype=torch.int32, device=_dev())   # workspace, then the guard
+    dw_tight = torch.full(dw_shape, float("nan"), device=_dev())
+    run(buf.data_ptr(), dw_tight)
+    torch.cuda.synchronize()
+    note = (L.last_kernel() or b"").decode()
+    dw_roomy = torch.full(dw_shape, float("nan"), device=_dev())
+    run(e.wgrad_ws.data_ptr(), dw_roomy)
+    torch.cuda.synchronize()
+    assert note == (L.last_kernel() or b"").decode()
+    assert note.startswith(note_default if _WG_BF3_ON else note_fp32), note
+    print("wgrad workspace %s: %d bytes, %s" % (case[:6], nbytes, note))
+    assert bool((buf[nbytes // 4:] == sentinel).all()), "the weight gradient wrote past the workspace it asked for"
+    assert torch.isfinite(dw_tight).all()
+    assert torch.equal(dw_tight.view(torch.int32), dw_roomy.view(torch.int32)), "dw differs between the exact and the roomy workspace"
 
 
 @pytest.mark.parametrize("K", [256, 4096, 65536])
