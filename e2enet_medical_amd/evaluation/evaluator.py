@@ -4,8 +4,13 @@ e2enet/evaluation/metrics.py:106-121, :601-790).
 
 Host tooling, not the hot path: the inputs are the exported uint8 label volumes.  One joint histogram of (reference, test)
 labels per case replaces the reference's thirteen boolean passes per label; the numbers are the same integers divided the same
-way.  The surface-distance metrics (``default_advanced_metrics``) are not evaluated by ``aggregate_scores`` either
-(``evaluate(advanced=False)``).
+way.
+
+``advanced=True`` adds the reference's ``default_advanced_metrics`` (evaluator.py:53-59: "Hausdorff Distance 95", "Avg. Surface
+Distance", "Avg. Symmetric Surface Distance") and, with ``nsd_tolerance``, "Normalized Surface Dice" (surface_dice.py:20-56).
+Those are computed on the device (``surface_distance.py``, csrc/surface.hip) under the case's ``voxel_spacing``; the empty / full
+rule of metrics.py:797-803 is applied from the voxel counts first, so a case without a scorable label needs no device.  With the
+defaults the output is the thirteen confusion-matrix metrics, as ``evaluate(advanced=False)`` gives them.
 """
 import hashlib
 import json
@@ -59,29 +64,48 @@ def metrics_from_counts(tp, fp, tn, fn, nan_for_nonexisting=True):
     return OrderedDict((k, res[k]) for k in sorted(res))
 
 
-def evaluate_pair(test: np.ndarray, reference: np.ndarray, labels, nan_for_nonexisting=True):
-    """label (str) -> metric dict: ``Evaluator.evaluate`` for a list of integer labels (evaluator.py:216-226)."""
+def evaluate_pair(test: np.ndarray, reference: np.ndarray, labels, nan_for_nonexisting=True, advanced=False, voxel_spacing=None,
+                  nsd_tolerance=None):
+    """label (str) -> metric dict: ``Evaluator.evaluate`` for a list of integer labels (evaluator.py:216-226).  ``advanced``: the
+    surface-distance metrics under ``voxel_spacing`` (array-axis order, None = 1 mm) join each dict, keys sorted as before."""
     counts = confusion_counts(test, reference, labels)
-    return OrderedDict((str(l), metrics_from_counts(*counts[l], nan_for_nonexisting)) for l in labels)
+    res = OrderedDict((str(l), metrics_from_counts(*counts[l], nan_for_nonexisting)) for l in labels)
+    if advanced:
+        from .surface_distance import surface_distance_metrics, ADVANCED_METRICS, NSD_KEY
+        surf = surface_distance_metrics(test, reference, labels, voxel_spacing, nsd_tolerance, nan_for_nonexisting)
+        names = ADVANCED_METRICS + ((NSD_KEY,) if nsd_tolerance is not None else ())
+        for l in labels:
+            d = dict(res[str(l)])
+            d.update((k, surf[int(l)][k]) for k in names)
+            res[str(l)] = OrderedDict((k, d[k]) for k in sorted(d))
+    return res
 
 
 def aggregate_scores(cases, labels, nanmean=True, json_output_file=None, json_name="", json_description="",
-                     json_author="Fabian", json_task=""):
-    """``cases``: iterable of (test array, reference array, test name, reference name).  Returns the reference's
+                     json_author="Fabian", json_task="", advanced=False, voxel_spacing=None, nsd_tolerance=None):
+    """``cases``: iterable of (test array, reference array, test name, reference name[, voxel spacing]).  Returns the reference's
     ``all_scores`` ({"all": [per case], "mean": {label: {metric: mean}}}) and writes the reference's summary.json
-    (evaluator.py:353-400) when ``json_output_file`` is given."""
+    (evaluator.py:353-400) when ``json_output_file`` is given.  ``advanced``: see ``evaluate_pair``; a case's own fifth element
+    overrides ``voxel_spacing``, and the case's entry records the spacing it was scored with under "voxel_spacing"."""
     all_scores = OrderedDict()
     all_scores["all"] = []
     all_scores["mean"] = OrderedDict()
-    for test, ref, test_name, ref_name in cases:
-        res = evaluate_pair(test, ref, labels)
+    for case in cases:
+        test, ref, test_name, ref_name = case[:4]
+        if advanced:
+            spacing = case[4] if len(case) > 4 and case[4] is not None else voxel_spacing
+            spacing = [1., 1., 1.] if spacing is None else [float(v) for v in spacing]
+            res = evaluate_pair(test, ref, labels, advanced=True, voxel_spacing=spacing, nsd_tolerance=nsd_tolerance)
+            res["voxel_spacing"] = spacing
+        else:
+            res = evaluate_pair(test, ref, labels)
         if test_name is not None:
             res["test"] = test_name
         if ref_name is not None:
             res["reference"] = ref_name
         all_scores["all"].append(res)
         for label, score_dict in res.items():
-            if label in ("test", "reference"):
+            if label in ("test", "reference", "voxel_spacing"):
                 continue
             dst = all_scores["mean"].setdefault(label, OrderedDict())
             for score, value in score_dict.items():

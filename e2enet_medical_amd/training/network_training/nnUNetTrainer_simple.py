@@ -853,10 +853,22 @@ class nnUNetTrainer_simple(object):
         return ret
 
     # ------------------------------------------------------------------------------------------ validation
+    def _scoring_spacing(self, properties, original_grid):
+        """voxel spacing (array-axis order) of the grid a validation case is scored on, or None when nothing states it (the
+        surface metrics then assume 1 mm)"""
+        if original_grid:
+            s = properties.get('itk_spacing')
+            return None if s is None else [float(v) for v in s][::-1]
+        s = properties.get('spacing_after_resampling')
+        if s is None:
+            s = self.plans['plans_per_stage'][self.stage].get('current_spacing') if self.plans else None
+        return None if s is None else [float(v) for v in s]
+
     def validate(self, do_mirroring: bool = True, use_sliding_window: bool = True, step_size: float = 0.5,
                  save_softmax: bool = True, use_gaussian: bool = True, overwrite: bool = True,
                  validation_folder_name: str = 'validation_raw', debug: bool = False, all_in_gpu: bool = False,
-                 segmentation_export_kwargs: dict = None, run_postprocessing_on_folds: bool = True, writer=None, gt_reader=None):
+                 segmentation_export_kwargs: dict = None, run_postprocessing_on_folds: bool = True, writer=None, gt_reader=None,
+                 advanced_metrics: bool = False, nsd_tolerance=None):
         """reference :1309-1479: every case of the validation split through the sliding-window prediction, exported to the case's
         original geometry, scored against the ground truth, ``summary.json`` written in the reference's structure.
 
@@ -868,7 +880,13 @@ class nnUNetTrainer_simple(object):
                                                            folder, else the segmentation channel of the preprocessed case (then the
                                                            comparison happens on the network's grid and summary.json says so).
         The connected-component post-processing search (``determine_postprocessing``, e2enet/postprocessing) is outside the hot
-        path and is skipped with a log line.  Returns the score dict ``aggregate_scores`` builds (the reference returns None)."""
+        path and is skipped with a log line.  Returns the score dict ``aggregate_scores`` builds (the reference returns None).
+
+        ``advanced_metrics=True`` adds the reference's ``default_advanced_metrics`` (HD95, ASD, ASSD; evaluation/evaluator.py:53-59)
+        to every label's dict and ``nsd_tolerance`` (mm) the normalized surface Dice, both computed on the device
+        (evaluation/surface_distance.py).  A case scored on its original grid uses ``properties['itk_spacing'][::-1]`` (reference
+        evaluator.py:299-301), one scored on the preprocessed grid its ``properties['spacing_after_resampling']`` (the plans' stage
+        ``current_spacing`` when the properties lack it), both in network-axis order; the case's entry in summary.json records it."""
         import json
         import shutil
         from ...inference.predict import export_segmentation
@@ -971,11 +989,12 @@ class nnUNetTrainer_simple(object):
                     gt_path = join(self.gt_niftis_folder, fname + ".nii.gz") if self.gt_niftis_folder else None
                     gt = gt_reader(gt_path) if gt_path is not None else None
                     if gt is not None and tuple(gt.shape) == tuple(seg.shape):
-                        cases.append((seg, np.asarray(gt), out_nii, gt_path))
+                        cases.append((seg, np.asarray(gt), out_nii, gt_path, self._scoring_spacing(properties, True)))
                         grids.add("original")
                     else:
                         # no readable ground-truth volume: score on the network's grid against the preprocessed case's own labels
-                        cases.append((seg_grid.cpu().numpy().astype(np.uint8), data[-1].astype(np.int16), out_nii, entry['data_file']))
+                        cases.append((seg_grid.cpu().numpy().astype(np.uint8), data[-1].astype(np.int16), out_nii, entry['data_file'],
+                                      self._scoring_spacing(properties, False)))
                         grids.add("preprocessed")
         finally:
             net.keep_on_device = keep
@@ -986,7 +1005,8 @@ class nnUNetTrainer_simple(object):
                                   json_name=self.experiment_name + " val tiled %s" % (str(use_sliding_window)),
                                   json_description="" if grids == {"original"} else
                                   "scored on the network's grid against the preprocessed labels (no readable ground-truth volume)",
-                                  json_author="Fabian", json_task=task)
+                                  json_author="Fabian", json_task=task, advanced=advanced_metrics, nsd_tolerance=nsd_tolerance)
+        cases = [c[:4] for c in cases]
         self._validation_extra(cases, join(output_folder, "summary.json"))
         if run_postprocessing_on_folds:
             self.print_to_log_file("validate: determine_postprocessing (connected-component search, e2enet/postprocessing) is outside "

@@ -533,6 +533,32 @@ int e2e_aug_lowres_up3(const float* coef, float* dst, const double* minmax, int 
                        void* stream);
 int e2e_aug_finish(float* data, float* seg, const int* use_mask, int B, int C, int CS, long long vol, void* stream);
 
+/* ---- E1: surface-distance scoring of exported label volumes ---------------------------------------------------
+ * Replaces: medpy's surface distances behind hausdorff_distance / hausdorff_distance_95 / avg_surface_distance /
+ * avg_surface_distance_symmetric (e2enet/evaluation/metrics.py:792-861) and normalized_surface_dice
+ * (e2enet/evaluation/surface_dice.py:20-56): binary_erosion with the 6-neighbour cross (connectivity 1) and one
+ * scipy.ndimage.distance_transform_edt over the whole volume per label and direction.  Volumes are [D,H,W], W contiguous.
+ *   surface_border: border [D,H,W] u8 = m & ~erode(m) of m = (labels == label), voxels outside the volume count as 0;
+ *     the binary map is formed on load.  *count (device int64, zeroed by the callee) = number of border voxels
+ *   distance_transform_edt_sq: dt2 [D,H,W] fp32 = squared distance to the nearest set voxel of mask under spacing (sd,sh,sw),
+ *     exact up to one fp32 rounding of each axis term and of each of the two sums (integers below 2^24 at unit spacing are
+ *     exact); +inf everywhere for a mask without a set voxel.  One lower-envelope pass per axis, lines staged in LDS: an
+ *     axis longer than the value surface_max_line returns is E2E_ERR_UNSUPPORTED
+ *   surface_distances_stats: with d1 = sqrt(dt2_b) at border_a and d2 = sqrt(dt2_a) at border_b (n voxels each):
+ *     out[0..3] = count, sum (fp64), max, count <= threshold of d1; out[4..7] the same of d2; out[8], out[9] = the values
+ *     of 0-based rank rank_lo and rank_hi in the sorted concatenation of d1 and d2 (the neighbours HD95 interpolates
+ *     between; ranks past the number of border voxels are the caller's error and give an unspecified value).  All ten are
+ *     doubles and the same bits on every run.  ws: surface_distances_ws_bytes bytes                                     */
+int e2e_surface_border(const unsigned char* labels, int label, unsigned char* border, long long* count, int D, int H,
+                       int W, void* stream);
+int e2e_surface_max_line(void);
+int e2e_distance_transform_edt_sq(const unsigned char* mask, float* dt2, int D, int H, int W, double sd, double sh,
+                                  double sw, void* stream);
+long long e2e_surface_distances_ws_bytes(void);
+int e2e_surface_distances_stats(const unsigned char* border_a, const float* dt2_b, const unsigned char* border_b,
+                                const float* dt2_a, long long n, double threshold, long long rank_lo, long long rank_hi,
+                                double* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
