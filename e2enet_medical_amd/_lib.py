@@ -190,11 +190,13 @@ SIGNATURES = {
     "e2e_distance_transform_edt_sq": (I, [P, P, I, I, I, C.c_double, C.c_double, C.c_double, P]),
     "e2e_surface_distances_ws_bytes": (LL, []),
     "e2e_surface_distances_stats": (I, [P, P, P, P, LL, C.c_double, LL, LL, P, P, P]),
+    "e2e_cc_ws_bytes": (LL, [I, I, I]),
+    "e2e_cc_remove_all_but_largest": (I, [P, I, I, I, P, C.c_double, C.c_double, P, P, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
               "e2e_convT_wgrad_ws_bytes", "e2e_conv133_input_ranges_ws_bytes", "e2e_in_lrelu_bwd_ws_doubles", "e2e_head1x1_wgrad_ws_bytes", "e2e_loss_ws_bytes", "e2e_aug_stats_ws_bytes",
-              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes"}
+              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes"}
 
 
 class E2EError(RuntimeError):

@@ -105,9 +105,13 @@ def resample_softmax(softmax: torch.Tensor, new_shape: Sequence[int], transpose_
 
 def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_backward: Optional[Sequence[int]] = None,
                         region_class_order: Optional[Sequence[int]] = None, force_separate_z: Optional[bool] = None,
-                        order: int = 1, interpolation_order_z: int = 0) -> np.ndarray:
+                        order: int = 1, interpolation_order_z: int = 0, postprocessing=None) -> np.ndarray:
     """uint8 label volume in the ORIGINAL (uncropped) geometry from a device softmax [K, X, Y, Z]
-    (reference predict.py:298-301 + segmentation_export.py:73-136)."""
+    (reference predict.py:298-301 + segmentation_export.py:73-136).
+
+    ``postprocessing``: ``(for_which_classes, min_valid_object_sizes or None)`` as ``load_postprocessing`` returns them; all but the
+    largest connected component of those classes is then removed (reference predict.py:339-352, load_remove_save) on the device
+    label volume, before its one download; ``volume_per_voxel`` is the product of ``properties_dict['itk_spacing']``."""
     assert softmax.is_cuda and softmax.dtype == torch.float32 and softmax.dim() == 4 and softmax.is_contiguous()
     k = softmax.shape[0]
     tb = [0, 1, 2] if transpose_backward is None else [int(i) for i in transpose_backward]
@@ -137,22 +141,28 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
                            strides[1], strides[2], out_shape[0], out_shape[1], out_shape[2], off[0], off[1], off[2],
                            regions.data_ptr() if regions is not None else None, len(regions) if regions is not None else 0,
                            _stream())
+    if postprocessing is not None:
+        from ..postprocessing.connected_components import apply_postprocessing
+        for_which_classes, min_valid_object_sizes = postprocessing
+        volume_per_voxel = float(np.prod(properties_dict['itk_spacing'], dtype=np.float64))
+        seg = apply_postprocessing(seg, for_which_classes, min_valid_object_sizes, volume_per_voxel)
     return seg.cpu().numpy()
 
 
 def predict_cases(trainer, params: Sequence[dict], preprocessed: Iterable[Tuple[str, Tuple[np.ndarray, dict]]],
                   writer: Callable[[np.ndarray, str, dict], None], do_tta: bool = True, step_size: float = 0.5,
-                  all_in_gpu: bool = False, mixed_precision: bool = True):
+                  all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None):
     """The per-case loop of reference predict_cases (predict.py:273-331) on preprocessed cases
     ``(output_filename, (data [C,X,Y,Z], properties_dict))``; ``writer(seg_uint8, output_filename, properties_dict)``
-    stores the label volume (the reference's SimpleITK NIfTI writer, segmentation_export.py:144-148, is host tooling)."""
+    stores the label volume (the reference's SimpleITK NIfTI writer, segmentation_export.py:144-148, is host tooling).
+    ``postprocessing``: see ``export_segmentation``."""
     done = []
     for output_filename, (d, dct) in preprocessed:
         if isinstance(d, str):
             d = np.load(d)
         softmax = predict_case_ensemble(trainer, params, d, do_tta, step_size, all_in_gpu, mixed_precision)
         tb = trainer.plans.get('transpose_backward') if trainer.plans.get('transpose_forward') is not None else None
-        seg = export_segmentation(softmax, dct, tb, getattr(trainer, 'regions_class_order', None))
+        seg = export_segmentation(softmax, dct, tb, getattr(trainer, 'regions_class_order', None), postprocessing=postprocessing)
         writer(seg, output_filename, dct)
         done.append(output_filename)
     return done
@@ -210,7 +220,9 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.
     The per-case work is ``predict_cases`` above (softmax resident in HBM).  ``num_threads_*`` are accepted and unused: there are
-    no preprocessing / export worker processes here."""
+    no preprocessing / export worker processes here.  Unless ``disable_postprocessing``, ``<model>/postprocessing.json`` is copied to
+    ``output_folder`` and applied to every case on the device (reference :337-356); when the file is missing the reference's warning
+    is printed and the raw label maps are written."""
     import shutil
     from ..training.model_restore import load_model_and_checkpoint_files
     if mode != "normal":
@@ -238,6 +250,18 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
         return []
     trainer, params = load_model_and_checkpoint_files(model, folds, mixed_precision=mixed_precision, checkpoint_name=checkpoint_name)
     all_in_gpu = False if overwrite_all_in_gpu is None else overwrite_all_in_gpu
+    postprocessing = None
+    if not disable_postprocessing:
+        pp_file = os.path.join(model, "postprocessing.json")
+        if os.path.isfile(pp_file):
+            from ..postprocessing.connected_components import load_postprocessing
+            print("postprocessing...")
+            shutil.copy(pp_file, os.path.abspath(output_folder))
+            postprocessing = load_postprocessing(pp_file)
+        else:
+            print("WARNING! Cannot run postprocessing because the postprocessing file is missing. Make sure to run "
+                  "consolidate_folds in the output folder of the model first!\nThe folder you need to run this in is "
+                  "%s" % model)
 
     def cases():
         for c, out in zip(case_ids, output_files):
@@ -248,4 +272,4 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
             d = np.asarray(d)[:expected_num_modalities]          # (preprocessed training cases carry their labels as a last channel)
             yield out, (d, props)
     return predict_cases(trainer, params, cases(), writer if writer is not None else nifti_writer(), do_tta=tta,
-                         step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision)
+                         step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision, postprocessing=postprocessing)

@@ -55,6 +55,9 @@ def build_parser():
     # ---- extensions of this package (absent from the reference's parser) ----
     parser.add_argument('--base_num_features', type=int, required=False, default=None,
                         help='network width; default: the reference\'s hard-coded 48')
+    parser.add_argument('--determine_postprocessing', action='store_true', default=False,
+                        help='after the validation, search for which classes removing all but the largest connected component '
+                             'improves the Dice and write postprocessing.json (on the device; the reference always does this)')
     parser.add_argument('--synthetic_data', action='store_true', default=False,
                         help='train on seeded Gaussian noise / random labels when no preprocessed data exists')
     add_sparse_args(parser)
@@ -139,7 +142,8 @@ def main(argv=None):
     trainer.network.eval()
     if args.validation_only:
         trainer.validate(save_softmax=args.npz, validation_folder_name=args.val_folder,
-                         run_postprocessing_on_folds=not args.disable_postprocessing_on_folds, overwrite=args.val_disable_overwrite)
+                         run_postprocessing_on_folds=not args.disable_postprocessing_on_folds, overwrite=args.val_disable_overwrite,
+                         determine_postprocessing=args.determine_postprocessing)
     print(f'finish training {args.Tconv} !!!')
     if network == '3d_lowres' and not args.disable_next_stage_pred:
         raise NotImplementedError("predict_next_stage (3d_lowres cascade) is outside the shiftConvPP hot path")

@@ -868,7 +868,7 @@ class nnUNetTrainer_simple(object):
                  save_softmax: bool = True, use_gaussian: bool = True, overwrite: bool = True,
                  validation_folder_name: str = 'validation_raw', debug: bool = False, all_in_gpu: bool = False,
                  segmentation_export_kwargs: dict = None, run_postprocessing_on_folds: bool = True, writer=None, gt_reader=None,
-                 advanced_metrics: bool = False, nsd_tolerance=None):
+                 advanced_metrics: bool = False, nsd_tolerance=None, determine_postprocessing: bool = False):
         """reference :1309-1479: every case of the validation split through the sliding-window prediction, exported to the case's
         original geometry, scored against the ground truth, ``summary.json`` written in the reference's structure.
 
@@ -879,8 +879,12 @@ class nnUNetTrainer_simple(object):
           ``gt_reader(path_nii_gz) -> label array``         default: SimpleITK when importable, else ``<case>.npy`` in the ground-truth
                                                            folder, else the segmentation channel of the preprocessed case (then the
                                                            comparison happens on the network's grid and summary.json says so).
-        The connected-component post-processing search (``determine_postprocessing``, e2enet/postprocessing) is outside the hot
-        path and is skipped with a log line.  Returns the score dict ``aggregate_scores`` builds (the reference returns None).
+        The connected-component post-processing search (``determine_postprocessing``, reference :1446-1453) runs when
+        ``determine_postprocessing=True`` and ``run_postprocessing_on_folds`` is set, after the scoring and with the reference's
+        arguments: on the label volumes this call holds in memory, components labelled on the device
+        (postprocessing/connected_components.py), the decision written to ``<output_folder>/postprocessing.json`` and the final
+        volumes through ``writer`` into ``<validation_folder_name>_postprocessed`` (with its summary.json).  With the default it is
+        skipped with a log line.  Returns the score dict ``aggregate_scores`` builds (the reference returns None).
 
         ``advanced_metrics=True`` adds the reference's ``default_advanced_metrics`` (HD95, ASD, ASSD; evaluation/evaluator.py:53-59)
         to every label's dict and ``nsd_tolerance`` (mm) the normalized surface Dice, both computed on the device
@@ -954,7 +958,7 @@ class nnUNetTrainer_simple(object):
 
         net = self.network
         keep = net.keep_on_device
-        cases, grids = [], set()
+        cases, grids, case_properties = [], set(), []
         try:
             with torch.no_grad():
                 for k in self.dataset_val.keys():
@@ -986,6 +990,7 @@ class nnUNetTrainer_simple(object):
                         np.savez_compressed(join(output_folder, fname + ".npz"),
                                             softmax=softmax.permute(0, *[i + 1 for i in tb]).cpu().numpy().astype(np.float16))
                     writer(seg, out_nii, properties)
+                    case_properties.append(properties)
                     gt_path = join(self.gt_niftis_folder, fname + ".nii.gz") if self.gt_niftis_folder else None
                     gt = gt_reader(gt_path) if gt_path is not None else None
                     if gt is not None and tuple(gt.shape) == tuple(seg.shape):
@@ -1006,9 +1011,16 @@ class nnUNetTrainer_simple(object):
                                   json_description="" if grids == {"original"} else
                                   "scored on the network's grid against the preprocessed labels (no readable ground-truth volume)",
                                   json_author="Fabian", json_task=task, advanced=advanced_metrics, nsd_tolerance=nsd_tolerance)
+        scored = cases
         cases = [c[:4] for c in cases]
         self._validation_extra(cases, join(output_folder, "summary.json"))
-        if run_postprocessing_on_folds:
+        if run_postprocessing_on_folds and determine_postprocessing:
+            from ...postprocessing.connected_components import determine_postprocessing as search
+            print("determining postprocessing")
+            search(scored, [c for c in range(self.num_classes) if c != 0], self.output_folder, validation_folder_name,
+                   final_subf_name=validation_folder_name + "_postprocessed",
+                   writer=lambda vol, path, i: writer(vol, path, case_properties[i]))
+        elif run_postprocessing_on_folds:
             self.print_to_log_file("validate: determine_postprocessing (connected-component search, e2enet/postprocessing) is outside "
                                    "the MI355X hot path and was skipped; run it with the reference package on %s" % output_folder)
         if self.gt_niftis_folder and os.path.isdir(self.gt_niftis_folder) and self.output_folder_base:

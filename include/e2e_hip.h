@@ -559,6 +559,26 @@ int e2e_surface_distances_stats(const unsigned char* border_a, const float* dt2_
                                 const float* dt2_a, long long n, double threshold, long long rank_lo, long long rank_hi,
                                 double* out, void* ws, void* stream);
 
+/* ---- P1: connected-component post-processing of exported label volumes -------------------------------------------
+ * Replaces: remove_all_but_the_largest_connected_component (e2enet/postprocessing/connected_components.py:50-107): one
+ * scipy.ndimage.label over the whole volume per class entry and one (lmap == id).sum() per object.  volume: uint8 [D,H,W], W
+ * contiguous, edited in place.  The entry's mask is class_words[x >> 5] >> (x & 31) & 1 (class_words: 8 HOST words, a 256-bit
+ * class set; a joint region sets several bits), formed on load.  6-neighbour connectivity (scipy's default structure).
+ *   cc_ws_bytes: bytes of `ws` for a volume of that shape: 8 per voxel (32-bit parent and size arrays) plus 64 for the result
+ *     words; 0 for a shape cc_remove_all_but_largest refuses
+ *   cc_remove_all_but_largest: every mask voxel of a component whose size differs from the largest size and, when
+ *     min_valid >= 0, whose size * volume_per_voxel (fp64) is < min_valid, becomes 0; min_valid < 0: no minimum.  All components
+ *     of the largest size stay.  result (device, four 64-bit words, written by the callee): number of components, largest size
+ *     in voxels, largest removed size in voxels (0: nothing removed), give-up flag.  The flag is a backstop: non-zero means the
+ *     union-find met a link it must never meet or ran out of its V + 64 step budget; the volume is then left as it was and the
+ *     caller, who reads the words after the stream has run, must treat the call as failed.  Same bits on every run.
+ *     Refused before anything is launched: an axis < 1 (E2E_ERR_ARG), more than 2^31 - 2 voxels (E2E_ERR_UNSUPPORTED), class 0 in
+ *     the set, an empty set, a volume_per_voxel that is not positive and finite, a NaN min_valid (E2E_ERR_ARG)                  */
+long long e2e_cc_ws_bytes(int D, int H, int W);
+int e2e_cc_remove_all_but_largest(unsigned char* volume, int D, int H, int W, const unsigned* class_words,
+                                  double volume_per_voxel, double min_valid, void* ws, unsigned long long* result,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
