@@ -192,11 +192,27 @@ SIGNATURES = {
     "e2e_surface_distances_stats": (I, [P, P, P, P, LL, C.c_double, LL, LL, P, P, P]),
     "e2e_cc_ws_bytes": (LL, [I, I, I]),
     "e2e_cc_remove_all_but_largest": (I, [P, I, I, I, P, C.c_double, C.c_double, P, P, P]),
+    "e2e_pp_nonzero_ws_bytes": (LL, [I, I, I]),
+    "e2e_pp_nonzero_mask": (I, [P, I, I, I, I, P, P, P, P]),
+    "e2e_pp_bbox": (I, [P, I, I, I, I, P, P]),
+    "e2e_pp_crop": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, P]),
+    "e2e_pp_label_hist_bins": (I, []),
+    "e2e_pp_label_hist": (I, [P, LL, P, I, P]),
+    "e2e_pp_nan_to_zero": (I, [P, LL, P]),
+    "e2e_pp_minmax_ws_bytes": (LL, [I, I, I, I, I]),
+    "e2e_pp_minmax": (I, [P, P, P, I, LL, I, I, I, LL, LL, LL, I, P]),
+    "e2e_pp_pad_edge": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, P]),
+    "e2e_pp_resize_cubic": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
+    "e2e_pp_resize_seg": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, I, P]),
+    "e2e_pp_norm_ws_bytes": (LL, [I]),
+    "e2e_pp_norm_stats": (I, [P, P, P, P, P, I, LL, P]),
+    "e2e_pp_normalize": (I, [P, P, P, P, I, LL, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
               "e2e_convT_wgrad_ws_bytes", "e2e_conv133_input_ranges_ws_bytes", "e2e_in_lrelu_bwd_ws_doubles", "e2e_head1x1_wgrad_ws_bytes", "e2e_loss_ws_bytes", "e2e_aug_stats_ws_bytes",
-              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes"}
+              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
+              "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes"}
 
 
 class E2EError(RuntimeError):

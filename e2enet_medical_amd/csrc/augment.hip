@@ -26,18 +26,12 @@
 // All of them are HBM streaming kernels.  Parity: unpinned by construction (batchgenerators is absent from the image); every
 // kernel is tested, given the drawn parameters, against scipy.ndimage / numpy on the CPU (tests/test_gpu_augment.py).
 #include "e2e_common.h"
+#include "e2e_resample.h"
 
 namespace {
 
 // ---- cubic B-spline (scipy.ndimage, order 3) --------------------------------------------------------------------------------
-// weights of the four taps floor(x) - 1 .. floor(x) + 2 at offset t = x - floor(x)
-__device__ __forceinline__ void bspline3_weights(double t, double (&w)[4]) {
-  const double u = 1.0 - t;
-  w[0] = u * u * u / 6.0;
-  w[1] = (3.0 * t * t * t - 6.0 * t * t + 4.0) / 6.0;
-  w[2] = (-3.0 * t * t * t + 3.0 * t * t + 3.0 * t + 1.0) / 6.0;
-  w[3] = t * t * t / 6.0;
-}
+using e2e::rs::bspline3_weights;              // the four taps floor(x) - 1 .. floor(x) + 2 at offset t = x - floor(x)
 // tap index outside [0, n): the coefficient image continues by mirror (d c b | a b c d | c b a), period 2 n - 2
 __device__ __forceinline__ int mirror_index(int i, int n) {
   if (n <= 1) return 0;

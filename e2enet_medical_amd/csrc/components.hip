@@ -16,23 +16,18 @@
 //   remove   a mask voxel of a component with size != max, and (size * volume_per_voxel < min_valid when a minimum is given), is
 //            written as 0; every component whose size equals the maximum is kept (the reference's object_sizes[id] != maximum_size)
 //
-// Invariants.
-//   * parent[i] <= i at all times, equality exactly at roots: a link is only ever written by atomicMin with a smaller index, so every
-//     find walks strictly decreasing indices and ends.  A value read late (before another thread's link) is still an ancestor of
-//     the same component, so a find may return a former root; the atomicMin on it then returns the link and the union goes on.
-//   * A union retries only after another thread's successful atomicMin on the root it tried to link; each retry lowers the larger
-//     of the two indices.
-//   * Every find and union loop also carries a step budget of V + 64, and a find refuses a link that does not point downwards.
-//     When either trips, the thread sets the give-up word, stops looping, and the kernel runs to its end; result[3] reports it.
-//     This is a backstop for a broken invariant, never a path a valid input takes.
-//   * All atomics are integer min / max / add: every output, the volume and the result words, is the same bits on every run.
+// The union-find itself (init_runs, merge_back, find_root), its invariants and its step-budget backstop are e2e_unionfind.h,
+// shared with the hole filling of preprocess.hip; result[3] reports the give-up word.  All atomics are integer min / max /
+// add / or: every output, the volume and the result words, is the same bits on every run.
 #include "e2e_common.h"
+#include "e2e_unionfind.h"
 #include <cmath>
 
 namespace {
 
-constexpr unsigned NONE = 0xFFFFFFFFu;
-constexpr long long MAX_VOXELS = 0x7FFFFFFFll - 1;      // indices and sizes stay below NONE and inside an int
+using e2e::uf::NONE;
+using e2e::uf::MAX_VOXELS;
+using e2e::uf::find_root;
 constexpr int WS_WORDS = 16;                            // result words behind the two arrays (64 bytes)
 enum { W_ROOTS = 0, W_MAX = 1, W_REMOVED = 2, W_GIVEUP = 3 };
 
@@ -40,98 +35,17 @@ struct ClassSet { unsigned w[8]; };
 
 __device__ __forceinline__ bool in_set(const ClassSet& s, unsigned v) { return (s.w[v >> 5] >> (v & 31)) & 1u; }
 
-__device__ __forceinline__ unsigned load_parent(const unsigned* parent, unsigned i) {
-  return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of i, or NONE after setting the give-up word
-__device__ __forceinline__ unsigned find_root(const unsigned* parent, unsigned i, unsigned& budget, unsigned* words) {
-  for (;;) {
-    const unsigned p = load_parent(parent, i);
-    if (p == i) return i;
-    if (p > i || budget == 0u) {
-      atomicOr(&words[W_GIVEUP], 1u);
-      return NONE;
-    }
-    --budget;
-    i = p;
-  }
-}
-
-__device__ __forceinline__ void unite(unsigned* parent, unsigned i, unsigned j, unsigned& budget, unsigned* words) {
-  unsigned a = find_root(parent, i, budget, words), b = find_root(parent, j, budget, words);
-  while (a != NONE && b != NONE && a != b) {
-    if (a < b) {
-      const unsigned t = a;
-      a = b;
-      b = t;
-    }
-    const unsigned old = atomicMin(&parent[a], b);
-    if (old == a) return;                     // a was a root and now hangs under b
-    if (budget == 0u) {                       // (another thread linked a first: old < a)
-      atomicOr(&words[W_GIVEUP], 1u);
-      return;
-    }
-    --budget;
-    a = find_root(parent, old, budget, words);
-    b = find_root(parent, b, budget, words);
-  }
-}
-
 // parent[i] = first voxel of i's run of mask voxels along W; size[i] = 0; workgroup 0 clears the result words
 __global__ __launch_bounds__(256) void cc_init_kernel(const unsigned char* __restrict__ x, ClassSet set, unsigned* __restrict__ parent,
                                                       unsigned* __restrict__ size, unsigned* __restrict__ words, unsigned V, unsigned W) {
   if (blockIdx.x == 0 && threadIdx.x < WS_WORDS) words[threadIdx.x] = 0u;
-  const unsigned lane = threadIdx.x & 63u;
+  e2e::uf::init_runs([&](unsigned j) { return in_set(set, x[j]); }, parent, V, W);
   const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  const bool live = i64 < V;
-  const unsigned i = (unsigned)i64;
-  const unsigned base = i - lane;                              // the wave's first voxel (< V whenever any lane is live)
-  const bool m = live && in_set(set, x[i]);
-  const unsigned long long bits = __ballot(m);
-  // where the run that reaches lane 0 begins: the wave steps left through lane 0's row, 64 voxels at a time
-  unsigned start0 = base;
-  if (bits & 1ull) {
-    const unsigned row0 = base - base % W;
-    while (start0 > row0) {
-      const bool valid = start0 - row0 >= 64u - lane;          // start0 - 64 + lane >= row0
-      const bool mm = valid && in_set(set, x[start0 - 64u + lane]);
-      const unsigned long long inv = ~__ballot(mm);
-      if (inv == 0ull) {
-        start0 -= 64u;
-        continue;
-      }
-      start0 -= (unsigned)__clzll(inv);                        // mask voxels directly left of start0
-      break;
-    }
-  }
-  if (live) {
-    unsigned p = NONE;
-    if (m) {
-      const unsigned w = i % W;
-      const unsigned l0 = w >= lane ? 0u : lane - w;           // lane at which this voxel's row begins inside the wave
-      const unsigned long long below = (1ull << lane) - 1ull, row = ~((1ull << l0) - 1ull);
-      const unsigned long long gaps = ~bits & below & row;     // non-mask voxels of the row left of this one, inside the wave
-      if (gaps) p = base + 64u - (unsigned)__clzll(gaps);      // one past the nearest gap
-      else p = l0 ? base + l0 : start0;
-    }
-    parent[i] = p;
-    size[i] = 0u;
-  }
+  if (i64 < V) size[i64] = 0u;
 }
 
-// Unite with the neighbours one row and one plane back.  The union with (i - s) is implied, and skipped, when i - 1 and i - s - 1
-// are both in the mask: i ~ i - 1 and i - s ~ i - s - 1 by their runs, and i - 1 ~ i - s - 1 by the same rule one voxel to the left.
 __global__ __launch_bounds__(256) void cc_merge_kernel(unsigned* parent, unsigned* words, unsigned V, unsigned W, unsigned HW) {
-  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-  if (i64 >= V) return;
-  const unsigned i = (unsigned)i64;
-  if (parent[i] == NONE) return;                               // (NONE never changes after init)
-  unsigned budget = V + 64u;
-  const unsigned w = i % W;
-  const bool left = w > 0u && parent[i - 1u] != NONE;
-  if (i % HW >= W && parent[i - W] != NONE && !(left && parent[i - W - 1u] != NONE)) unite(parent, i, i - W, budget, words);
-  if (i >= HW && parent[i - HW] != NONE && !(left && parent[i - HW - 1u] != NONE)) unite(parent, i, i - HW, budget, words);
+  e2e::uf::merge_back(parent, &words[W_GIVEUP], V, W, HW);
 }
 
 __global__ __launch_bounds__(256) void cc_flatten_count_kernel(unsigned* parent, unsigned* size, unsigned* words, unsigned V) {
@@ -142,7 +56,7 @@ __global__ __launch_bounds__(256) void cc_flatten_count_kernel(unsigned* parent,
   unsigned root = NONE;
   if (i64 < V && parent[i] != NONE) {
     unsigned budget = V + 64u;
-    root = find_root(parent, i, budget, words);
+    root = find_root(parent, i, budget, &words[W_GIVEUP]);
     if (root != NONE) parent[i] = root;                        // (roots keep parent[r] == r; a racing reader sees an ancestor)
   }
   const bool m = root != NONE;

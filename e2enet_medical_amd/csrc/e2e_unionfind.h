@@ -1,0 +1,126 @@
+// Lock-free union-find over the voxels of a [D, H, W] volume, 6-neighbour connectivity: the labelling that components.hip
+// (connected components of a class set) and preprocess.hip (background components, for binary_fill_holes) share.  The mask is
+// a predicate on the flat voxel index, formed on load, so neither user materialises one for it.
+//
+//   init_runs   parent[i] = flat index of the first voxel of i's run of mask voxels along W (a segmented scan inside the row),
+//               NONE off the mask
+//   merge_back  every mask voxel unites with its mask neighbours at i - W and i - H W: find both roots, atomicMin(&parent[larger
+//               root], smaller root), and go on from the returned value when another thread linked that root first
+//   find_root   after merge_back has run to its end (a kernel boundary), the root of i is its component's smallest voxel
+//
+// Invariants.
+//   * parent[i] <= i at all times, equality exactly at roots: a link is only ever written by atomicMin with a smaller index, so every
+//     find walks strictly decreasing indices and ends.  A value read late (before another thread's link) is still an ancestor of
+//     the same component, so a find may return a former root; the atomicMin on it then returns the link and the union goes on.
+//   * A union retries only after another thread's successful atomicMin on the root it tried to link; each retry lowers the larger
+//     of the two indices.
+//   * Every find and union loop also carries a step budget (the callers give V + 64), and a find refuses a link that does not
+//     point downwards.  When either trips, the thread sets the give-up word, stops looping, and the kernel runs to its end; the
+//     caller reports the word as an error.  This is a backstop for a broken invariant, never a path a valid input takes, and it
+//     is never retried.
+//   * All atomics are integer min / or: the labelling is the same bits on every run.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace e2e {
+namespace uf {
+
+constexpr unsigned NONE = 0xFFFFFFFFu;
+constexpr long long MAX_VOXELS = 0x7FFFFFFFll - 1;      // indices and sizes stay below NONE and inside an int
+
+__device__ __forceinline__ unsigned load_parent(const unsigned* parent, unsigned i) {
+  return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of i, or NONE after setting the give-up word
+__device__ __forceinline__ unsigned find_root(const unsigned* parent, unsigned i, unsigned& budget, unsigned* giveup) {
+  for (;;) {
+    const unsigned p = load_parent(parent, i);
+    if (p == i) return i;
+    if (p > i || budget == 0u) {
+      atomicOr(giveup, 1u);
+      return NONE;
+    }
+    --budget;
+    i = p;
+  }
+}
+
+__device__ __forceinline__ void unite(unsigned* parent, unsigned i, unsigned j, unsigned& budget, unsigned* giveup) {
+  unsigned a = find_root(parent, i, budget, giveup), b = find_root(parent, j, budget, giveup);
+  while (a != NONE && b != NONE && a != b) {
+    if (a < b) {
+      const unsigned t = a;
+      a = b;
+      b = t;
+    }
+    const unsigned old = atomicMin(&parent[a], b);
+    if (old == a) return;                     // a was a root and now hangs under b
+    if (budget == 0u) {                       // (another thread linked a first: old < a)
+      atomicOr(giveup, 1u);
+      return;
+    }
+    --budget;
+    a = find_root(parent, old, budget, giveup);
+    b = find_root(parent, b, budget, giveup);
+  }
+}
+
+// parent[i] = first voxel of i's run of mask voxels along W, for the voxel i = blockIdx.x * 256 + threadIdx.x of a 256-thread
+// block.  Every thread of the block calls it (it votes across the wave); in_mask(j) is asked only for j < V.
+template <class Pred>
+__device__ __forceinline__ void init_runs(Pred in_mask, unsigned* __restrict__ parent, unsigned V, unsigned W) {
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  const bool live = i64 < V;
+  const unsigned i = (unsigned)i64;
+  const unsigned base = i - lane;                              // the wave's first voxel (< V whenever any lane is live)
+  const bool m = live && in_mask(i);
+  const unsigned long long bits = __ballot(m);
+  // where the run that reaches lane 0 begins: the wave steps left through lane 0's row, 64 voxels at a time
+  unsigned start0 = base;
+  if (bits & 1ull) {
+    const unsigned row0 = base - base % W;
+    while (start0 > row0) {
+      const bool valid = start0 - row0 >= 64u - lane;          // start0 - 64 + lane >= row0
+      const bool mm = valid && in_mask(start0 - 64u + lane);
+      const unsigned long long inv = ~__ballot(mm);
+      if (inv == 0ull) {
+        start0 -= 64u;
+        continue;
+      }
+      start0 -= (unsigned)__clzll(inv);                        // mask voxels directly left of start0
+      break;
+    }
+  }
+  if (live) {
+    unsigned p = NONE;
+    if (m) {
+      const unsigned w = i % W;
+      const unsigned l0 = w >= lane ? 0u : lane - w;           // lane at which this voxel's row begins inside the wave
+      const unsigned long long below = (1ull << lane) - 1ull, row = ~((1ull << l0) - 1ull);
+      const unsigned long long gaps = ~bits & below & row;     // non-mask voxels of the row left of this one, inside the wave
+      if (gaps) p = base + 64u - (unsigned)__clzll(gaps);      // one past the nearest gap
+      else p = l0 ? base + l0 : start0;
+    }
+    parent[i] = p;
+  }
+}
+
+// Unite voxel i = blockIdx.x * 256 + threadIdx.x with the neighbours one row and one plane back.  The union with (i - s) is
+// implied, and skipped, when i - 1 and i - s - 1 are both in the mask: i ~ i - 1 and i - s ~ i - s - 1 by their runs, and
+// i - 1 ~ i - s - 1 by the same rule one voxel to the left.
+__device__ __forceinline__ void merge_back(unsigned* parent, unsigned* giveup, unsigned V, unsigned W, unsigned HW) {
+  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  if (i64 >= V) return;
+  const unsigned i = (unsigned)i64;
+  if (parent[i] == NONE) return;                               // (NONE never changes after init)
+  unsigned budget = V + 64u;
+  const unsigned w = i % W;
+  const bool left = w > 0u && parent[i - 1u] != NONE;
+  if (i % HW >= W && parent[i - W] != NONE && !(left && parent[i - W - 1u] != NONE)) unite(parent, i, i - W, budget, giveup);
+  if (i >= HW && parent[i - HW] != NONE && !(left && parent[i - HW - 1u] != NONE)) unite(parent, i, i - HW, budget, giveup);
+}
+
+}  // namespace uf
+}  // namespace e2e

@@ -3,6 +3,7 @@
 // result *= gaussian) and _internal_predict_3D_3Dconv_tiled (neural_network.py:383-407: overlap-add, count map,
 // divide, argmax).  The reference moves every tile to the host and adds in numpy; here everything stays in HBM.
 #include "e2e_common.h"
+#include "e2e_resample.h"
 
 namespace {
 
@@ -168,21 +169,8 @@ __global__ __launch_bounds__(256) void export_argmax_kernel(const float* __restr
 // fraction, weights (1 - t, t), the 2^n taps visited last axis fastest, coefficient multiplied by the axis weights in axis
 // order and added to a double sum (this file is built with -ffp-contract=off), result cast to float32.
 // lowres < 0: trilinear over all three axes; lowres = 0..2: nearest along that axis, bilinear in the plane.
-__device__ __forceinline__ void lin_coord(int o, int n_in, int n_out, int& i0, int& i1, double& t) {
-  double c = ((double)o + 0.5) * ((double)n_in / (double)n_out) - 0.5;
-  if (c < 0.0) c = 0.0;
-  if (c > (double)(n_in - 1)) c = (double)(n_in - 1);
-  const double f = floor(c);
-  i0 = (int)f;
-  t = c - f;
-  i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
-}
-__device__ __forceinline__ int near_coord(int o, int n_in, int n_out) {
-  double c = ((double)n_in / (double)n_out) * ((double)o + 0.5) - 0.5;
-  if (c < 0.0) c = 0.0;
-  if (c > (double)(n_in - 1)) c = (double)(n_in - 1);
-  return (int)floor(c + 0.5);
-}
+using e2e::rs::lin_coord;
+using e2e::rs::near_coord;
 __global__ __launch_bounds__(256) void resample_linear_kernel(const float* __restrict__ src, float* __restrict__ dst, int K,
                                                               long long kstride, int A, int B, int C, long long sa,
                                                               long long sb, long long sc, int OA, int OB, int OC, int lowres) {

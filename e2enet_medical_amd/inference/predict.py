@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .._lib import lib
+from ..preprocessing.preprocessing import RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD, get_do_separate_z, get_lowres_axis  # noqa: F401
 
 
 def _stream():
@@ -54,19 +55,6 @@ def predict_case_ensemble(trainer, params: Sequence[dict], data: np.ndarray, do_
     finally:
         net.keep_on_device = keep
     return total
-
-
-RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD = 3        # reference e2enet/configuration.py
-
-
-def get_do_separate_z(spacing, anisotropy_threshold=RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD):
-    """reference preprocessing.py:28-30"""
-    return (np.max(spacing) / np.min(spacing)) > anisotropy_threshold
-
-
-def get_lowres_axis(new_spacing):
-    """reference preprocessing.py:33-35"""
-    return np.where(max(new_spacing) / np.array(new_spacing) == 1)[0]
 
 
 def resample_plan(properties_dict: dict, force_separate_z: Optional[bool] = None):
@@ -192,8 +180,8 @@ def check_input_folder_and_return_caseIDs(input_folder: str, expected_num_modali
     """Case identifiers of an input folder.  Two layouts are served:
       * PREPROCESSED cases (what the reference's GenericPreprocessor writes): ``<case>.npz`` (or ``<case>.npy``) holding
         [modalities (+ seg), X, Y, Z] plus ``<case>.pkl`` with the properties dict -- returned as (ids, "preprocessed");
-      * the reference's raw layout ``<case>_XXXX.nii.gz`` (predict.py:631-672) -- returned as (ids, "nifti"); predicting from it
-        needs the reference's preprocessing package (crop, resample, normalise: SimpleITK / scikit-image), outside this engine."""
+      * the reference's raw layout ``<case>_XXXX.nii.gz`` (predict.py:631-672) -- returned as (ids, "nifti"); these cases are
+        read by a ``reader`` callback and preprocessed on the device (``trainer.preprocess_patient``)."""
     files = sorted(os.listdir(input_folder))
     nii = [f for f in files if f.endswith(".nii.gz")]
     if nii:
@@ -216,13 +204,15 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
                         mixed_precision: bool = True, overwrite_existing: bool = True, mode: str = 'normal',
                         overwrite_all_in_gpu: bool = None, step_size: float = 0.5,
                         checkpoint_name: str = "model_final_checkpoint", segmentation_export_kwargs: dict = None,
-                        disable_postprocessing: bool = False, writer=None):
+                        disable_postprocessing: bool = False, writer=None, reader=None):
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.
     The per-case work is ``predict_cases`` above (softmax resident in HBM).  ``num_threads_*`` are accepted and unused: there are
     no preprocessing / export worker processes here.  Unless ``disable_postprocessing``, ``<model>/postprocessing.json`` is copied to
     ``output_folder`` and applied to every case on the device (reference :337-356); when the file is missing the reference's warning
-    is printed and the raw label maps are written."""
+    is printed and the raw label maps are written.  A folder of raw cases (``<case>_XXXX.nii.gz``) is read through
+    ``reader(list_of_files) -> (data [C, X, Y, Z], properties)`` -- default: the reference's SimpleITK loader -- and preprocessed on
+    the device by ``trainer.preprocess_patient``; without a reader such a folder is refused before anything is loaded."""
     import shutil
     from ..training.model_restore import load_model_and_checkpoint_files
     if mode != "normal":
@@ -236,10 +226,8 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
         expected_num_modalities = pickle.load(f)['num_modalities']
     case_ids, layout = check_input_folder_and_return_caseIDs(input_folder, expected_num_modalities)
     if layout == "nifti":
-        raise NotImplementedError(
-            "%s holds raw NIfTI cases (<case>_XXXX.nii.gz): cropping / resampling / normalisation is the reference's preprocessing "
-            "package (e2enet/preprocessing, SimpleITK + scikit-image; SURVEY.md section 2 row 11, out of scope).  Preprocess the "
-            "folder with it and point -i at the resulting <case>.npz + <case>.pkl files" % input_folder)
+        from ..preprocessing.cropping import require_reader
+        reader = require_reader(reader, "predict_from_folder(%s: raw cases, <case>_XXXX.nii.gz)" % input_folder)
     case_ids = case_ids[part_id::num_parts]
     output_files = [os.path.join(output_folder, c + ".nii.gz") for c in case_ids]
     if not overwrite_existing:
@@ -265,6 +253,11 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
 
     def cases():
         for c, out in zip(case_ids, output_files):
+            if layout == "nifti":
+                files = [os.path.join(input_folder, c + "_%04.0d.nii.gz" % n) for n in range(expected_num_modalities)]
+                d, _, props = trainer.preprocess_patient(files, reader=reader)
+                yield out, (d, props)
+                continue
             npy, npz = os.path.join(input_folder, c + ".npy"), os.path.join(input_folder, c + ".npz")
             d = np.load(npy) if os.path.isfile(npy) else np.load(npz)['data']
             with open(os.path.join(input_folder, c + ".pkl"), 'rb') as f:

@@ -1,8 +1,8 @@
 """``python -m e2enet_medical_amd.simple_predict`` -- the reference's inference entry point (simple_predict.py:25-228) on the MI355X
 engine: the same argv; the checkpoint name is prefixed with ``--Tconv`` (:152) and ``predict_from_folder`` runs the cases
 ``[part_id::num_parts]`` (one process per GPU; within a process ``SegmentationNetwork.shard_tiles`` can split the tiles of a case
-over a process group instead).  The input folder holds PREPROCESSED cases (``<case>.npz|.npy`` + ``<case>.pkl``): raw NIfTI needs
-the reference's preprocessing package (``inference.predict.predict_from_folder`` says so)."""
+over a process group instead).  The input folder holds preprocessed cases (``<case>.npz|.npy`` + ``<case>.pkl``) or raw cases
+(``<case>_XXXX.nii.gz``); raw cases are read by a ``reader`` callback (default: SimpleITK) and preprocessed on the device."""
 import argparse
 import os
 
@@ -43,7 +43,8 @@ def build_parser():
     return parser
 
 
-def main(argv=None):
+def main(argv=None, reader=None, writer=None):
+    """``reader`` / ``writer``: handed to ``predict_from_folder`` unchanged (None: its SimpleITK defaults)"""
     args = build_parser().parse_args(argv)
     folds, lowres_segmentations, all_in_gpu, model = args.folds, args.lowres_segmentations, args.all_in_gpu, args.model
     task_name = args.task_name
@@ -71,7 +72,7 @@ def main(argv=None):
                                args.num_threads_preprocessing, args.num_threads_nifti_save, lowres_segmentations, args.part_id,
                                args.num_parts, not args.disable_tta, overwrite_existing=args.overwrite_existing, mode=args.mode,
                                overwrite_all_in_gpu=all_in_gpu, mixed_precision=not args.disable_mixed_precision,
-                               step_size=args.step_size, checkpoint_name=args.chk)
+                               step_size=args.step_size, checkpoint_name=args.chk, writer=writer, reader=reader)
 
 
 if __name__ == "__main__":

@@ -1033,9 +1033,25 @@ class nnUNetTrainer_simple(object):
         return scores
 
     # ------------------------------------------------------------------------------------------ out of scope
-    def preprocess_patient(self, input_files):
-        """reference :425-452"""
-        _out_of_scope("preprocess_patient()", "preprocessing package (e2enet/preprocessing: crop, resample, normalise)")
+    def preprocess_patient(self, input_files, reader=None):
+        """reference :425-452 on the device (e2enet_medical_amd/preprocessing): crop to the non-zero region, resample to the stage's
+        ``current_spacing``, normalise.  ``input_files``: a list of file paths, read through ``reader(list_of_files) -> (data,
+        properties)`` (default: the reference's SimpleITK loader), or an in-memory case ``(data [C, X, Y, Z], properties)``.  The
+        plans' ``preprocessor_name`` may name GenericPreprocessor (the default) or GenericPreprocessor_linearResampling."""
+        from ... import preprocessing
+        if not (isinstance(input_files, tuple) and len(input_files) == 2 and isinstance(input_files[1], dict)):
+            reader = preprocessing.cropping.require_reader(reader, "preprocess_patient()")      # (before anything is computed)
+        preprocessor_name = self.plans.get('preprocessor_name')
+        if preprocessor_name is None:
+            preprocessor_name = "GenericPreprocessor"
+        if not self.threeD or preprocessor_name not in ("GenericPreprocessor", "GenericPreprocessor_linearResampling"):
+            raise NotImplementedError("preprocessor %r: the device preprocessing implements GenericPreprocessor and "
+                                      "GenericPreprocessor_linearResampling on 3-D plans" % (preprocessor_name,))
+        print("using preprocessor", preprocessor_name)
+        preprocessor = getattr(preprocessing, preprocessor_name)(self.normalization_schemes, self.use_mask_for_norm,
+                                                                 self.transpose_forward, self.intensity_properties)
+        return preprocessor.preprocess_test_case(input_files, self.plans['plans_per_stage'][self.stage]['current_spacing'],
+                                                 reader=reader)
 
     def preprocess_predict_nifti(self, *args, **kwargs):
         """reference :454-489"""

@@ -579,6 +579,62 @@ int e2e_cc_remove_all_but_largest(unsigned char* volume, int D, int H, int W, co
                                   double volume_per_voxel, double min_valid, void* ws, unsigned long long* result,
                                   void* stream);
 
+/* ---- P2: preprocessing of a raw case (crop to non-zero, resample, normalise) ----------------------------------------
+ * Replaces: e2enet/preprocessing/cropping.py (create_nonzero_mask, get_bbox_from_mask, crop_to_nonzero) and
+ * e2enet/preprocessing/preprocessing.py (resample_data_or_seg, GenericPreprocessor.resample_and_normalize).  Volumes are fp32,
+ * masks uint8; "strided" sources give a channel stride and one element stride per axis (a transposed view needs no copy), every
+ * destination is contiguous.  lowres_axis: -1, or the axis (0..2) that is resampled with order 0 while the planes across it are
+ * resampled in 2-D (the reference's do_separate_z).
+ *   pp_nonzero_mask: mask[D,H,W] = OR over the C contiguous modalities of x != 0 (NaN counts as non-zero), then
+ *     scipy.ndimage.binary_fill_holes (6 neighbours): every background component without a voxel on a face of the volume
+ *     becomes mask.  ws: pp_nonzero_ws_bytes bytes (5 per voxel; 0: shape refused).  result (device, 8 words): word 6 is the
+ *     union-find's give-up flag (see cc_remove_all_but_largest): non-zero means the call failed; it is never retried.
+ *   pp_bbox: result[0..5] = lo, hi of axis 0, 1, 2 with hi exclusive, over the voxels mask != outside_value; result[7] = their
+ *     number (0: the box words are meaningless).  Integer atomics only.
+ *   pp_crop: out_data[C,d,h,w] = data[:, z0:z0+d, y0:y0+h, x0:x0+w]; out_seg[S,d,h,w] = the cropped seg with nonzero_label
+ *     where seg == 0 and the mask is off; seg == NULL: out_seg[1,d,h,w] = nonzero_label off the mask, 0 on it.
+ *   pp_label_hist: hist[v + 256] += 1 for whole-number labels v in [-256, 255], hist[512] += 1 for anything else (hist: 513
+ *     words, zeroed by the caller); fix_below != 0 additionally writes seg[seg < -1] = 0.
+ *   pp_nan_to_zero: x[isnan(x)] = 0 in place.
+ *   pp_minmax: dst[2 g], dst[2 g + 1] = min, max of group g = modality k (lowres_axis < 0) or k * n[lowres_axis] + slice.
+ *     ws: pp_minmax_ws_bytes bytes.
+ *   pp_pad_edge: dst[K, A + 2 pa, B + 2 pb, C + 2 pc] = src continued by its edge values (np.pad mode 'edge').
+ *   pp_resize_cubic: src = the B-spline coefficients of the volume padded by `pad` on every axis but lowres_axis
+ *     (pp_pad_edge, then aug_bspline_prefilter_axis on those axes); dst[K,OA,OB,OC] = the cubic spline at
+ *     (o + 0.5) * in / out - 0.5 + pad, which is scipy.ndimage.zoom(order=3, mode='nearest', grid_mode=True) for pad = 12,
+ *     clipped to the group's range in minmax (pp_minmax of the same lowres_axis); along lowres_axis the plane
+ *     floor(c + 0.5) of the clamped coordinate.
+ *   pp_resize_seg: per voxel the largest label whose binary mask, resampled like resample_linear does (order 1, order 0 along
+ *     lowres_axis), is >= 0.5, else 0; a result < -1 is written as 0.
+ *   pp_norm_stats: stats[4 c ..] = (voxels counted, mean, std with ddof 0) of channel c for the schemes that need them:
+ *     prm[8 c ..] = (scheme: 0 default, 1 CT, 2 CT2, 3 noNorm; lower bound; upper bound; mean; sd; use_nonzero_mask; 0; 0).
+ *     Scheme 0 counts seg >= 0 when use_nonzero_mask is set and every voxel otherwise, scheme 2 counts lb < x < ub.  Two passes,
+ *     fp64 per-block records folded in a fixed order: the same bits on every run.  ws: pp_norm_ws_bytes bytes.
+ *   pp_normalize: in place.  0: (x - mean) / (std + 1e-8); 1: (clip(x, lb, ub) - prm mean) / prm sd; 2: (clip(x, lb, ub) - mean) /
+ *     std; 3: untouched.  With use_nonzero_mask, voxels with seg < 0 become 0 (schemes 0..2).  seg: one channel [vol] or NULL. */
+long long e2e_pp_nonzero_ws_bytes(int D, int H, int W);
+int e2e_pp_nonzero_mask(const float* data, int C, int D, int H, int W, unsigned char* mask, void* ws, unsigned* result,
+                        void* stream);
+int e2e_pp_bbox(const unsigned char* mask, int outside_value, int D, int H, int W, unsigned* result, void* stream);
+int e2e_pp_crop(const float* data, const float* seg, const unsigned char* mask, float* out_data, float* out_seg, int C, int S,
+                int D, int H, int W, int z0, int y0, int x0, int d, int h, int w, float nonzero_label, void* stream);
+int e2e_pp_label_hist_bins(void);
+int e2e_pp_label_hist(float* seg, long long n, unsigned* hist, int fix_below, void* stream);
+int e2e_pp_nan_to_zero(float* x, long long n, void* stream);
+long long e2e_pp_minmax_ws_bytes(int K, int A, int B, int C, int lowres_axis);
+int e2e_pp_minmax(const float* src, double* dst, void* ws, int K, long long kstride, int A, int B, int C, long long sa,
+                  long long sb, long long sc, int lowres_axis, void* stream);
+int e2e_pp_pad_edge(const float* src, float* dst, int K, long long kstride, int A, int B, int C, long long sa, long long sb,
+                    long long sc, int pa, int pb, int pc, void* stream);
+int e2e_pp_resize_cubic(const float* src, float* dst, const double* minmax, int K, int A, int B, int C, int OA, int OB, int OC,
+                        int pad, int lowres_axis, void* stream);
+int e2e_pp_resize_seg(const float* src, float* dst, int K, long long kstride, int A, int B, int C, long long sa, long long sb,
+                      long long sc, int OA, int OB, int OC, int lowres_axis, void* stream);
+long long e2e_pp_norm_ws_bytes(int C);
+int e2e_pp_norm_stats(const float* x, const float* seg, const double* prm, double* stats, void* ws, int C, long long vol,
+                      void* stream);
+int e2e_pp_normalize(float* x, const float* seg, const double* prm, const double* stats, int C, long long vol, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
