@@ -1,22 +1,35 @@
-"""The reference's e2enet/preprocessing/preprocessing.py (GenericPreprocessor) on the device (csrc/preprocess.hip), in memory.
+"""The reference's e2enet/preprocessing/preprocessing.py (GenericPreprocessor) on the device (csrc/preprocess.hip, class_select.hip):
+a case in memory, or a cropped training folder into the stage folders the trainer reads.
 
   get_do_separate_z, get_lowres_axis, resample_patient, resample_data_or_seg   :28-202, same names, arguments and return values
-  GenericPreprocessor (resample_and_normalize, preprocess_test_case)          :205-329
+  GenericPreprocessor (load_cropped, resample_and_normalize, preprocess_test_case, _run_internal, run)   :205-407
   GenericPreprocessor_linearResampling                                         :410-415
+  class_locations                                                              :343-361, the sampling inside _run_internal
+  run_preprocessing                     experiment_planning/experiment_planner_baseline_3DUNet.py:425-445, from a plans dict or file
 
 The data is resized like ``skimage.transform.resize(order=3, mode='edge', anti_aliasing=False, clip=True)`` (scikit-image >= 0.19:
 ``scipy.ndimage.zoom(order=3, mode='nearest', grid_mode=True)`` clipped to the input's range), the segmentation like
 batchgenerators' ``resize_segmentation(order=1)``; with a separate low-resolution axis every slice across it is resized in 2-D and the
 axis itself with order 0.  These are the reference's defaults; its other orders raise NotImplementedError, except ``order_data=1``
-(GenericPreprocessor_linearResampling), which is ``e2e_resample_linear``.  ``GenericPreprocessor.run`` over a training folder, the 2-D
-preprocessor and the custom preprocessors are not part of this package."""
+(GenericPreprocessor_linearResampling), which is ``e2e_resample_linear``.  The 2-D preprocessor and the custom preprocessors are not
+part of this package."""
+import os
+import pickle
+import shutil
+import zipfile
+from collections import deque
+
 import numpy as np
 
+from .class_sampling import MIN_PERCENT_COVERAGE, NUM_SAMPLES, SEED, draw_ranks, sort_ranks
 from .cropping import ImageCropper, _stream, label_values, load_case, to_device
 
 RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD = 3        # reference e2enet/configuration.py
 SPLINE_PAD = 12                                  # scipy's pre-padding for mode 'nearest' in front of the spline prefilter
 SCHEMES = {"CT": 1, "CT2": 2, "noNorm": 3}       # every other name is the default scheme (0)
+DEFAULT_NUM_THREADS = 8                          # reference e2enet/configuration.py
+MAX_WRITER_THREADS = 16                          # host threads that compress and write finished cases (never sized from the machine)
+BUILT_PREPROCESSORS = ("GenericPreprocessor", "GenericPreprocessor_linearResampling")
 
 
 def get_do_separate_z(spacing, anisotropy_threshold=RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD):
@@ -146,8 +159,80 @@ def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separat
     return out.cpu().numpy().astype(data.dtype) if was_numpy else out
 
 
+def class_locations(seg, all_classes, num_samples=NUM_SAMPLES, min_percent_coverage=MIN_PERCENT_COVERAGE, seed=SEED):
+    """Reference :343-361: ``{c: np.argwhere(seg == c)[RandomState(seed).choice(n, t, replace=False)]}`` over ``all_classes`` in
+    order (int64 ``[t, 3]``; ``[]`` for a class without a voxel, which draws nothing), one RandomState for all of them.  ``seg``: a
+    label volume [X, Y, Z], a device tensor (it stays there) or a numpy array (uploaded once).  The device counts the classes
+    (e2e_pp_select_count), the host draws the ranks with the reference's numpy calls (class_sampling.draw_ranks), the device turns
+    them into coordinates (e2e_pp_select_coords): ``argwhere`` is never materialised."""
+    import torch
+    from .._lib import lib, E2EError
+    L = lib()
+    assert len(seg.shape) == 3, "seg must be (x, y, z)"
+    s, _ = to_device(seg)
+    all_classes = list(all_classes)
+    shape = [int(v) for v in s.shape]
+    n = int(s.numel())
+    if n == 0 or not all_classes:
+        return {c: [] for c in all_classes}
+    kmax = L.pp_select_max_classes()
+    groups = [all_classes[g:g + kmax] for g in range(0, len(all_classes), kmax)]
+    st = _stream()
+    counted = []
+    for grp in groups:                               # one read of the volume per kmax classes
+        cls = np.ascontiguousarray(grp, dtype=np.float32)
+        nbytes = L.pp_select_ws_bytes(n, len(grp))
+        if nbytes <= 0:
+            raise E2EError("pp_select_ws_bytes: a volume of %d voxels is not supported" % n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        counts = torch.empty(len(grp), dtype=torch.int64, device=s.device)
+        L.pp_select_count(s.data_ptr(), n, cls.ctypes.data, len(grp), counts.data_ptr(), ws.data_ptr(), st)
+        counted.append((cls, ws, counts))
+    totals = torch.cat([c[2] for c in counted]).cpu().numpy()
+    drawn = draw_ranks(totals, num_samples, min_percent_coverage, seed)
+    locs, pos = {}, 0
+    for grp, (cls, ws, _) in zip(groups, counted):
+        pairs = [sort_ranks(r) for r in drawn[pos:pos + len(grp)]]
+        pos += len(grp)
+        class_offsets = np.zeros(len(grp) + 1, dtype=np.int64)
+        class_offsets[1:] = np.cumsum([len(p[0]) for p in pairs])
+        rows = None
+        if class_offsets[-1]:
+            ranks = torch.from_numpy(np.concatenate([p[0] for p in pairs])).to(s.device)
+            slots = torch.from_numpy(np.concatenate([p[1] for p in pairs])).to(s.device)
+            out = torch.empty((int(class_offsets[-1]), 3), dtype=torch.int64, device=s.device)
+            L.pp_select_coords(s.data_ptr(), shape[0], shape[1], shape[2], cls.ctypes.data, len(grp), ranks.data_ptr(), slots.data_ptr(),
+                               class_offsets.ctypes.data, out.data_ptr(), ws.data_ptr(), st)
+            rows = out.cpu().numpy()
+        for i, c in enumerate(grp):
+            a, b = int(class_offsets[i]), int(class_offsets[i + 1])
+            locs[c] = rows[a:b].copy() if b > a else []
+    return locs
+
+
+def save_npz(path, data):
+    """``np.savez_compressed(path, data=data)`` with a fixed time stamp on the archive member: the file's bytes depend on the array
+    alone, not on when or by which thread it was written"""
+    info = zipfile.ZipInfo("data.npy", date_time=(1980, 1, 1, 0, 0, 0))
+    info.compress_type = zipfile.ZIP_DEFLATED
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, allowZip64=True) as z:
+        with z.open(info, "w", force_zip64=True) as f:
+            np.lib.format.write_array(f, np.asanyarray(data), allow_pickle=False)
+
+
+def preprocessor_class(preprocessor_name, three_d=True):
+    """The class the plans' ``preprocessor_name`` names (None: GenericPreprocessor); NotImplementedError for anything but the two
+    built classes, or for 2-D plans"""
+    if preprocessor_name is None:
+        preprocessor_name = "GenericPreprocessor"
+    if not three_d or preprocessor_name not in BUILT_PREPROCESSORS:
+        raise NotImplementedError("preprocessor %r: the device preprocessing implements GenericPreprocessor and "
+                                  "GenericPreprocessor_linearResampling on 3-D plans" % (preprocessor_name,))
+    return globals()[preprocessor_name]
+
+
 class GenericPreprocessor(object):
-    """Reference :205-329 without ``run`` (preprocessing a training folder stays with the reference package)"""
+    """Reference :205-407"""
 
     def __init__(self, normalization_scheme_per_modality, use_nonzero_mask, transpose_forward, intensityproperties=None):
         self.transpose_forward = transpose_forward
@@ -176,6 +261,16 @@ class GenericPreprocessor(object):
                     raise ValueError("use_nonzero_mask[%d] is set but there is no seg to take the mask from" % c)
                 prm[c, 5] = 1.0
         return prm
+
+    @staticmethod
+    def load_cropped(cropped_output_dir, case_identifier):
+        """Reference :223-229"""
+        all_data = np.load(os.path.join(cropped_output_dir, "%s.npz" % case_identifier))['data']
+        data = all_data[:-1].astype(np.float32)
+        seg = all_data[-1:]
+        with open(os.path.join(cropped_output_dir, "%s.pkl" % case_identifier), 'rb') as f:
+            properties = pickle.load(f)
+        return data, seg, properties
 
     def resample_and_normalize(self, data, target_spacing, properties, seg=None, force_separate_z=None):
         """Reference :231-319.  ``data`` [C, X, Y, Z] and ``seg`` [S, X, Y, Z] are already transposed by ``transpose_forward``,
@@ -241,6 +336,102 @@ class GenericPreprocessor(object):
                                                             force_separate_z=force_separate_z)
         seg = seg.cpu().numpy()
         return data.cpu().numpy().astype(np.float32), (seg.astype(int) if made_up_seg else seg), properties
+
+
+    def _preprocess_cropped(self, target_spacing, case_identifier, cropped_output_dir, force_separate_z, all_classes):
+        """the device half of _run_internal (:333-361): ``(vstack((data, seg)) as fp32 numpy, properties with class_locations)``"""
+        import torch
+        data, seg, properties = self.load_cropped(cropped_output_dir, case_identifier)
+        perm = (0, *[i + 1 for i in self.transpose_forward])
+        data, seg = to_device(data)[0].permute(perm), to_device(seg)[0].permute(perm)
+        data, seg, properties = self.resample_and_normalize(data, target_spacing, properties, seg, force_separate_z)
+        properties['class_locations'] = class_locations(seg[-1], all_classes)
+        for c, locs in properties['class_locations'].items():
+            if len(locs):
+                print(c, len(locs))
+        return torch.cat((data, seg)).cpu().numpy(), properties
+
+    @staticmethod
+    def _write_case(all_data, properties, output_folder_stage, case_identifier, unpack_npy=False):
+        """the host half of _run_internal (:363-367): ``<case>.npz`` (key ``data``), ``<case>.pkl``; ``unpack_npy`` also writes the
+        ``<case>.npy`` that DataLoader3D memory-maps (the reference's unpack_dataset).  Touches no device."""
+        print("saving: ", os.path.join(output_folder_stage, "%s.npz" % case_identifier))
+        save_npz(os.path.join(output_folder_stage, "%s.npz" % case_identifier), all_data)
+        if unpack_npy:
+            np.save(os.path.join(output_folder_stage, "%s.npy" % case_identifier), all_data)
+        with open(os.path.join(output_folder_stage, "%s.pkl" % case_identifier), 'wb') as f:
+            pickle.dump(properties, f)
+
+    def _run_internal(self, target_spacing, case_identifier, output_folder_stage, cropped_output_dir, force_separate_z, all_classes,
+                      unpack_npy=False):
+        """Reference :331-367"""
+        all_data, properties = self._preprocess_cropped(target_spacing, case_identifier, cropped_output_dir, force_separate_z,
+                                                        all_classes)
+        self._write_case(all_data, properties, output_folder_stage, case_identifier, unpack_npy)
+
+    def run(self, target_spacings, input_folder_with_cropped_npz, output_folder, data_identifier, num_threads=DEFAULT_NUM_THREADS,
+            force_separate_z=None, unpack_npy=False):
+        """Reference :369-407: every ``<case>.npz`` + ``<case>.pkl`` of a cropped folder into ``<output_folder>/<data_identifier>_stage<i>``
+        for each target spacing.  This process owns the GPU and walks the cases; ``num_threads`` (one number, or one per stage; at most
+        16) host threads compress and write finished cases while the device works on the next ones.  The files do not depend on it."""
+        from concurrent.futures import ThreadPoolExecutor
+        print("Initializing to run preprocessing")
+        print("npz folder:", input_folder_with_cropped_npz)
+        print("output_folder:", output_folder)
+        cases = sorted(f[:-4] for f in os.listdir(input_folder_with_cropped_npz) if f.endswith(".npz"))
+        os.makedirs(output_folder, exist_ok=True)
+        num_stages = len(target_spacings)
+        if not isinstance(num_threads, (list, tuple, np.ndarray)):
+            num_threads = [num_threads] * num_stages
+        assert len(num_threads) == num_stages
+        # the classes of the dataset, so that every case records where they are: the loader's foreground oversampling needs it
+        with open(os.path.join(input_folder_with_cropped_npz, 'dataset_properties.pkl'), 'rb') as f:
+            all_classes = pickle.load(f)['all_classes']
+        for i in range(num_stages):
+            output_folder_stage = os.path.join(output_folder, data_identifier + "_stage%d" % i)
+            os.makedirs(output_folder_stage, exist_ok=True)
+            workers = max(1, min(int(num_threads[i]), MAX_WRITER_THREADS))
+            with ThreadPoolExecutor(max_workers=workers) as pool:
+                pending = deque()
+                for case_identifier in cases:
+                    done = self._preprocess_cropped(target_spacings[i], case_identifier, input_folder_with_cropped_npz,
+                                                    force_separate_z, all_classes)
+                    while len(pending) >= workers:           # bounds the finished cases held in host memory
+                        pending.popleft().result()
+                    pending.append(pool.submit(self._write_case, *done, output_folder_stage, case_identifier, unpack_npy))
+                while pending:
+                    pending.popleft().result()
+
+
+def run_preprocessing(plans, folder_with_cropped_data, preprocessed_output_folder, num_threads=DEFAULT_NUM_THREADS, unpack_npy=False):
+    """ExperimentPlanner.run_preprocessing (experiment_planner_baseline_3DUNet.py:425-445) from a plans dict or plans file: copies
+    ``gt_segmentations`` when the cropped folder has one, then runs the plans' preprocessor over every stage's ``current_spacing``
+    into ``<preprocessed_output_folder>/<data_identifier>_stage<i>``.  Plans that name another preprocessor than the two built
+    classes, or 2-D plans, raise NotImplementedError before any file is touched."""
+    if not isinstance(plans, dict):
+        with open(plans, 'rb') as f:
+            plans = pickle.load(f)
+    stages = plans['plans_per_stage']
+    three_d = all(len(stage['patch_size']) == 3 for stage in stages.values())
+    cls = preprocessor_class(plans.get('preprocessor_name'), three_d)
+    gt = os.path.join(folder_with_cropped_data, "gt_segmentations")
+    if os.path.isdir(gt):
+        gt_out = os.path.join(preprocessed_output_folder, "gt_segmentations")
+        if os.path.isdir(gt_out):
+            shutil.rmtree(gt_out)
+        shutil.copytree(gt, gt_out)
+    dataset_properties = plans.get('dataset_properties')
+    intensityproperties = dataset_properties.get('intensityproperties') if isinstance(dataset_properties, dict) else None
+    preprocessor = cls(plans['normalization_schemes'], plans['use_mask_for_norm'], plans.get('transpose_forward', [0, 1, 2]),
+                       intensityproperties)
+    target_spacings = [stage["current_spacing"] for stage in stages.values()]
+    if len(stages) > 1 and not isinstance(num_threads, (list, tuple)):
+        num_threads = (DEFAULT_NUM_THREADS, num_threads)
+    elif len(stages) == 1 and isinstance(num_threads, (list, tuple)):
+        num_threads = num_threads[-1]
+    from ..paths import default_data_identifier
+    preprocessor.run(target_spacings, folder_with_cropped_data, preprocessed_output_folder,
+                     plans.get('data_identifier', default_data_identifier), num_threads, unpack_npy=unpack_npy)
 
 
 class GenericPreprocessor_linearResampling(GenericPreprocessor):

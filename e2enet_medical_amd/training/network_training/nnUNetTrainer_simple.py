@@ -283,7 +283,7 @@ class nnUNetTrainer_simple(object):
                 else:
                     raise FileNotFoundError(
                         "no preprocessed data under %r (dataset_directory / plans['data_identifier'] + '_stage%s', reference "
-                        "nnUNetTrainer_simple.py:216-217): preprocess the task with the reference package, hand the trainer its own "
+                        "nnUNetTrainer_simple.py:216-217): preprocess the task (python -m e2enet_medical_amd.preprocess_dataset), hand the trainer its own "
                         "tr_gen / val_gen before initialize(), or set trainer.synthetic_data = True to train on synthetic noise on "
                         "purpose" % (folder, self.stage))
             assert isinstance(self.network, (SegmentationNetwork, nn.DataParallel))
@@ -1041,15 +1041,10 @@ class nnUNetTrainer_simple(object):
         from ... import preprocessing
         if not (isinstance(input_files, tuple) and len(input_files) == 2 and isinstance(input_files[1], dict)):
             reader = preprocessing.cropping.require_reader(reader, "preprocess_patient()")      # (before anything is computed)
-        preprocessor_name = self.plans.get('preprocessor_name')
-        if preprocessor_name is None:
-            preprocessor_name = "GenericPreprocessor"
-        if not self.threeD or preprocessor_name not in ("GenericPreprocessor", "GenericPreprocessor_linearResampling"):
-            raise NotImplementedError("preprocessor %r: the device preprocessing implements GenericPreprocessor and "
-                                      "GenericPreprocessor_linearResampling on 3-D plans" % (preprocessor_name,))
-        print("using preprocessor", preprocessor_name)
-        preprocessor = getattr(preprocessing, preprocessor_name)(self.normalization_schemes, self.use_mask_for_norm,
-                                                                 self.transpose_forward, self.intensity_properties)
+        preprocessor_class = preprocessing.preprocessing.preprocessor_class(self.plans.get('preprocessor_name'), self.threeD)
+        print("using preprocessor", preprocessor_class.__name__)
+        preprocessor = preprocessor_class(self.normalization_schemes, self.use_mask_for_norm, self.transpose_forward,
+                                          self.intensity_properties)
         return preprocessor.preprocess_test_case(input_files, self.plans['plans_per_stage'][self.stage]['current_spacing'],
                                                  reader=reader)
 

@@ -635,6 +635,31 @@ int e2e_pp_norm_stats(const float* x, const float* seg, const double* prm, doubl
                       void* stream);
 int e2e_pp_normalize(float* x, const float* seg, const double* prm, const double* stats, int C, long long vol, void* stream);
 
+/* ---- P3: class locations of a preprocessed training case ------------------------------------------------------------
+ * Replaces: e2enet/preprocessing/preprocessing.py:343-361 (GenericPreprocessor._run_internal): per class c of all_classes,
+ * np.argwhere(seg == c), which lists the class's voxels in raster order, and rows of it drawn by one RandomState.  seg: the
+ * contiguous fp32 label volume [D,H,W] (n = D*H*W voxels, whole-number labels) on the device.  classes: K fp32 values on the
+ * HOST (read before the call returns), 1 <= K <= pp_select_max_classes; the caller loops over longer lists.  A voxel equal to
+ * none of them belongs to no class (-1, 0, stray values, NaN).  All indices, offsets and counts are 64-bit.
+ *   pp_select_chunk: voxels per workgroup (a chunk of the flat volume; wave w of pass p owns voxels 256 p + 64 w .. + 63 of it).
+ *   pp_select_ws_bytes: workspace of one (n, K) pair: per chunk and class a 32-bit count and a 64-bit offset.  0: refused
+ *     (n < 1, K outside 1 .. pp_select_max_classes, or more than 2^24 - 1 chunks).
+ *   pp_select_count: counts[k] (device, K 64-bit words) = number of voxels equal to classes[k]; ws keeps the per-chunk counts
+ *     and their exclusive prefix sums for pp_select_coords.  One read of the volume.
+ *   pp_select_coords: for class k and every p in [class_offsets[k], class_offsets[k+1]): ranks[p] (device, ascending within a
+ *     class) is a position in the raster order of the class's voxels, slots[p] (device) in [0, class_offsets[k+1] -
+ *     class_offsets[k]) the row of the class it goes to: out[(class_offsets[k] + slots[p]) * 3 ..] = (i, j, k) of that voxel,
+ *     64-bit.  class_offsets: K + 1 non-decreasing 64-bit words on the HOST.  ws: as pp_select_count of the same seg, n and
+ *     classes left it.  A workgroup none of whose voxels was drawn leaves without reading the volume: at most one read.  Every
+ *     row has one writer and there are no atomics: the same bits on every run.  A rank that is not below the class's count
+ *     and a slot outside the class's rows write nothing.                                                                    */
+int e2e_pp_select_chunk(void);
+int e2e_pp_select_max_classes(void);
+long long e2e_pp_select_ws_bytes(long long n, int K);
+int e2e_pp_select_count(const float* seg, long long n, const float* classes, int K, long long* counts, void* ws, void* stream);
+int e2e_pp_select_coords(const float* seg, int D, int H, int W, const float* classes, int K, const long long* ranks,
+                         const long long* slots, const long long* class_offsets, long long* out, const void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
