@@ -212,12 +212,21 @@ SIGNATURES = {
     "e2e_pp_select_ws_bytes": (LL, [LL, I]),
     "e2e_pp_select_count": (I, [P, LL, P, I, P, P, P]),
     "e2e_pp_select_coords": (I, [P, I, I, I, P, I, P, P, P, P, P, P]),
+    "e2e_fingerprint_sample_chunk": (I, []),
+    "e2e_fingerprint_sample_ws_bytes": (LL, [LL]),
+    "e2e_fingerprint_sample_count": (I, [P, LL, P, P, P]),
+    "e2e_fingerprint_sample_gather": (I, [P, P, I, LL, I, P, LL, P, P]),
+    "e2e_fingerprint_stats_max_ranks": (I, []),
+    "e2e_fingerprint_stats_ws_bytes": (LL, []),
+    "e2e_fingerprint_stats": (I, [P, LL, P, I, P, P, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
               "e2e_convT_wgrad_ws_bytes", "e2e_conv133_input_ranges_ws_bytes", "e2e_in_lrelu_bwd_ws_doubles", "e2e_head1x1_wgrad_ws_bytes", "e2e_loss_ws_bytes", "e2e_aug_stats_ws_bytes",
               "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
-              "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes"}
+              "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes",
+              "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
+              "e2e_fingerprint_stats_ws_bytes"}
 
 
 class E2EError(RuntimeError):
@@ -255,7 +264,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 20          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 21          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

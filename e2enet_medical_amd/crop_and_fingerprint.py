@@ -1,0 +1,49 @@
+"""``python -m e2enet_medical_amd.crop_and_fingerprint -t TASK`` -- the cropping and fingerprint legs of the reference's
+``nnUNet_plan_and_preprocess`` on the device: the raw task folder (``<nnUNet_raw_data_base>/nnUNet_raw_data/<task>``) into the cropped
+folder (``<nnUNet_raw_data_base>/nnUNet_cropped_data/<task>``: ``<case>.npz``, ``<case>.pkl``, ``gt_segmentations``, ``dataset.json``),
+then its fingerprint (``dataset_properties.pkl``, and ``intensityproperties.pkl`` when a modality is CT), copied with ``dataset.json``
+into ``<nnUNet_preprocessed>/<task>`` where the reference's planner (``-no_pp``) reads it.  ``preprocess_dataset`` takes it from there."""
+import argparse
+import json
+import os
+import shutil
+
+from . import paths
+from .experiment_planning.DatasetAnalyzer import DEFAULT_NUM_THREADS, DatasetAnalyzer
+from .experiment_planning.utils import crop
+from .utilities.task_name_id_conversion import convert_id_to_task_name
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('-t', '--task_name', required=True, help='task name or task ID')
+    parser.add_argument('-tf', type=int, default=DEFAULT_NUM_THREADS, required=False,
+                        help='host threads that write cropped cases and read them again (at most 16); the GPU work is one process')
+    parser.add_argument('--override', action='store_true',
+                        help='empty the cropped folder and crop every case again, and recompute the intensity properties')
+    return parser
+
+
+def main(argv=None, reader=None):
+    args = build_parser().parse_args(argv)
+    task_name = args.task_name
+    if not task_name.startswith("Task"):
+        task_name = convert_id_to_task_name(int(task_name))
+    raw = os.path.join(paths.nnUNet_raw_data, task_name)
+    assert os.path.isfile(os.path.join(raw, "dataset.json")), "dataset.json not found. Expected: %s" % os.path.join(raw, "dataset.json")
+    crop(task_name, args.override, args.tf, reader=reader)
+    cropped = os.path.join(paths.nnUNet_cropped_data, task_name)
+    preprocessed = os.path.join(paths.preprocessing_output_dir, task_name)
+    # the intensity properties are collected only when one of the modalities is CT
+    with open(os.path.join(cropped, 'dataset.json'), 'r') as f:
+        modalities = list(json.load(f)["modality"].values())
+    collect_intensityproperties = ("CT" in modalities) or ("ct" in modalities)
+    dataset_analyzer = DatasetAnalyzer(cropped, overwrite=args.override, num_processes=args.tf)
+    dataset_analyzer.analyze_dataset(collect_intensityproperties)
+    os.makedirs(preprocessed, exist_ok=True)
+    shutil.copy(os.path.join(cropped, "dataset_properties.pkl"), preprocessed)
+    shutil.copy(os.path.join(raw, "dataset.json"), preprocessed)
+
+
+if __name__ == "__main__":
+    main()

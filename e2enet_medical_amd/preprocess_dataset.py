@@ -2,7 +2,8 @@
 ``nnUNet_plan_and_preprocess`` on the device: the task's cropped folder (``<nnUNet_raw_data_base>/nnUNet_cropped_data/<task>``) and its
 3-D plans file (``<nnUNet_preprocessed>/<task>/<plans identifier>_plans_3D.pkl``, written by the reference's planner, e.g. with
 ``-no_pp``) into the stage folders ``<nnUNet_preprocessed>/<task>/<data_identifier>_stage<i>`` that ``simple_main`` trains on.
-Cropping, the dataset fingerprint and experiment planning stay with the reference."""
+The cropped folder and its fingerprint come from ``python -m e2enet_medical_amd.crop_and_fingerprint``; experiment planning stays
+with the reference."""
 import argparse
 import os
 

@@ -1,17 +1,24 @@
 """The reference's e2enet/preprocessing/cropping.py on the device (csrc/preprocess.hip): non-zero mask with filled holes, its
-bounding box and the crop, in memory.
+bounding box and the crop, in memory or from a raw task folder into a cropped folder.
 
   create_nonzero_mask, get_bbox_from_mask, crop_to_bbox, crop_to_nonzero   :23-116, same names, arguments and return values
   ImageCropper.crop, ImageCropper.crop_from_list_of_files                  :139-155
+  ImageCropper.load_crop_save, run_cropping, load_properties, ...          :157-217, with a ``reader`` argument
+  get_patient_identifiers_from_cropped_files                               :119-120
   load_case_from_list_of_files                                             :61-81, the default ``reader``
 
 Arrays are numpy arrays or device tensors; a numpy array is uploaded once and the results come back as numpy arrays, a device
 tensor stays on the device.  Files are read by a ``reader(list_of_files) -> (data [C, X, Y, Z], properties)`` callback, the
 counterpart of the ``writer`` of ``predict_cases``; the default is the reference's SimpleITK loader when SimpleITK is importable.
 There is no host fallback for the arithmetic: without the library or a device these functions raise."""
-from collections import OrderedDict
+import os
+import pickle
+import shutil
+from collections import OrderedDict, deque
 
 import numpy as np
+
+MAX_WRITER_THREADS = 16              # host threads that compress and write finished cases (never sized from the machine)
 
 
 def _device():
@@ -203,11 +210,39 @@ def load_case(data_files, seg_file, reader, what):
     return data, None, properties
 
 
+def load_seg_with_reader(seg_file, reader):
+    """``seg [1, X, Y, Z]`` fp32 of a segmentation file: ``reader`` is handed the one-file list and the first channel is kept"""
+    seg, _ = reader([seg_file])
+    return np.asarray(seg[0:1], dtype=np.float32)
+
+
+def load_case_with_reader(data_files, seg_file, reader, what):
+    """``(data, seg or None, properties)`` like load_case_from_list_of_files (reference :61-81), every file read through ``reader``
+    (default: the SimpleITK loader; without either, the refusal of require_reader)"""
+    assert isinstance(data_files, (list, tuple)), "case must be either a list or a tuple"
+    reader = require_reader(reader, what)
+    data, properties = reader(list(data_files))
+    data = np.asarray(data, dtype=np.float32)
+    properties.setdefault("original_size_of_raw_data", np.array([int(v) for v in data.shape[1:]]))
+    properties.setdefault("list_of_data_files", data_files)
+    properties["seg_file"] = seg_file
+    seg = load_seg_with_reader(seg_file, reader) if seg_file is not None else None
+    return data, seg, properties
+
+
+def get_patient_identifiers_from_cropped_files(folder):
+    """Reference :119-120: the sorted case names of the ``.npz`` files of a cropped folder"""
+    return sorted(f[:-4] for f in os.listdir(folder) if f.endswith(".npz") and os.path.isfile(os.path.join(folder, f)))
+
+
 class ImageCropper(object):
-    """Reference :123-155, the in-memory part (``num_threads`` and ``output_folder`` are accepted and unused: nothing is written)"""
+    """Reference :123-217.  The device crops one case after the other; ``num_threads`` (at most 16) host threads compress and write
+    the finished ones meanwhile."""
 
     def __init__(self, num_threads=None, output_folder=None):
         self.num_threads, self.output_folder = num_threads, output_folder
+        if self.output_folder is not None:
+            os.makedirs(self.output_folder, exist_ok=True)
 
     @staticmethod
     def crop(data, properties, seg=None):
@@ -234,3 +269,78 @@ class ImageCropper(object):
         """Reference :152-155 through the ``reader`` callback (a seg file needs the SimpleITK loader)"""
         data, seg, properties = load_case(data_files, seg_file, reader, "ImageCropper.crop_from_list_of_files")
         return ImageCropper.crop(data, properties, seg)
+
+    def _is_done(self, case_identifier):
+        return all(os.path.isfile(os.path.join(self.output_folder, case_identifier + e)) for e in (".npz", ".pkl"))
+
+    def _crop_case(self, case, reader):
+        """the device half of load_crop_save: ``(vstack((data, seg)) as fp32 numpy, properties)``"""
+        import torch
+        data, seg, properties = load_case_with_reader(case[:-1], case[-1], reader, "ImageCropper.load_crop_save")
+        data, seg, properties = self.crop(to_device(data)[0], properties, to_device(seg)[0] if seg is not None else None)
+        return torch.cat((data, seg)).cpu().numpy(), properties
+
+    def _write_case(self, all_data, properties, case_identifier):
+        """the host half: ``<case>.npz`` (key ``data``) with a fixed time stamp, ``<case>.pkl``.  Touches no device."""
+        from .preprocessing import save_npz
+        save_npz(os.path.join(self.output_folder, "%s.npz" % case_identifier), all_data)
+        self.save_properties(case_identifier, properties)
+
+    def load_crop_save(self, case, case_identifier, overwrite_existing=False, reader=None):
+        """Reference :157-174.  ``case``: the modality files and, last, the segmentation file (or None)"""
+        try:
+            print(case_identifier)
+            if overwrite_existing or not self._is_done(case_identifier):
+                self._write_case(*self._crop_case(case, reader), case_identifier)
+        except Exception as e:
+            print("Exception in", case_identifier, ":")
+            print(e)
+            raise e
+
+    def get_list_of_cropped_files(self):
+        """Reference :176-177"""
+        return [os.path.join(self.output_folder, c + ".npz") for c in get_patient_identifiers_from_cropped_files(self.output_folder)]
+
+    def get_patient_identifiers_from_cropped_files(self):
+        """Reference :179-180"""
+        return [i.split("/")[-1][:-4] for i in self.get_list_of_cropped_files()]
+
+    def run_cropping(self, list_of_files, overwrite_existing=False, output_folder=None, reader=None):
+        """Reference :182-208: copies the ground-truth files into ``gt_segmentations`` and crops every case of ``list_of_files``
+        (``[[modality files ..., seg file], ...]``) into ``<case>.npz`` (key ``data``: modalities and seg stacked, fp32) and
+        ``<case>.pkl``.  ``overwrite_existing=False`` skips a case whose two files exist.  This process owns the GPU and walks the
+        cases; the writer threads compress and write finished ones.  The files do not depend on their number."""
+        from concurrent.futures import ThreadPoolExecutor
+        if output_folder is not None:
+            self.output_folder = output_folder
+        output_folder_gt = os.path.join(self.output_folder, "gt_segmentations")
+        os.makedirs(output_folder_gt, exist_ok=True)
+        for case in list_of_files:
+            if case[-1] is not None:
+                shutil.copy(case[-1], output_folder_gt)
+        reader = require_reader(reader, "ImageCropper.run_cropping")
+        workers = max(1, min(int(self.num_threads if self.num_threads is not None else 1), MAX_WRITER_THREADS))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            pending = deque()
+            for case in list_of_files:
+                case_identifier = get_case_identifier(case)
+                print(case_identifier)
+                if not overwrite_existing and self._is_done(case_identifier):
+                    continue
+                done = self._crop_case(case, reader)
+                while len(pending) >= workers:               # bounds the finished cases held in host memory
+                    pending.popleft().result()
+                pending.append(pool.submit(self._write_case, *done, case_identifier))
+            while pending:
+                pending.popleft().result()
+
+    def load_properties(self, case_identifier):
+        """Reference :210-213"""
+        with open(os.path.join(self.output_folder, "%s.pkl" % case_identifier), 'rb') as f:
+            properties = pickle.load(f)
+        return properties
+
+    def save_properties(self, case_identifier, properties):
+        """Reference :215-217"""
+        with open(os.path.join(self.output_folder, "%s.pkl" % case_identifier), 'wb') as f:
+            pickle.dump(properties, f)

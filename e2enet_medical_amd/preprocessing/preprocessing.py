@@ -22,13 +22,12 @@ from collections import deque
 import numpy as np
 
 from .class_sampling import MIN_PERCENT_COVERAGE, NUM_SAMPLES, SEED, draw_ranks, sort_ranks
-from .cropping import ImageCropper, _stream, label_values, load_case, to_device
+from .cropping import MAX_WRITER_THREADS, ImageCropper, _stream, label_values, load_case, to_device
 
 RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD = 3        # reference e2enet/configuration.py
 SPLINE_PAD = 12                                  # scipy's pre-padding for mode 'nearest' in front of the spline prefilter
 SCHEMES = {"CT": 1, "CT2": 2, "noNorm": 3}       # every other name is the default scheme (0)
 DEFAULT_NUM_THREADS = 8                          # reference e2enet/configuration.py
-MAX_WRITER_THREADS = 16                          # host threads that compress and write finished cases (never sized from the machine)
 BUILT_PREPROCESSORS = ("GenericPreprocessor", "GenericPreprocessor_linearResampling")
 
 

@@ -660,6 +660,35 @@ int e2e_pp_select_count(const float* seg, long long n, const float* classes, int
 int e2e_pp_select_coords(const float* seg, int D, int H, int W, const float* classes, int K, const long long* ranks,
                          const long long* slots, const long long* class_offsets, long long* out, const void* ws, void* stream);
 
+/* ---- P4: the dataset fingerprint of a cropped training folder --------------------------------------------------------
+ * Replaces: e2enet/experiment_planning/DatasetAnalyzer.py:161-179 (_get_voxels_in_foreground: modality[seg > 0][::10] per case
+ * and modality; _compute_stats: np.median / mean / std / min / max / percentile over a Python list of the samples).  A cropped
+ * case is [C + 1, X, Y, Z] fp32 on the device with the seg last; n = X*Y*Z voxels.  All indices, offsets and counts are 64-bit.
+ *   fingerprint_sample_chunk: voxels per workgroup (a chunk of the flat seg, laid out like pp_select_chunk's).
+ *   fingerprint_sample_ws_bytes: workspace of a volume of n voxels: per chunk a 32-bit count and a 64-bit offset.  0: refused
+ *     (n < 1 or more than 2^24 - 1 chunks).
+ *   fingerprint_sample_count: *n_fg (device, one 64-bit word) = number of voxels with seg > 0 (a NaN is not); ws keeps the
+ *     per-chunk counts and their exclusive prefix sums for fingerprint_sample_gather.  One read of the seg.
+ *   fingerprint_sample_gather: out[c * out_len + r / stride] = data[c * n + v] for c < C and every voxel v with seg > 0 whose
+ *     rank r in the raster order of those voxels is a multiple of stride (1 .. 2^30): out[c] is data[c][seg > 0][::stride] when
+ *     out_len = ceil(n_fg / stride); a column >= out_len is not written.  ws: as fingerprint_sample_count of the same seg and n
+ *     left it.  A chunk without a sampled rank is not read; the seg is read once whatever C is.  One writer per element.
+ *   fingerprint_stats: over the n (1 .. 2^32 - 1) values of x (device).  out (device, 16 doubles): [0] number of NaNs, [1] min,
+ *     [2] max, [3] sum (NaNs left out of all three), [4] sum of (x - out[3] / n)^2, [5..7] 0, [8 + r] the value at position
+ *     ranks[r] of the sorted array (exact, as stored; -0.0 sorts in front of 0.0, a NaN behind +inf).  ranks: num_ranks (1 ..
+ *     fingerprint_stats_max_ranks) positions in [0, n) on the HOST, read before the call returns; duplicates are allowed.
+ *     Sums are fp64 per-workgroup partials added in workgroup order; the order statistics come from a byte-wise radix select (four
+ *     sweeps of x for all ranks together, integer histograms).  ws: fingerprint_stats_ws_bytes bytes.  The same bits on every run. */
+int e2e_fingerprint_sample_chunk(void);
+long long e2e_fingerprint_sample_ws_bytes(long long n);
+int e2e_fingerprint_sample_count(const float* seg, long long n, long long* n_fg, void* ws, void* stream);
+int e2e_fingerprint_sample_gather(const float* data, const float* seg, int C, long long n, int stride, float* out,
+                                  long long out_len, const void* ws, void* stream);
+int e2e_fingerprint_stats_max_ranks(void);
+long long e2e_fingerprint_stats_ws_bytes(void);
+int e2e_fingerprint_stats(const float* x, long long n, const long long* ranks, int num_ranks, double* out, void* ws,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,12 @@
                                                       (np.argwhere + RandomState.choice per class) on the same downloaded volume
    python tools/dataset_bench.py run [threads]        GenericPreprocessor.run over a synthetic cropped folder: wall time per case,
                                                       the share of the device half and of the compression + writing
+   python tools/dataset_bench.py fingerprint          the dataset fingerprint of one 256 x 400 x 400 CT-like case (two modalities, about
+                                                      30 % foreground): device time of the two sample passes, of the statistics over
+                                                      the case's sample and over 100 copies of it behind one another, wall time of
+                                                      DatasetAnalyzer.collect_intensity_properties over a synthetic cropped folder, and
+                                                      the host time of the reference's method on the same arrays (modality[mask][::10]
+                                                      as a list, list concatenation, the seven numpy calls)
 small: 128 x 160 x 160 with 3 classes; large: 256 x 400 x 400 with 15 classes.  Each mode prints one JSON line."""
 import json
 import os
@@ -150,10 +156,125 @@ def bench_run(threads):
                           "threads_env": os.environ.get("OMP_NUM_THREADS")}))
 
 
+def ct_like_case(shape, seed):
+    """[3, *shape] fp32: two modalities of whole-number intensities that follow the labels, and the label volume of label_volume"""
+    rng = np.random.default_rng(seed)
+    seg = label_volume(shape, 3, seed=seed)
+    out = np.empty((3,) + tuple(shape), dtype=np.float32)
+    for c in range(2):
+        out[c] = np.rint(rng.standard_normal(shape, dtype=np.float32) * (25.0 + 10.0 * c) + 100.0)
+        out[c] += 40.0 * seg
+        out[c] *= seg >= 0
+    out[2] = seg
+    return out
+
+
+def reference_stats(voxels):
+    """DatasetAnalyzer._compute_stats of the reference, on the list it is handed"""
+    if len(voxels) == 0:
+        return (np.nan,) * 7
+    return (np.median(voxels), np.mean(voxels), np.std(voxels), np.min(voxels), np.max(voxels), np.percentile(voxels, 99.5),
+            np.percentile(voxels, 00.5))
+
+
+def reference_intensity_properties(folder, cases, num_modalities):
+    """collect_intensity_properties of the reference without its process pool: one read of every case per modality"""
+    out = []
+    for mod in range(num_modalities):
+        v = []
+        for c in cases:
+            all_data = np.load(os.path.join(folder, c + ".npz"))['data']
+            v.append(list(all_data[mod][all_data[-1] > 0][::10]))
+        w = []
+        for iv in v:
+            w += iv
+        out.append((reference_stats(w), [reference_stats(iv) for iv in v]))
+    return out
+
+
+def bench_fingerprint():
+    import torch
+    from e2enet_medical_amd._lib import lib
+    from e2enet_medical_amd.experiment_planning import DatasetAnalyzer
+    from e2enet_medical_amd.experiment_planning.DatasetAnalyzer import foreground_sample
+    from e2enet_medical_amd.experiment_planning.intensity_stats import requested_ranks
+    from e2enet_medical_amd.preprocessing.preprocessing import save_npz
+    shape, copies = (256, 400, 400), 100
+    case = ct_like_case(shape, 31)
+    dev = torch.from_numpy(case).cuda()
+    L, st = lib(), torch.cuda.current_stream().cuda_stream
+    n = int(np.prod(shape))
+    ws = torch.empty(L.fingerprint_sample_ws_bytes(n), dtype=torch.uint8, device="cuda")
+    n_fg = torch.empty(1, dtype=torch.int64, device="cuda")
+    ms_count = median_ms(lambda: L.fingerprint_sample_count(dev[2].data_ptr(), n, n_fg.data_ptr(), ws.data_ptr(), st))
+    fg = int(n_fg.item())
+    m = -(-fg // 10)
+    out = torch.empty((2, m), dtype=torch.float32, device="cuda")
+    ms_gather = median_ms(lambda: L.fingerprint_sample_gather(dev.data_ptr(), dev[2].data_ptr(), 2, n, 10, out.data_ptr(), m, ws.data_ptr(), st))
+    sample = foreground_sample(dev)
+    assert torch.equal(sample, out)
+
+    def stats_ms(x, inner):
+        ranks = np.asarray(requested_ranks(x.numel()), dtype=np.int64)
+        sws = torch.empty(L.fingerprint_stats_ws_bytes(), dtype=torch.uint8, device="cuda")
+        res = torch.empty(16, dtype=torch.float64, device="cuda")
+        return median_ms(lambda: L.fingerprint_stats(x.data_ptr(), x.numel(), ranks.ctypes.data, len(ranks), res.data_ptr(), sws.data_ptr(), st),
+                         inner=inner)
+    ms_stats_case = stats_ms(sample[0], 20)
+    big = sample[0].repeat(copies)
+    ms_stats_big = stats_ms(big, 3)
+    got_case, got_big = DatasetAnalyzer._compute_stats(sample[0]), DatasetAnalyzer._compute_stats(big)
+    # the reference's method on the same arrays, one modality of the case, then the seven numbers of the list
+    host = case
+    t0 = time.perf_counter()
+    voxels = list(host[0][host[-1] > 0][::10])
+    t1 = time.perf_counter()
+    want_case = reference_stats(voxels)
+    t2 = time.perf_counter()
+    assert len(voxels) == m and got_case[0] == want_case[0] and got_case[3] == want_case[3] and got_case[4] == want_case[4]
+    del dev, big, out
+    # a folder of smaller cases: the whole of collect_intensity_properties against the reference's loop over the same files
+    fshape, n_cases = (128, 200, 200), 4
+    with tempfile.TemporaryDirectory() as tmp:
+        names = ["case_%d" % i for i in range(n_cases)]
+        for i, c in enumerate(names):
+            save_npz(os.path.join(tmp, c + ".npz"), ct_like_case(fshape, 50 + i))
+        with open(os.path.join(tmp, "dataset.json"), "w") as f:
+            json.dump({"modality": {"0": "CT", "1": "CT"}, "labels": {"0": "bg", "1": "a", "2": "b", "3": "c"}}, f)
+        walls = {}
+        for th in (1, 8):
+            an = DatasetAnalyzer(tmp, overwrite=True, num_processes=th)
+            t3 = time.perf_counter()
+            got = an.collect_intensity_properties(2)
+            torch.cuda.synchronize()
+            walls[str(th)] = round(time.perf_counter() - t3, 3)
+        t3 = time.perf_counter()
+        want = reference_intensity_properties(tmp, names, 2)
+        s_ref_folder = time.perf_counter() - t3
+        ulps = []
+        for mod in range(2):
+            assert got[mod]['median'] == want[mod][0][0] and got[mod]['mn'] == want[mod][0][3]
+            for k, i in (('percentile_99_5', 5), ('percentile_00_5', 6), ('mean', 1), ('sd', 2)):
+                ulps.append(abs(float(got[mod][k]) - float(want[mod][0][i])) / float(np.spacing(np.float32(abs(want[mod][0][i])))))
+    print(json.dumps({"mode": "fingerprint", "shape": list(shape), "modalities": 2, "foreground_voxels": fg, "sample_per_modality": m,
+                      "ms_sample_count": round(ms_count, 3), "ms_sample_gather": round(ms_gather, 3),
+                      "gbps_count": round(n * 4 / ms_count / 1e6, 1), "ms_stats_case": round(ms_stats_case, 3),
+                      "values_100_copies": m * copies, "ms_stats_100_copies": round(ms_stats_big, 3),
+                      "gbps_stats_100_copies_6_sweeps": round(6 * m * copies * 4 / ms_stats_big / 1e6, 1),
+                      "stats_100_copies_equal_case": [bool(a == b) for a, b in zip(got_big, got_case)],
+                      "s_reference_sample_as_list_one_modality": round(t1 - t0, 3), "s_reference_seven_numpy_calls": round(t2 - t1, 3),
+                      "folder": {"cases": n_cases, "shape": list(fshape), "s_collect_intensity_properties_by_threads": walls,
+                                 "s_reference_method_host": round(s_ref_folder, 3),
+                                 "max_fp32_ulp_from_reference_pct_mean_sd": round(max(ulps), 2)},
+                      "threads_env": os.environ.get("OMP_NUM_THREADS")}))
+
+
 def main(argv):
     mode = argv[0] if argv else "select"
     if mode == "select":
         bench_select(argv[1] if len(argv) > 1 else "small")
+    elif mode == "fingerprint":
+        bench_fingerprint()
     else:
         bench_run([int(v) for v in argv[1:]] or [1, 8])
 
