@@ -190,6 +190,11 @@ SIGNATURES = {
     "e2e_distance_transform_edt_sq": (I, [P, P, I, I, I, C.c_double, C.c_double, C.c_double, P]),
     "e2e_surface_distances_ws_bytes": (LL, []),
     "e2e_surface_distances_stats": (I, [P, P, P, P, LL, C.c_double, LL, LL, P, P, P]),
+    "e2e_eval_census_max_slots": (I, []),
+    "e2e_eval_census_chunk": (LL, []),
+    "e2e_eval_census_workgroups": (I, []),
+    "e2e_eval_census": (I, [P, P, P, I, I, I, I, P, P, P]),
+    "e2e_surface_border_set": (I, [P, P, P, P, I, I, I, P]),
     "e2e_cc_ws_bytes": (LL, [I, I, I]),
     "e2e_cc_remove_all_but_largest": (I, [P, I, I, I, P, C.c_double, C.c_double, P, P, P]),
     "e2e_pp_nonzero_ws_bytes": (LL, [I, I, I]),
@@ -226,7 +231,7 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
               "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes",
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
-              "e2e_fingerprint_stats_ws_bytes"}
+              "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups"}
 
 
 class E2EError(RuntimeError):
@@ -264,7 +269,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 21          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 22          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

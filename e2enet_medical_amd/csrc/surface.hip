@@ -1,4 +1,4 @@
-// K10: surface-distance scoring (gfx950): border mask of one label read straight from the uint8 label volume, exact squared
+// K10: surface-distance scoring (gfx950): border mask of one label (or one set of labels) read straight from the uint8 label volume, exact squared
 // Euclidean distance transform with per-axis spacing, and the reductions behind Hausdorff / HD95 / ASD / ASSD / NSD.
 // Reference: medpy's __surface_distances as called by e2enet/evaluation/metrics.py:792-861 and surface_dice.py:20-56
 // (binary_erosion with the 6-neighbour cross, distance_transform_edt(~border, sampling)).
@@ -23,20 +23,33 @@ struct StatsWs {
   unsigned long long k[2];             // rank inside the prefix's bucket
 };
 
-__device__ __forceinline__ bool is_label(const unsigned char* __restrict__ x, long long i, int label) { return (int)x[i] == label; }
+// the two membership tests a border is taken of: one label value, or a set of values (bit v of eight words)
+struct IsLabel {
+  int label;
+  __device__ __forceinline__ bool operator()(unsigned char v) const { return (int)v == label; }
+};
+struct InSet {
+  unsigned w0, w1, w2, w3, w4, w5, w6, w7;
+  __device__ __forceinline__ bool operator()(unsigned char v) const {
+    const unsigned q = v >> 5;
+    const unsigned w = q == 0u ? w0 : q == 1u ? w1 : q == 2u ? w2 : q == 3u ? w3 : q == 4u ? w4 : q == 5u ? w5 : q == 6u ? w6 : w7;
+    return (w >> (v & 31u)) & 1u;
+  }
+};
 
-// border(m) = m & ~erode(m), m = (x == label), 6-neighbour cross, outside the volume = 0; count += number of border voxels
-__global__ __launch_bounds__(256) void border_kernel(const unsigned char* __restrict__ x, int label, unsigned char* __restrict__ border,
+// border(m) = m & ~erode(m), m = member(x), 6-neighbour cross, outside the volume = 0; count += number of border voxels
+template <class Member>
+__global__ __launch_bounds__(256) void border_kernel(const unsigned char* __restrict__ x, Member member, unsigned char* __restrict__ border,
                                                      unsigned long long* __restrict__ count, int D, int H, int W) {
   const long long n = (long long)D * H * W, hw = (long long)H * W;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   bool b = false;
   if (i < n) {
     const int w = (int)(i % W), h = (int)((i / W) % H), d = (int)(i / hw);
-    if (is_label(x, i, label)) {
+    if (member(x[i])) {
       const bool inner = d > 0 && d < D - 1 && h > 0 && h < H - 1 && w > 0 && w < W - 1 &&
-                         is_label(x, i - hw, label) && is_label(x, i + hw, label) && is_label(x, i - W, label) &&
-                         is_label(x, i + W, label) && is_label(x, i - 1, label) && is_label(x, i + 1, label);
+                         member(x[i - hw]) && member(x[i + hw]) && member(x[i - W]) &&
+                         member(x[i + W]) && member(x[i - 1]) && member(x[i + 1]);
       b = !inner;
     }
     border[i] = b ? 1 : 0;
@@ -230,20 +243,33 @@ int stat_blocks(long long n) {
   return (int)(b < STAT_BLOCKS ? b : STAT_BLOCKS);
 }
 
+template <class Member>
+int launch_border(const char* what, const unsigned char* labels, Member member, unsigned char* border, long long* count, int D, int H, int W,
+                  void* stream) {
+  if (!dims_ok(what, D, H, W)) return E2E_ERR_ARG;
+  E2E_REQUIRE(labels && border && count, "%s: null pointer", what);
+  const long long n = (long long)D * H * W;
+  E2E_REQUIRE(e2e::cdivll(n, 256) <= 0x7FFFFFFFll, "%s: volume too large (%lld voxels)", what, n);
+  hipStream_t st = (hipStream_t)stream;
+  e2e::zero_async(count, 8, st);
+  hipLaunchKernelGGL(border_kernel<Member>, dim3((unsigned)e2e::cdivll(n, 256)), dim3(256), 0, st, labels, member, border,
+                     (unsigned long long*)count, D, H, W);
+  return e2e::check_launch("border_kernel");
+}
+
 }  // namespace
 
 extern "C" int e2e_surface_border(const unsigned char* labels, int label, unsigned char* border, long long* count, int D, int H,
                                   int W, void* stream) {
-  if (!dims_ok("surface_border", D, H, W)) return E2E_ERR_ARG;
-  E2E_REQUIRE(labels && border && count, "surface_border: null pointer");
   E2E_REQUIRE(label >= 0 && label <= 255, "surface_border: label %d is outside a uint8 volume's range", label);
-  const long long n = (long long)D * H * W;
-  E2E_REQUIRE(e2e::cdivll(n, 256) <= 0x7FFFFFFFll, "surface_border: volume too large (%lld voxels)", n);
-  hipStream_t st = (hipStream_t)stream;
-  e2e::zero_async(count, 8, st);
-  hipLaunchKernelGGL(border_kernel, dim3((unsigned)e2e::cdivll(n, 256)), dim3(256), 0, st, labels, label, border,
-                     (unsigned long long*)count, D, H, W);
-  return e2e::check_launch("border_kernel");
+  return launch_border("surface_border", labels, IsLabel{label}, border, count, D, H, W, stream);
+}
+
+extern "C" int e2e_surface_border_set(const unsigned char* labels, const unsigned* members, unsigned char* border, long long* count, int D,
+                                      int H, int W, void* stream) {
+  E2E_REQUIRE(members, "surface_border_set: null pointer");
+  const InSet set{members[0], members[1], members[2], members[3], members[4], members[5], members[6], members[7]};
+  return launch_border("surface_border_set", labels, set, border, count, D, H, W, stream);
 }
 
 extern "C" int e2e_surface_max_line(void) { return MAX_LINE; }

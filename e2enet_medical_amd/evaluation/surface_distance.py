@@ -70,11 +70,38 @@ def label_boxes(test, reference):
     return boxes
 
 
+def _members(label):
+    """None for one integer label, else the sorted tuple of distinct values of a label set (a region)"""
+    if isinstance(label, (tuple, list, set, frozenset, np.ndarray)):
+        return tuple(sorted({int(v) for v in label}))
+    return None
+
+
+def member_words(values):
+    """the 256-bit set of uint8 values as the eight words e2e_surface_border_set reads; values outside [0, 255] occur in no volume"""
+    import ctypes
+    words = (ctypes.c_uint * 8)()
+    for v in values:
+        if 0 <= int(v) <= 255:
+            words[int(v) >> 5] |= 1 << (int(v) & 31)
+    return words
+
+
+def union_box(boxes, values):
+    """the smallest box around the boxes of ``values`` (those that have one); None when none has"""
+    have = [boxes[v] for v in values if v in boxes]
+    if not have:
+        return None
+    return tuple(slice(min(b[a].start for b in have), max(b[a].stop for b in have)) for a in range(3))
+
+
 class SurfaceScorer:
     """Both label volumes of one case on the device (uploaded once); every label of the case is scored from that copy, inside the
-    label's bounding box when ``crop`` is set."""
+    label's bounding box when ``crop`` is set.  ``boxes``: value -> three slices, e.g. from ``evaluator.label_census``; given, it
+    replaces the host ``find_objects`` pass of ``label_boxes``.  A label is one integer or a tuple of integers (a region: the
+    mask "value is in the tuple"), scored inside the union of its members' boxes."""
 
-    def __init__(self, test, reference, voxel_spacing=None, crop=True):
+    def __init__(self, test, reference, voxel_spacing=None, crop=True, boxes=None):
         import torch
         from .._lib import lib
         if not torch.cuda.is_available():
@@ -86,7 +113,7 @@ class SurfaceScorer:
             raise ValueError("Shape mismatch: {} and {}".format(tuple(test.shape), tuple(reference.shape)))
         dev = torch.device("cuda")
         host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x
-        self.boxes = label_boxes(host(test), host(reference)) if crop else None
+        self.boxes = None if not crop else dict(boxes) if boxes is not None else label_boxes(host(test), host(reference))
         # (np.array: a contiguous copy torch may wrap whatever the caller's array allows)
         up = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x, order="C"))).to(dev).contiguous()
         self.test, self.reference = up(test), up(reference)
@@ -100,7 +127,11 @@ class SurfaceScorer:
         """the volumes the next calls work on: the label's bounding box of both volumes (a contiguous device copy), or the whole
         volumes for ``label=None`` or a scorer built with ``crop=False``"""
         import torch
-        box = None if label is None or self.boxes is None else self.boxes.get(int(label))
+        if label is None or self.boxes is None:
+            box = None
+        else:
+            members = _members(label)
+            box = self.boxes.get(int(label)) if members is None else union_box(self.boxes, members)
         self.vols = [self.test, self.reference] if box is None else [self.test[box].contiguous(), self.reference[box].contiguous()]
         self.shape = tuple(int(v) for v in self.vols[0].shape)
         dev = self.test.device
@@ -109,10 +140,15 @@ class SurfaceScorer:
 
     def border(self, which, label):
         """(border mask uint8 tensor of the selected volumes' shape; number of border voxels, a device scalar) of
-        ``volume == label``; ``which``: 0 = test, 1 = reference"""
+        ``volume == label`` (a tuple: of "volume is one of its values"); ``which``: 0 = test, 1 = reference"""
         D, H, W = self.shape
-        self.L.surface_border(self.vols[which].data_ptr(), int(label), self.borders[which].data_ptr(), self.count[which:].data_ptr(),
-                              D, H, W, self.stream)
+        members = _members(label)
+        if members is None:
+            self.L.surface_border(self.vols[which].data_ptr(), int(label), self.borders[which].data_ptr(), self.count[which:].data_ptr(),
+                                  D, H, W, self.stream)
+        else:
+            self.L.surface_border_set(self.vols[which].data_ptr(), member_words(members), self.borders[which].data_ptr(),
+                                      self.count[which:].data_ptr(), D, H, W, self.stream)
         return self.borders[which], self.count[which]
 
     def edt_sq(self, which):

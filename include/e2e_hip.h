@@ -559,6 +559,27 @@ int e2e_surface_distances_stats(const unsigned char* border_a, const float* dt2_
                                 const float* dt2_a, long long n, double threshold, long long rank_lo, long long rank_hi,
                                 double* out, void* ws, void* stream);
 
+/* ---- E2: label census of a (prediction, ground truth) pair; border of a label set ---------------------------------------
+ * Replaces: ConfusionMatrix.compute (e2enet/evaluation/metrics.py:67-80: four boolean passes per label and volume) and the
+ * scipy.ndimage.find_objects pass that finds the label boxes surface scoring works in.  test / reference: uint8 [D,H,W] on the
+ * device, W contiguous, any byte alignment (16-byte loads where both pointers share their phase modulo 16, byte loads otherwise).
+ *   eval_census: one pass, 2 B read per voxel.  lut: 256 bytes on the HOST (read before the call returns), value -> slot in
+ *     [0, slots); 1 <= slots <= eval_census_max_slots (values nobody evaluates share one slot).  joint (device, slots * slots
+ *     64-bit words) [reference slot * slots + test slot] = number of voxels with that pair, exact.  boxes (device, slots * 6
+ *     ints) [slot] = lo d, h, w then exclusive hi d, h, w over the voxels that carry the slot in EITHER volume; a slot nobody
+ *     carries has lo = INT_MAX >= hi = 0 on every axis.  Both are initialised by the callee.  Integer atomics only: the same
+ *     bits on every run.  A fixed grid of at most eval_census_workgroups workgroups strides over chunks of eval_census_chunk
+ *     voxels; a volume that would give one workgroup 2^32 voxels or more is refused (32-bit bins in LDS).
+ *   surface_border_set: surface_border on the mask "the value's bit is set in members" (8 HOST words, bit v of the 256 = value
+ *     v belongs; the empty set gives an empty border).  One kernel serves both entry points.                                  */
+int e2e_eval_census_max_slots(void);
+long long e2e_eval_census_chunk(void);
+int e2e_eval_census_workgroups(void);
+int e2e_eval_census(const unsigned char* test, const unsigned char* reference, const unsigned char* lut, int slots, int D, int H,
+                    int W, unsigned long long* joint, int* boxes, void* stream);
+int e2e_surface_border_set(const unsigned char* labels, const unsigned* members, unsigned char* border, long long* count, int D,
+                           int H, int W, void* stream);
+
 /* ---- P1: connected-component post-processing of exported label volumes -------------------------------------------
  * Replaces: remove_all_but_the_largest_connected_component (e2enet/postprocessing/connected_components.py:50-107): one
  * scipy.ndimage.label over the whole volume per class entry and one (lmap == id).sum() per object.  volume: uint8 [D,H,W], W
