@@ -3,95 +3,49 @@
 // lists the class's voxels in raster order, then RandomState(1234).choice(n, t, replace=False) rows of it.  The label volume is
 // where resample_and_normalize left it, on the device; only the K class totals go down and only the drawn ranks come up.
 //
-//   e2e_pp_select_count    a workgroup owns SEL_CHUNK consecutive voxels of the flat fp32 volume and writes how many of them equal
-//                          each class (one 64-bit ballot and a popcount per class and 64 voxels); one workgroup per class then scans
-//                          the per-chunk counts into exclusive 64-bit offsets and the class total
+// The raster rank of a class's voxels comes from e2e_rank.h (chunks, counts, offset scan, rank inside a chunk), one count row per class.
+//
+//   e2e_pp_select_count    a workgroup writes how many voxels of its chunk equal each class; one workgroup per class then scans the
+//                          per-chunk counts into exclusive 64-bit offsets and the class total
 //   e2e_pp_select_coords   the host has drawn ranks into the raster order of each class and sorted them.  A workgroup looks up which
 //                          of a class's ranks fall into its own [offset, offset + count); without any it leaves before it reads a
-//                          voxel.  Otherwise it recomputes the rank of its matching voxels (ballot + popcount inside a wave, wave
-//                          totals through LDS) and every voxel whose rank was drawn writes its (i, j, k) into the row of the draw
+//                          voxel.  Otherwise it recomputes the rank of its matching voxels and every voxel whose rank was drawn
+//                          writes its (i, j, k) into the row of the draw
 // Every output row has exactly one writer and nothing is accumulated with atomics: the same bits on every run.  The volume is read
 // once per pass whatever K is; all indices, offsets and counts are 64-bit.
-#include "e2e_common.h"
+#include "e2e_rank.h"
 
 namespace {
 
-constexpr int SEL_THREADS = 256, SEL_ITERS = 16;
-constexpr int SEL_CHUNK = SEL_THREADS * SEL_ITERS;             // voxels per workgroup; wave w of pass `it` owns 64 consecutive ones
+namespace rk = e2e::rank;
+
 constexpr int SEL_MAX_CLASSES = 64;                            // one lane per class holds its count
-constexpr long long SEL_MAX_BLOCKS = (1ll << 24) - 1;          // grid limit of a 256-thread launch: 2^36 - 4096 voxels
-constexpr int SCAN_STEP = 256;                                 // chunks per iteration of the offset scan
 
 struct SelClasses { float c[SEL_MAX_CLASSES]; };
 struct SelOffsets { long long o[SEL_MAX_CLASSES + 1]; };       // class k's ranks, slots and output rows are [o[k], o[k + 1])
 
-// voxel base + it * 256 + thread; NaN (equal to no class) behind the end of the volume
-__device__ __forceinline__ void sel_load(const float* __restrict__ seg, long long n, long long base, float v[SEL_ITERS]) {
-#pragma unroll
-  for (int it = 0; it < SEL_ITERS; ++it) {
-    const long long i = base + (long long)(it * SEL_THREADS + (int)threadIdx.x);
-    v[it] = i < n ? seg[i] : __builtin_nanf("");
-  }
-}
+struct IsClass {
+  float c;
+  __device__ __forceinline__ bool operator()(float v) const { return v == c; }
+};
 
 // counts[k * nb + chunk]
-__global__ __launch_bounds__(SEL_THREADS) void pp_select_count_kernel(const float* __restrict__ seg, long long n, SelClasses cls, int K,
+__global__ __launch_bounds__(rk::THREADS) void pp_select_count_kernel(const float* __restrict__ seg, long long n, SelClasses cls, int K,
                                                                       long long nb, unsigned* __restrict__ counts) {
   const long long blk = blockIdx.x;
-  float v[SEL_ITERS];
-  sel_load(seg, n, blk * SEL_CHUNK, v);
+  float v[rk::ITERS];
+  rk::load_chunk(seg, n, blk * rk::CHUNK, v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned mine = 0u;                                          // lane k: this wave's voxels of class k
   for (int k = 0; k < K; ++k) {
-    const float c = cls.c[k];
-    unsigned tot = 0u;
-#pragma unroll
-    for (int it = 0; it < SEL_ITERS; ++it) tot += (unsigned)__popcll(__ballot(v[it] == c));
+    const unsigned tot = rk::wave_matches(v, IsClass{cls.c[k]});
     if (lane == k) mine = tot;
   }
-  __shared__ unsigned sh[SEL_THREADS / 64][SEL_MAX_CLASSES];
+  __shared__ unsigned sh[rk::WAVES][SEL_MAX_CLASSES];
   sh[wave][lane] = mine;
   __syncthreads();
   const int t = threadIdx.x;
   if (t < K) counts[(long long)t * nb + blk] = sh[0][t] + sh[1][t] + sh[2][t] + sh[3][t];
-}
-
-// inclusive sum over the lanes of a wave
-__device__ __forceinline__ unsigned long long wave_scan_u64(unsigned long long x, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  return x;
-}
-
-// one workgroup per class: offsets[k * nb + chunk] = number of the class's voxels in front of the chunk, totals[k] = all of them
-__global__ __launch_bounds__(SCAN_STEP) void pp_select_scan_kernel(const unsigned* __restrict__ counts, unsigned long long* __restrict__ offsets,
-                                                                   long long nb, long long* __restrict__ totals) {
-  const unsigned* c = counts + (long long)blockIdx.x * nb;
-  unsigned long long* o = offsets + (long long)blockIdx.x * nb;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ unsigned long long wsum[SCAN_STEP / 64];
-  unsigned long long carry = 0ull;
-  for (long long b0 = 0; b0 < nb; b0 += SCAN_STEP) {
-    const long long b = b0 + threadIdx.x;
-    const unsigned long long x = b < nb ? (unsigned long long)c[b] : 0ull;
-    const unsigned long long inc = wave_scan_u64(x, lane);
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0ull, all = 0ull;
-#pragma unroll
-    for (int w = 0; w < SCAN_STEP / 64; ++w) {
-      const unsigned long long s = wsum[w];
-      before += w < wave ? s : 0ull;
-      all += s;
-    }
-    if (b < nb) o[b] = carry + before + inc - x;
-    carry += all;
-    __syncthreads();                                           // wsum is rewritten by the next step
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = (long long)carry;
 }
 
 // first p in [lo, hi) with a[p] >= x, or hi
@@ -103,7 +57,7 @@ __device__ __forceinline__ long long sel_lower_bound(const long long* __restrict
   return lo;
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void pp_select_coords_kernel(const float* __restrict__ seg, long long n, long long HW, long long W,
+__global__ __launch_bounds__(rk::THREADS) void pp_select_coords_kernel(const float* __restrict__ seg, long long n, long long HW, long long W,
                                                                        SelClasses cls, SelOffsets off, int K, long long nb,
                                                                        const unsigned* __restrict__ counts,
                                                                        const unsigned long long* __restrict__ offsets,
@@ -112,7 +66,7 @@ __global__ __launch_bounds__(SEL_THREADS) void pp_select_coords_kernel(const flo
   const long long blk = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   __shared__ long long p_lo[SEL_MAX_CLASSES], p_hi[SEL_MAX_CLASSES], first[SEL_MAX_CLASSES];
-  __shared__ unsigned wtot[SEL_ITERS * (SEL_THREADS / 64)];
+  __shared__ unsigned wtot[rk::ITERS * rk::WAVES];
   __shared__ int any;
   if (t == 0) any = 0;
   __syncthreads();
@@ -129,37 +83,26 @@ __global__ __launch_bounds__(SEL_THREADS) void pp_select_coords_kernel(const flo
   }
   __syncthreads();
   if (any == 0) return;
-  float v[SEL_ITERS];
-  sel_load(seg, n, blk * SEL_CHUNK, v);
+  float v[rk::ITERS];
+  rk::load_chunk(seg, n, blk * rk::CHUNK, v);
   for (int k = 0; k < K; ++k) {
     const long long a = p_lo[k], b = p_hi[k];
     if (b <= a) continue;                                      // (the same for the whole workgroup)
-    const float c = cls.c[k];
-    // matching voxels per (pass, wave), in raster order at wtot[it * 4 + wave]
-    unsigned mine = 0u;
-#pragma unroll
-    for (int it = 0; it < SEL_ITERS; ++it) {
-      const unsigned tot = (unsigned)__popcll(__ballot(v[it] == c));
-      if (lane == it) mine = tot;
-    }
-    if (lane < SEL_ITERS) wtot[lane * (SEL_THREADS / 64) + wave] = mine;
-    __syncthreads();
-    const unsigned long long x = wtot[lane];                   // (64 entries: one per lane)
-    const unsigned long long ex = wave_scan_u64(x, lane) - x;  // lane it * 4 + w: the class's voxels of this chunk in front of (it, w)
+    const IsClass is_class{cls.c[k]};
+    const unsigned ex = rk::matches_before(v, is_class, wtot, lane, wave);
     __syncthreads();                                           // wtot is rewritten for the next class
     const long long row0 = off.o[k], rows = off.o[k + 1] - off.o[k], lo = first[k];
 #pragma unroll
-    for (int it = 0; it < SEL_ITERS; ++it) {
-      const bool m = v[it] == c;
+    for (int it = 0; it < rk::ITERS; ++it) {
+      const bool m = is_class(v[it]);
       const unsigned long long bits = __ballot(m);
-      const unsigned long long base = __shfl(ex, it * (SEL_THREADS / 64) + wave, 64);
+      const long long r = lo + (long long)rk::rank_in_chunk(ex, it, wave, bits, lane);
       if (!m) continue;
-      const long long r = lo + (long long)base + (long long)__popcll(bits & ((1ull << lane) - 1ull));
       const long long p = sel_lower_bound(ranks, a, b, r);
       if (p >= b || ranks[p] != r) continue;
       const long long slot = slots[p];
       if (slot < 0 || slot >= rows) continue;                  // (a slot outside the class's rows: a bad call writes nothing)
-      const long long idx = blk * SEL_CHUNK + (long long)(it * SEL_THREADS + t);
+      const long long idx = blk * rk::CHUNK + (long long)(it * rk::THREADS + t);
       const long long i = idx / HW, rem = idx - i * HW, j = rem / W;
       long long* o = out + (row0 + slot) * 3;
       o[0] = i; o[1] = j; o[2] = rem - j * W;
@@ -167,37 +110,27 @@ __global__ __launch_bounds__(SEL_THREADS) void pp_select_coords_kernel(const flo
   }
 }
 
-inline long long sel_blocks(long long n) { return e2e::cdivll(n, SEL_CHUNK); }
-inline long long sel_counts_bytes(long long nb, int K) { return ((long long)K * nb * 4 + 15) / 16 * 16; }
-
 }  // namespace
 
-extern "C" int e2e_pp_select_chunk(void) { return SEL_CHUNK; }
+extern "C" int e2e_pp_select_chunk(void) { return rk::CHUNK; }
 extern "C" int e2e_pp_select_max_classes(void) { return SEL_MAX_CLASSES; }
 
 extern "C" long long e2e_pp_select_ws_bytes(long long n, int K) {
-  if (n < 1 || K < 1 || K > SEL_MAX_CLASSES || sel_blocks(n) > SEL_MAX_BLOCKS) return 0;
-  const long long nb = sel_blocks(n);
-  return sel_counts_bytes(nb, K) + (long long)K * nb * 8;
+  if (n < 1 || K < 1 || K > SEL_MAX_CLASSES || rk::chunks(n) > rk::MAX_CHUNKS) return 0;
+  return rk::ws_bytes(rk::chunks(n), K);
 }
 
 extern "C" int e2e_pp_select_count(const float* seg, long long n, const float* classes, int K, long long* counts, void* ws, void* stream) {
   E2E_REQUIRE(seg && classes && counts && ws && n > 0, "pp_select_count: bad arguments");
   E2E_REQUIRE(K >= 1 && K <= SEL_MAX_CLASSES, "pp_select_count: %d classes, one call serves 1 .. %d", K, SEL_MAX_CLASSES);
-  const long long nb = sel_blocks(n);
-  if (nb > SEL_MAX_BLOCKS) {
-    e2e::set_error("pp_select_count: %lld voxels are more than the %lld one launch covers", n, SEL_MAX_BLOCKS * SEL_CHUNK);
-    return E2E_ERR_UNSUPPORTED;
-  }
+  if (int e = rk::check_voxels("pp_select_count", n)) return e;
+  const long long nb = rk::chunks(n);
   SelClasses cls = {};
   for (int k = 0; k < K; ++k) cls.c[k] = classes[k];
-  unsigned* cnt = (unsigned*)ws;
-  unsigned long long* offs = (unsigned long long*)((char*)ws + sel_counts_bytes(nb, K));
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(pp_select_count_kernel, dim3((unsigned)nb), dim3(SEL_THREADS), 0, st, seg, n, cls, K, nb, cnt);
+  hipLaunchKernelGGL(pp_select_count_kernel, dim3((unsigned)nb), dim3(rk::THREADS), 0, st, seg, n, cls, K, nb, (unsigned*)ws);
   if (int e = e2e::check_launch("pp_select_count_kernel")) return e;
-  hipLaunchKernelGGL(pp_select_scan_kernel, dim3((unsigned)K), dim3(SCAN_STEP), 0, st, (const unsigned*)cnt, offs, nb, counts);
-  return e2e::check_launch("pp_select_scan_kernel");
+  return rk::launch_scan(ws, nb, K, counts, st);
 }
 
 extern "C" int e2e_pp_select_coords(const float* seg, int D, int H, int W, const float* classes, int K, const long long* ranks,
@@ -205,11 +138,8 @@ extern "C" int e2e_pp_select_coords(const float* seg, int D, int H, int W, const
   E2E_REQUIRE(seg && classes && ranks && slots && class_offsets && out && ws, "pp_select_coords: null pointer");
   E2E_REQUIRE(D > 0 && H > 0 && W > 0, "pp_select_coords: every axis needs at least one voxel (got %d x %d x %d)", D, H, W);
   E2E_REQUIRE(K >= 1 && K <= SEL_MAX_CLASSES, "pp_select_coords: %d classes, one call serves 1 .. %d", K, SEL_MAX_CLASSES);
-  const long long n = (long long)D * H * W, nb = sel_blocks(n);
-  if (nb > SEL_MAX_BLOCKS) {
-    e2e::set_error("pp_select_coords: %lld voxels are more than the %lld one launch covers", n, SEL_MAX_BLOCKS * SEL_CHUNK);
-    return E2E_ERR_UNSUPPORTED;
-  }
+  const long long n = (long long)D * H * W, nb = rk::chunks(n);
+  if (int e = rk::check_voxels("pp_select_coords", n)) return e;
   SelClasses cls = {};
   SelOffsets off = {};
   E2E_REQUIRE(class_offsets[0] >= 0, "pp_select_coords: class_offsets[0] is negative");
@@ -219,9 +149,8 @@ extern "C" int e2e_pp_select_coords(const float* seg, int D, int H, int W, const
   }
   for (int k = 0; k <= SEL_MAX_CLASSES; ++k) off.o[k] = class_offsets[k < K ? k : K];
   if (class_offsets[K] == class_offsets[0]) return E2E_OK;     // nothing was drawn
-  const unsigned* cnt = (const unsigned*)ws;
-  const unsigned long long* offs = (const unsigned long long*)((const char*)ws + sel_counts_bytes(nb, K));
-  hipLaunchKernelGGL(pp_select_coords_kernel, dim3((unsigned)nb), dim3(SEL_THREADS), 0, (hipStream_t)stream, seg, n, (long long)H * W,
-                     (long long)W, cls, off, K, nb, cnt, offs, ranks, slots, out);
+  hipLaunchKernelGGL(pp_select_coords_kernel, dim3((unsigned)nb), dim3(rk::THREADS), 0, (hipStream_t)stream, seg, n, (long long)H * W,
+                     (long long)W, cls, off, K, nb, (const unsigned*)ws, (const unsigned long long*)rk::ws_offsets(ws, nb, K),
+                     ranks, slots, out);
   return e2e::check_launch("pp_select_coords_kernel");
 }

@@ -1,6 +1,6 @@
 // K9: DSFF kernel statistics (gfx950): kernel-L1 magnitudes, exact k-th order statistic, death mask, mask /
 // liveness-bit expansion.  Reference: Masking.kernel_death (core_channel.py:647-666).
-#include "e2e_common.h"
+#include "e2e_select.h"
 
 namespace {
 
@@ -27,15 +27,15 @@ __global__ __launch_bounds__(256) void kernel_l1_kernel(const float* __restrict_
   l1[i] = sd;
 }
 
-// Exact k-th smallest of n non-negative floats: 4-pass 8-bit radix select on the IEEE bit patterns (which order
-// like the values for non-negative floats), one workgroup, wavefront-level histogram via LDS atomics.
+// Exact k-th smallest of n non-negative floats: the radix select of e2e_select.h on the raw bit patterns (which order like the
+// values for non-negative floats), one workgroup, all four passes here: the launch sits inside the training step.
 __global__ __launch_bounds__(1024) void kth_value_kernel(const float* __restrict__ v, int n, int k, float* __restrict__ out) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix, s_k;
   if (threadIdx.x == 0) { s_prefix = 0u; s_k = (unsigned)k; }
-  unsigned mask = 0u;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int sft = 24 - 8 * pass;
+  for (int pass = 0; pass < e2e::select::PASSES; ++pass) {
+    const int sft = e2e::select::pass_shift(pass);
+    const unsigned mask = e2e::select::pass_mask(pass);
     if (threadIdx.x < 256) hist[threadIdx.x] = 0u;
     __syncthreads();
     const unsigned prefix = s_prefix;
@@ -45,17 +45,11 @@ __global__ __launch_bounds__(1024) void kth_value_kernel(const float* __restrict
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      unsigned kk = s_k, cum = 0u;
-      int b = 0;
-      for (; b < 256; ++b) {
-        if (cum + hist[b] > kk) break;
-        cum += hist[b];
-      }
-      if (b > 255) b = 255;
-      s_k = kk - cum;
+      unsigned kk = s_k;
+      const int b = e2e::select::pick_bucket(hist, kk);
+      s_k = kk;
       s_prefix = prefix | ((unsigned)b << sft);
     }
-    mask |= 255u << sft;
     __syncthreads();
   }
   if (threadIdx.x == 0) *out = __uint_as_float(s_prefix);

@@ -5,22 +5,20 @@
 //
 // Shape of the code: every loop's trip count is fixed by the arguments, no workgroup waits on another, atomics are histogram
 // and counter increments on integers only -- so every result, the fp64 sums included, is the same bits on every run.
-#include "e2e_common.h"
+#include "e2e_select.h"
 #include <cmath>
 
 namespace {
 
+namespace sel = e2e::select;
+
 constexpr int MAX_LINE = 960;          // longest axis an EDT pass stages: MAX_LINE * (16 + 1) floats fit 64 KiB of LDS
 constexpr int LDS_FLOATS = 16384;      // 64 KiB
-constexpr int STAT_BLOCKS = 1024;      // most workgroups of a full-volume reduction (fixed by n alone: the sums stay reproducible)
-constexpr int STAT_THREADS = 256;
 
 // ws of e2e_surface_distances_stats
 struct StatsWs {
-  double part[STAT_BLOCKS][2][4];      // per workgroup and direction: count, sum d, max d2, count d <= threshold
-  unsigned hist[4][2][256];            // per select pass and rank: byte histogram of the d2 bit patterns that match the prefix
-  unsigned prefix[2];                  // bits of the rank's order statistic decided so far
-  unsigned long long k[2];             // rank inside the prefix's bucket
+  double part[sel::SWEEP_BLOCKS][2][4];      // per workgroup and direction: count, sum d, max d2, count d <= threshold
+  sel::State<2> select;                      // the two ranks of the concatenated distances, on the d2 bit patterns
 };
 
 // the two membership tests a border is taken of: one label value, or a set of values (bit v of eight words)
@@ -123,12 +121,12 @@ __global__ __launch_bounds__(256) void edt_pass_rows_kernel(float* g, int n, lon
 }
 
 // direction 0: d2 = dt2_b at border(a);  direction 1: d2 = dt2_a at border(b)
-__global__ __launch_bounds__(STAT_THREADS) void stats_partial_kernel(const unsigned char* __restrict__ border_a, const float* __restrict__ dt2_b,
+__global__ __launch_bounds__(sel::SWEEP_THREADS) void stats_partial_kernel(const unsigned char* __restrict__ border_a, const float* __restrict__ dt2_b,
                                                                      const unsigned char* __restrict__ border_b, const float* __restrict__ dt2_a,
                                                                      long long n, double thr, StatsWs* ws) {
-  __shared__ double red[STAT_THREADS][2][4];
+  __shared__ double red[sel::SWEEP_THREADS][2][4];
   double acc[2][4] = {{0., 0., 0., 0.}, {0., 0., 0., 0.}};
-  for (long long i = (long long)blockIdx.x * STAT_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STAT_THREADS) {
+  for (long long i = (long long)blockIdx.x * sel::SWEEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * sel::SWEEP_THREADS) {
 #pragma unroll
     for (int dir = 0; dir < 2; ++dir) {
       if ((dir == 0 ? border_a : border_b)[i]) {
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(STAT_THREADS) void stats_partial_kernel(const unsig
   }
   for (int q = 0; q < 8; ++q) red[threadIdx.x][q >> 2][q & 3] = acc[q >> 2][q & 3];
   __syncthreads();
-  for (int half = STAT_THREADS / 2; half > 0; half >>= 1) {      // a fixed tree: the same association order on every run
+  for (int half = sel::SWEEP_THREADS / 2; half > 0; half >>= 1) {      // a fixed tree: the same association order on every run
     if ((int)threadIdx.x < half) {
       for (int dir = 0; dir < 2; ++dir) {
         red[threadIdx.x][dir][0] += red[threadIdx.x + half][dir][0];
@@ -174,61 +172,24 @@ __global__ void stats_final_kernel(const StatsWs* ws, int nblocks, double* out) 
   out[dir * 4 + 3] = le;
 }
 
-__global__ void select_init_kernel(StatsWs* ws, unsigned long long k0, unsigned long long k1) {
-  if (threadIdx.x == 0) {
-    ws->prefix[0] = ws->prefix[1] = 0u;
-    ws->k[0] = k0;
-    ws->k[1] = k1;
-  }
-}
-
-// One pass of the byte-wise radix select (the scheme of dsff.hip's kth_value_kernel, for two ranks at once and over the
-// concatenation of both directions): histogram of byte (24 - 8 pass) of the d2 bit patterns whose higher bytes equal the prefix.
-// Non-negative floats order like their bit patterns and sqrt is monotone, so the select runs on d2.
-__global__ __launch_bounds__(STAT_THREADS) void select_hist_kernel(const unsigned char* __restrict__ border_a, const float* __restrict__ dt2_b,
-                                                                   const unsigned char* __restrict__ border_b, const float* __restrict__ dt2_a,
-                                                                   long long n, int pass, StatsWs* ws) {
-  __shared__ unsigned hist[2][256];
-  hist[0][threadIdx.x] = 0u;
-  hist[1][threadIdx.x] = 0u;
-  __syncthreads();
-  const int sft = 24 - 8 * pass;
-  const unsigned mask = pass == 0 ? 0u : 0xFFFFFFFFu << (sft + 8);
-  const unsigned p0 = ws->prefix[0], p1 = ws->prefix[1];
-  for (long long i = (long long)blockIdx.x * STAT_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STAT_THREADS) {
+// One sweep of the radix select (e2e_select.h) over the concatenation of both directions.  Non-negative floats order like their bit
+// patterns and sqrt is monotone, so the select runs on the raw bits of d2.
+__global__ __launch_bounds__(sel::SWEEP_THREADS) void select_hist_kernel(const unsigned char* __restrict__ border_a, const float* __restrict__ dt2_b,
+                                                                        const unsigned char* __restrict__ border_b, const float* __restrict__ dt2_a,
+                                                                        long long n, int pass, StatsWs* ws) {
+  __shared__ unsigned bins[2][256];
+  const sel::Sweep<2> sw = sel::sweep_begin(bins, &ws->select, 2);
+  for (long long i = (long long)blockIdx.x * sel::SWEEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * sel::SWEEP_THREADS) {
 #pragma unroll
-    for (int dir = 0; dir < 2; ++dir) {
-      if ((dir == 0 ? border_a : border_b)[i]) {
-        const unsigned key = __float_as_uint((dir == 0 ? dt2_b : dt2_a)[i]);
-        const unsigned byte = (key >> sft) & 255u;
-        if ((key & mask) == p0) atomicAdd(&hist[0][byte], 1u);
-        if ((key & mask) == p1) atomicAdd(&hist[1][byte], 1u);
-      }
-    }
+    for (int dir = 0; dir < 2; ++dir)
+      if ((dir == 0 ? border_a : border_b)[i]) sel::sweep_add(bins, sw, pass, __float_as_uint((dir == 0 ? dt2_b : dt2_a)[i]));
   }
-  __syncthreads();
-  if (hist[0][threadIdx.x]) atomicAdd(&ws->hist[pass][0][threadIdx.x], hist[0][threadIdx.x]);
-  if (hist[1][threadIdx.x]) atomicAdd(&ws->hist[pass][1][threadIdx.x], hist[1][threadIdx.x]);
+  sel::sweep_flush(bins, &ws->select, pass);
 }
 
-// picks the bucket of each rank from the pass's histogram; after the last pass out[8 + r] = sqrt of the rank's d2
-__global__ void select_step_kernel(StatsWs* ws, int pass, double* out) {
-  if (threadIdx.x >= 2) return;
-  const int r = threadIdx.x;
-  const int sft = 24 - 8 * pass;
-  unsigned long long kk = ws->k[r], cum = 0ull;
-  int b = 0;
-  for (; b < 256; ++b) {
-    const unsigned long long h = ws->hist[pass][r][b];
-    if (cum + h > kk) break;
-    cum += h;
-  }
-  if (b > 255) b = 255;
-  ws->k[r] = kk - cum;
-  const unsigned prefix = ws->prefix[r] | ((unsigned)b << sft);
-  ws->prefix[r] = prefix;
-  if (pass == 3) out[8 + r] = sqrt((double)__uint_as_float(prefix));
-}
+struct SqrtOfBits {                    // the distance behind the decided bits of a d2
+  __device__ __forceinline__ double operator()(unsigned bits) const { return sqrt((double)__uint_as_float(bits)); }
+};
 
 bool dims_ok(const char* what, int D, int H, int W) {
   if (D < 1 || H < 1 || W < 1) {
@@ -236,11 +197,6 @@ bool dims_ok(const char* what, int D, int H, int W) {
     return false;
   }
   return true;
-}
-
-int stat_blocks(long long n) {
-  const long long b = e2e::cdivll(n, STAT_THREADS);
-  return (int)(b < STAT_BLOCKS ? b : STAT_BLOCKS);
 }
 
 template <class Member>
@@ -322,15 +278,14 @@ extern "C" int e2e_surface_distances_stats(const unsigned char* border_a, const 
   E2E_REQUIRE(!(threshold != threshold), "surface_distances_stats: threshold is NaN");
   hipStream_t st = (hipStream_t)stream;
   StatsWs* w = (StatsWs*)ws;
-  const int nb = stat_blocks(n);
-  e2e::zero_async(&w->hist[0][0][0], sizeof(w->hist), st);
-  hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(64), 0, st, w, (unsigned long long)rank_lo, (unsigned long long)rank_hi);
-  hipLaunchKernelGGL(stats_partial_kernel, dim3(nb), dim3(STAT_THREADS), 0, st, border_a, dt2_b, border_b, dt2_a, n, threshold, w);
+  const int nb = sel::sweep_blocks(n);
+  sel::start(&w->select, sel::Ranks<2>{{(unsigned long long)rank_lo, (unsigned long long)rank_hi}}, st);
+  hipLaunchKernelGGL(stats_partial_kernel, dim3(nb), dim3(sel::SWEEP_THREADS), 0, st, border_a, dt2_b, border_b, dt2_a, n, threshold, w);
   hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(64), 0, st, w, nb, out);
   if (int rc = e2e::check_launch("stats_kernels")) return rc;
-  for (int pass = 0; pass < 4; ++pass) {
-    hipLaunchKernelGGL(select_hist_kernel, dim3(nb), dim3(STAT_THREADS), 0, st, border_a, dt2_b, border_b, dt2_a, n, pass, w);
-    hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(64), 0, st, w, pass, out);
+  for (int pass = 0; pass < sel::PASSES; ++pass) {
+    hipLaunchKernelGGL(select_hist_kernel, dim3(nb), dim3(sel::SWEEP_THREADS), 0, st, border_a, dt2_b, border_b, dt2_a, n, pass, w);
+    sel::step(&w->select, pass, 2, SqrtOfBits{}, out + 8, st);
   }
   return e2e::check_launch("select_kernels");
 }

@@ -221,6 +221,43 @@ def test_refused_arguments_launch_nothing():
     assert float(dt2.min()) == float(dt2.max()) == -1.0 and int(cnt) == -7 and float(out.max()) == -1.0 and int(ws.max()) == 0
 
 
+def test_two_rank_select_on_hand_made_values():
+    """e2e_surface_distances_stats on 600 voxels, both borders all ones, so the select sees all 1200 squared distances: ties of 300,
+    400 and 54 values, 256 + 64 values that differ in the lowest byte of their bit pattern alone (with one carry into the third
+    byte) and one value per top byte 0x01 .. 0x7e.  The order statistics are np.sqrt(np.sort(.).astype(float64))[rank], exactly.
+    Counts, maxima and the counts within the threshold are exact too; a sum of m non-negative fp64 terms is within (m - 1) 2^-53
+    of the true sum in any order, so the device's and numpy's differ by at most 2 * 599 * 2^-53 relative."""
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    n, thr = 600, 1.75
+    words = np.concatenate([np.zeros(300, np.uint32), np.full(400, 0x3FC00000, np.uint32),
+                            0x40490F00 + np.arange(256, dtype=np.uint32), 0x40491000 + np.arange(64, dtype=np.uint32),
+                            (np.arange(1, 0x7F, dtype=np.uint32) << 24) | 0x123456, np.full(54, 0x7149F2CA, np.uint32)]).astype(np.uint32)
+    assert words.size == 2 * n
+    d2 = np.random.RandomState(7).permutation(words).view(np.float32).reshape(2, n)     # [0]: dt2_b (direction 0), [1]: dt2_a
+    want = np.sqrt(np.sort(d2.reshape(-1)).astype(np.float64))
+    bits = np.sort(d2.reshape(-1)).view(np.uint32)
+    at = lambda w: int(np.flatnonzero(bits == w)[0])
+    low, carry, tie = at(0x40490F0A), at(0x40490FFF), at(0x3FC00000) + 100
+    assert 0 < (bits[low] ^ bits[low + 1]) < 256 and bits[carry + 1] == 0x40491000 and bits[tie] == bits[tie + 1] == 0x3FC00000
+    dev = torch.from_numpy(d2).cuda()
+    ones = torch.ones(n, dtype=torch.uint8, device="cuda")
+    out = torch.empty(10, dtype=torch.float64, device="cuda")
+    ws = torch.empty(L.surface_distances_ws_bytes(), dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    d = np.sqrt(d2.astype(np.float64))
+    assert np.abs(d - thr).min() > 1e-3
+    for lo, hi in ((low, low), (800, 800), (low, low + 1), (carry, carry + 1), (0, 2 * n - 1), (tie, tie + 1), (299, 300)):
+        L.surface_distances_stats(ones.data_ptr(), dev[0].data_ptr(), ones.data_ptr(), dev[1].data_ptr(), n, thr, lo, hi, out.data_ptr(),
+                                  ws.data_ptr(), st)
+        o = out.cpu().numpy()
+        print(lo, hi, o.tolist())
+        assert o[8] == want[lo] and o[9] == want[hi], (lo, hi, o[8], want[lo], o[9], want[hi])
+        for dir in range(2):
+            assert o[4 * dir] == n and o[4 * dir + 2] == d[dir].max() and o[4 * dir + 3] == (d[dir] <= thr).sum(), (dir, o.tolist())
+            assert _rel(o[4 * dir + 1], d[dir].sum()) <= 2 * (n - 1) * 2.0 ** -53, (dir, o[4 * dir + 1], d[dir].sum())
+
+
 def test_validate_scores_the_advanced_metrics(tmp_path):
     """validate(advanced_metrics=True) writes the three default_advanced_metrics (and NSD with a tolerance) into every label's dict
     of summary.json, scored under properties['itk_spacing'][::-1]; the values are the restatement's on the exported volumes.  Without
