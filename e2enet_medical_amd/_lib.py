@@ -175,6 +175,8 @@ SIGNATURES = {
     "e2e_ensemble_accumulate": (I, [P, P, LL, I, I, P]),
     "e2e_export_argmax_u8": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, I, I, I, P, I, P]),
     "e2e_resample_linear": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, I, P]),
+    "e2e_softmax_to_f16": (I, [P, P, I, LL, I, I, I, LL, LL, LL, P]),
+    "e2e_merge_softmax_f16": (I, [P, I, I, I, I, I, P, I, I, I, I, I, I, P, I, P, P]),
     "e2e_aug_spatial": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, P]),
     "e2e_aug_bspline_prefilter_axis": (I, [P, P, I, I, I, I, I, P]),
     "e2e_aug_stats_ws_bytes": (LL, [I]),
@@ -269,7 +271,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 22          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 23          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -91,15 +91,41 @@ def resample_softmax(softmax: torch.Tensor, new_shape: Sequence[int], transpose_
     return out
 
 
+def softmax_to_f16(softmax: torch.Tensor, dims: Sequence[int], strides: Sequence[int]) -> torch.Tensor:
+    """Contiguous device fp16 [K] + dims of a device fp32 softmax read through ``strides`` (those of ``softmax.transpose(...)``): the
+    bits of ``softmax.transpose(...).astype(np.float16)`` (segmentation_export.py:118), rounded on the device."""
+    assert softmax.is_cuda and softmax.dtype == torch.float32 and softmax.dim() == 4
+    k = softmax.shape[0]
+    out = torch.empty([k] + [int(v) for v in dims], dtype=torch.float16, device=softmax.device)
+    lib().softmax_to_f16(softmax.data_ptr(), out.data_ptr(), k, int(softmax.stride(0)), int(dims[0]), int(dims[1]), int(dims[2]),
+                         int(strides[0]), int(strides[1]), int(strides[2]), _stream())
+    return out
+
+
+def save_softmax_npz(softmax_f16: torch.Tensor, resampled_npz_fname: str, properties_dict: dict,
+                     region_class_order: Optional[Sequence[int]] = None):
+    """``<case>.npz`` (key ``softmax``, fp16) and ``<case>.pkl`` as segmentation_export.py:117-122 leaves them for the ensembling
+    step (inference/ensemble_predictions.py); the pickle names ``regions_class_order`` when there is one."""
+    np.savez_compressed(resampled_npz_fname, softmax=softmax_f16.cpu().numpy())
+    if region_class_order is not None:
+        properties_dict = dict(properties_dict, regions_class_order=region_class_order)
+    with open(resampled_npz_fname[:-4] + ".pkl", 'wb') as f:
+        pickle.dump(properties_dict, f)
+
+
 def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_backward: Optional[Sequence[int]] = None,
                         region_class_order: Optional[Sequence[int]] = None, force_separate_z: Optional[bool] = None,
-                        order: int = 1, interpolation_order_z: int = 0, postprocessing=None) -> np.ndarray:
+                        order: int = 1, interpolation_order_z: int = 0, postprocessing=None,
+                        resampled_npz_fname: Optional[str] = None) -> np.ndarray:
     """uint8 label volume in the ORIGINAL (uncropped) geometry from a device softmax [K, X, Y, Z]
     (reference predict.py:298-301 + segmentation_export.py:73-136).
 
     ``postprocessing``: ``(for_which_classes, min_valid_object_sizes or None)`` as ``load_postprocessing`` returns them; all but the
     largest connected component of those classes is then removed (reference predict.py:339-352, load_remove_save) on the device
-    label volume, before its one download; ``volume_per_voxel`` is the product of ``properties_dict['itk_spacing']``."""
+    label volume, before its one download; ``volume_per_voxel`` is the product of ``properties_dict['itk_spacing']``.
+
+    ``resampled_npz_fname`` (the reference's argument of that name): the probabilities the labels are taken from -- on the case's own
+    grid, in its own axis order -- are also stored there as fp16, with the properties beside them (``save_softmax_npz``)."""
     assert softmax.is_cuda and softmax.dtype == torch.float32 and softmax.dim() == 4 and softmax.is_contiguous()
     k = softmax.shape[0]
     tb = [0, 1, 2] if transpose_backward is None else [int(i) for i in transpose_backward]
@@ -115,6 +141,8 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
         softmax = resample_softmax(softmax, after_crop, tb, lowres)
         dims = [int(v) for v in after_crop]
         strides = [int(softmax.stride(1 + i)) for i in range(3)]
+    if resampled_npz_fname is not None:
+        save_softmax_npz(softmax_to_f16(softmax, dims, strides), resampled_npz_fname, properties_dict, region_class_order)
     bbox = properties_dict.get('crop_bbox')
     if bbox is not None:
         out_shape = tuple(int(v) for v in properties_dict.get('original_size_of_raw_data'))
@@ -139,18 +167,20 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
 
 def predict_cases(trainer, params: Sequence[dict], preprocessed: Iterable[Tuple[str, Tuple[np.ndarray, dict]]],
                   writer: Callable[[np.ndarray, str, dict], None], do_tta: bool = True, step_size: float = 0.5,
-                  all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None):
+                  all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None, save_npz: bool = False):
     """The per-case loop of reference predict_cases (predict.py:273-331) on preprocessed cases
     ``(output_filename, (data [C,X,Y,Z], properties_dict))``; ``writer(seg_uint8, output_filename, properties_dict)``
     stores the label volume (the reference's SimpleITK NIfTI writer, segmentation_export.py:144-148, is host tooling).
-    ``postprocessing``: see ``export_segmentation``."""
+    ``postprocessing``: see ``export_segmentation``.  ``save_npz``: ``<case>.npz`` and ``<case>.pkl`` beside every label file
+    (predict.py:303-304), what ``inference/ensemble_predictions.py`` merges."""
     done = []
     for output_filename, (d, dct) in preprocessed:
         if isinstance(d, str):
             d = np.load(d)
         softmax = predict_case_ensemble(trainer, params, d, do_tta, step_size, all_in_gpu, mixed_precision)
         tb = trainer.plans.get('transpose_backward') if trainer.plans.get('transpose_forward') is not None else None
-        seg = export_segmentation(softmax, dct, tb, getattr(trainer, 'regions_class_order', None), postprocessing=postprocessing)
+        seg = export_segmentation(softmax, dct, tb, getattr(trainer, 'regions_class_order', None), postprocessing=postprocessing,
+                                  resampled_npz_fname=output_filename[:-7] + ".npz" if save_npz else None)
         writer(seg, output_filename, dct)
         done.append(output_filename)
     return done
@@ -208,7 +238,8 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.
     The per-case work is ``predict_cases`` above (softmax resident in HBM).  ``num_threads_*`` are accepted and unused: there are
-    no preprocessing / export worker processes here.  Unless ``disable_postprocessing``, ``<model>/postprocessing.json`` is copied to
+    no preprocessing / export worker processes here.  ``save_npz`` (``simple_predict -z``): the class probabilities of every case are
+    stored beside its label file for ``inference/ensemble_predictions.py`` (``save_softmax_npz``).  Unless ``disable_postprocessing``, ``<model>/postprocessing.json`` is copied to
     ``output_folder`` and applied to every case on the device (reference :337-356); when the file is missing the reference's warning
     is printed and the raw label maps are written.  A folder of raw cases (``<case>_XXXX.nii.gz``) is read through
     ``reader(list_of_files) -> (data [C, X, Y, Z], properties)`` -- default: the reference's SimpleITK loader -- and preprocessed on
@@ -231,7 +262,8 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     case_ids = case_ids[part_id::num_parts]
     output_files = [os.path.join(output_folder, c + ".nii.gz") for c in case_ids]
     if not overwrite_existing:
-        keep = [i for i, o in enumerate(output_files) if not (os.path.isfile(o) or os.path.isfile(o[:-7] + ".npy"))]
+        keep = [i for i, o in enumerate(output_files) if not (os.path.isfile(o) or os.path.isfile(o[:-7] + ".npy"))
+                or (save_npz and not os.path.isfile(o[:-7] + ".npz"))]          # (predict.py:233-234)
         case_ids, output_files = [case_ids[i] for i in keep], [output_files[i] for i in keep]
     print("number of cases that still need to be predicted:", len(case_ids))
     if not case_ids:
@@ -265,4 +297,5 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
             d = np.asarray(d)[:expected_num_modalities]          # (preprocessed training cases carry their labels as a last channel)
             yield out, (d, props)
     return predict_cases(trainer, params, cases(), writer if writer is not None else nifti_writer(), do_tta=tta,
-                         step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision, postprocessing=postprocessing)
+                         step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision, postprocessing=postprocessing,
+                         save_npz=save_npz)

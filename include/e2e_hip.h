@@ -484,6 +484,27 @@ int e2e_export_argmax_u8(const float* probs, unsigned char* seg, int K, long lon
 int e2e_resample_linear(const float* src, float* dst, int K, long long kstride, int A, int B, int C, long long sa,
                         long long sb, long long sc, int OA, int OB, int OC, int lowres_axis, void* stream);
 
+/* ---- N2: ensembling of saved class probabilities (csrc/ensemble.hip) -------------------------------------------
+ * Replaces: `seg_old_spacing.astype(np.float16)` of save_segmentation_nifti_from_softmax (e2enet/inference/
+ * segmentation_export.py:117-122, the `-z` export) and merge_files (e2enet/inference/ensemble_predictions.py:28-30: np.vstack of N
+ * fp16 volumes, np.mean over them) followed by the argmax / region thresholds and the crop-box placement of
+ * segmentation_export.py:124-140.  fp16 volumes are passed as void* (IEEE binary16).
+ *   softmax_to_f16: out (contiguous [K, A, B, C], fp16) = probs read as e2e_export_argmax_u8 reads it (class stride kstride, voxel
+ *     (a,b,c) of the transposed frame at a*sa + b*sb + c*sc), each value rounded to nearest even, fp16 subnormals included:
+ *     the bits of softmax.transpose(...).astype(np.float16).
+ *   merge_softmax_f16: srcs is a HOST array of n_src (1 .. E2E_MERGE_MAX_SOURCES) device pointers, read before the call returns
+ *     and carried into the launch by value; each source is a contiguous fp16 [K, A, B, C].  Per class and voxel: fp32 sum of the
+ *     sources in source order, one fp32 division by n_src, one rounding to fp16 -- what numpy forms for np.mean over fp16 input.
+ *     Every decision is taken on that fp16 mean: without regions the first maximum over k (a NaN counts as a maximum), with
+ *     regions (device int[n_regions], n_regions <= K) the last region whose mean is > 0.5, else 0.  seg (zero-initialised uint8
+ *     [OA, OB, OC]) receives the label at (a0+a, b0+b, c0+c), clipped to its size; mean ([K, A, B, C] fp16) receives the mean.
+ *     Either of seg and mean may be NULL, not both.  A*B*C need not be a multiple of 8 (the width of one lane's load).           */
+#define E2E_MERGE_MAX_SOURCES 16
+int e2e_softmax_to_f16(const float* probs, void* out, int K, long long kstride, int A, int B, int C, long long sa, long long sb,
+                       long long sc, void* stream);
+int e2e_merge_softmax_f16(const void* const* srcs, int n_src, int K, int A, int B, int C, unsigned char* seg, int OA, int OB,
+                          int OC, int a0, int b0, int c0, const int* regions, int n_regions, void* mean, void* stream);
+
 
 /* ---- K1d: dense 1x3x3 convolution on the bf16 matrix pipe (fp32-exact three-piece operands) --------------------------
  * Same operator as e2e_conv133_fwd / e2e_conv133_dgrad (unetpp_d.py:45-59, :453-478, :93/:108 and their autograd) for layers
