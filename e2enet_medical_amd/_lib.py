@@ -95,6 +95,13 @@ class RangeJob(C.Structure):
     _fields_ = [("src", RangeSrc * 3), ("out", C.c_void_p)]
 
 
+class LoaderRec(C.Structure):
+    """e2e_loader_rec_t"""
+    _fields_ = [("src", C.c_void_p), ("d", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("off_d", C.c_int), ("off_h", C.c_int), ("off_w", C.c_int)]
+
+
+assert C.sizeof(LoaderRec) == 32
 assert C.sizeof(MmPackJob) == 56 and C.sizeof(RangeSrc) == 56 and C.sizeof(RangeJob) == 176
 assert C.sizeof(InChan) == 48 and C.sizeof(OutChan) == 24 and C.sizeof(ParamEntry) == 40 and C.sizeof(SparsePackJob) == 72 and C.sizeof(InSumChan) == 72
 
@@ -226,6 +233,8 @@ SIGNATURES = {
     "e2e_fingerprint_stats_max_ranks": (I, []),
     "e2e_fingerprint_stats_ws_bytes": (LL, []),
     "e2e_fingerprint_stats": (I, [P, LL, P, I, P, P, P]),
+    "e2e_loader_crop_max_batch": (I, []),
+    "e2e_loader_crop": (I, [P, I, I, I, I, I, P, P, I, F, F, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
@@ -233,7 +242,8 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
               "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes",
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
-              "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups"}
+              "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
+              "e2e_loader_crop_max_batch"}
 
 
 class E2EError(RuntimeError):
@@ -271,7 +281,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 23          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 24          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -7,7 +7,8 @@ engine: the same argv (incl. the sparse flags of ``add_sparse_args``), the same 
 Differences, all stated: ``--fp32`` / mixed precision is accepted and ignored (fp32 results); ``-c`` restores the DSFF masks and the
 optimizer state from the checkpoint (the reference re-draws the masks before loading); ``--base_num_features``
 is an extension (the reference hard-codes 48, nnUNetTrainer_simple.py:296); ``--synthetic_data`` trains on seeded noise when no
-preprocessed data exists (benchmarks / smoke tests); ``--validation_only`` really validates (the reference's call is commented out,
+preprocessed data exists (benchmarks / smoke tests); ``--resident_data GIB`` keeps the preprocessed cases on the device and cuts the
+training batches there; ``--validation_only`` really validates (the reference's call is commented out,
 :200-208); ``--find_lr`` and the 3d_lowres cascade hand-over are outside the engine."""
 import argparse
 
@@ -60,6 +61,10 @@ def build_parser():
                              'improves the Dice and write postprocessing.json (on the device; the reference always does this)')
     parser.add_argument('--synthetic_data', action='store_true', default=False,
                         help='train on seeded Gaussian noise / random labels when no preprocessed data exists')
+    parser.add_argument('--resident_data', type=float, required=False, default=None, metavar='GIB',
+                        help='keep up to GIB GiB of preprocessed cases on the device and cut every training batch there with one '
+                             'kernel launch (negative: no limit; 0: stage every case, still crop and pad on the device); '
+                             'default: the host loader')
     add_sparse_args(parser)
     return parser
 
@@ -109,6 +114,7 @@ def main(argv=None):
                             max_num_epochs=args.max_num_epochs, num_batches_per_epoch=args.num_batches_per_epoch, args=args)
     trainer.base_num_features_override = args.base_num_features
     trainer.synthetic_data = bool(args.synthetic_data)
+    trainer.resident_data_gib = args.resident_data
     if args.disable_saving:
         trainer.save_final_checkpoint = False
         trainer.save_best_checkpoint = False

@@ -102,6 +102,9 @@ class nnUNetTrainer_simple(object):
             if dataset_directory is not None and os.path.isdir(dataset_directory) else None
         self.folder_with_preprocessed_data = None
         self.dl_tr = self.dl_val = None
+        # GiB of preprocessed cases to keep on the device (training/dataloading/resident_loading.py): None is the host loader,
+        # a negative number no limit, 0 stages every case but still crops and pads on the device
+        self.resident_data_gib = None
         self.num_input_channels = self.num_classes = self.net_pool_per_axis = self.patch_size = self.batch_size = \
             self.threeD = self.base_num_features = self.intensity_properties = self.normalization_schemes = \
             self.net_num_pool_op_kernel_sizes = self.net_conv_kernel_sizes = None
@@ -649,6 +652,7 @@ class nnUNetTrainer_simple(object):
                 os.makedirs(self.output_folder_base, exist_ok=True)
                 with open(join(self.output_folder_base, "plans.pkl"), 'wb') as f:
                     pickle.dump(self.plans, f)
+        residency_logged = False
         while self.epoch < self.max_num_epochs:
             self.print_to_log_file("\nepoch: ", self.epoch)
             epoch_start_time = time()
@@ -661,6 +665,9 @@ class nnUNetTrainer_simple(object):
                 val_losses = [self.run_iteration(self.val_gen, False, True) for _ in range(self.num_val_batches_per_epoch)]
                 self.all_val_losses.append(self._rank_mean(np.mean(val_losses)))
                 self.print_to_log_file("validation loss: %.4f" % self.all_val_losses[-1])
+            if not residency_logged and hasattr(self.dl_tr, "residency_report"):
+                residency_logged = True
+                self.print_to_log_file("train " + self.dl_tr.residency_report())
             self.update_train_loss_MA()
             continue_training = self.on_epoch_end()
             if not continue_training:
@@ -1113,6 +1120,19 @@ class nnUNetTrainer_simple(object):
         from ..dataloading.dataset_loading import DataLoader3D
         self.load_dataset()
         self.do_split()
+        if self.resident_data_gib is not None:
+            from ..dataloading.resident_loading import DeviceCaseCache, ResidentDataLoader3D
+            gib = float(self.resident_data_gib)
+            # one cache for both loaders: fold 'all' trains and validates on the same cases
+            cache = DeviceCaseCache(None if gib < 0 else int(gib * 2 ** 30), torch.device("cuda", torch.cuda.current_device())
+                                    if torch.cuda.is_available() else "cuda")
+            dl_tr = ResidentDataLoader3D(self.dataset_tr, self.basic_generator_patch_size, self.patch_size, self.batch_size, False,
+                                         oversample_foreground_percent=self.oversample_foreground_percent, pad_mode="constant",
+                                         pad_sides=self.pad_all_sides, memmap_mode='r', cache=cache)
+            dl_val = ResidentDataLoader3D(self.dataset_val, self.patch_size, self.patch_size, self.batch_size, False,
+                                          oversample_foreground_percent=self.oversample_foreground_percent, pad_mode="constant",
+                                          pad_sides=self.pad_all_sides, memmap_mode='r', cache=cache)
+            return dl_tr, dl_val
         dl_tr = DataLoader3D(self.dataset_tr, self.basic_generator_patch_size, self.patch_size, self.batch_size, False,
                              oversample_foreground_percent=self.oversample_foreground_percent, pad_mode="constant",
                              pad_sides=self.pad_all_sides, memmap_mode='r')

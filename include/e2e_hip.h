@@ -731,6 +731,29 @@ long long e2e_fingerprint_stats_ws_bytes(void);
 int e2e_fingerprint_stats(const float* x, long long n, const long long* ranks, int num_ranks, double* out, void* ws,
                           void* stream);
 
+/* ---- N3: the training loader's crop, out of cases that live on the device ----------------------------------------------
+ * Replaces: e2enet/training/dataloading/dataset_loading.py:283-372 (DataLoader3D.generate_train_batch: per sample np.copy of the
+ * valid box, np.pad of the data and np.pad of the seg with -1, into a host batch that is then uploaded).  One launch cuts a whole
+ * batch.  recs: B records on the HOST, read before the call returns, 1 <= B <= loader_crop_max_batch.  A record names a source box
+ * src = [C + 1, d, h, w] fp32 on the device, contiguous, the seg as its last channel (a whole preprocessed case, or any box cut
+ * out of one), and the box coordinates off_d, off_h, off_w of patch voxel 0, 0, 0; they may be negative or beyond the extent
+ * (-2^30 .. 2^30).  out_data [B, C, pd, ph, pw] and out_seg [B, 1, pd, ph, pw], fp32, contiguous; every patch axis is at most 2^21
+ * and the patch has fewer than 2^31 voxels.  With q = off + p per axis:
+ *   out_seg: the source seg where q lies in the box on all three axes, seg_fill elsewhere;
+ *   out_data, data_mode 0 (np.pad 'constant'): the source value inside the box, data_fill outside;
+ *   out_data, data_mode 1 (np.pad 'edge'): the source value at q clamped per axis to [0, extent - 1].
+ * Values are copied as 32-bit words: every bit of a NaN or of -0.0 comes out as it went in.  Source offsets are 64-bit (a source
+ * may hold more than 2^31 elements).  One writer per element and no atomics: the same bits on every run.  Refused: B outside its
+ * range, a data_mode other than 0 and 1, an extent of a box or of the patch below 1, a null pointer.                          */
+typedef struct {
+  const float* src;
+  int d, h, w;
+  int off_d, off_h, off_w;
+} e2e_loader_rec_t;
+int e2e_loader_crop_max_batch(void);
+int e2e_loader_crop(const e2e_loader_rec_t* recs, int B, int C, int pd, int ph, int pw, float* out_data, float* out_seg,
+                    int data_mode, float data_fill, float seg_fill, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
