@@ -4,13 +4,19 @@
 //
 //   y[n,o,kd*d+i,kh*h+j,kw*w+k] = sum_c z[n,c,d,h,w] * W[c,o,i,j,k],   z = lrelu(scale*x + shift)
 //
-// The op is a per-voxel [Cin] x [Cin, Cout*KT] product; its input tensor is small next to its output (1/8 of
-// the voxels), so forward and data gradient are written in gather form straight from global memory (the
-// re-reads of z / dy are L2 hits) with the weights as wave-uniform scalars and the DSFF liveness bits walked
-// with scalar bit ops.  The dense weight gradient (huge reduction over voxels) runs on the fp32 MFMA.
+// The op is a per-voxel [Cin] x [Cin, Cout*KT] product.  Three families of kernels, chosen by the plans at the end of the file:
+//   * any kernel in {1,2}^3, small planes: forward and data gradient in gather form straight from global memory (the re-reads
+//     of z / dy are L2 hits, weights as wave-uniform scalars, DSFF liveness bits walked with scalar bit ops), weight gradient v1
+//     on the fp32 MFMA;
+//   * kw == 2, even W: the three GEMMs on the matrix pipe with split fp32-exact operands (*_bf3_kernel: fp16 two-piece or bf16
+//     three-piece), the default;
+//   * the same shapes on fp32 matrix instructions (convT_wgrad_v2, convT_dgrad_v3): E2E_CT_BF3=0, and the data gradient where
+//     W is no multiple of 32.
+// The gradient GEMMs take their dy addresses from DyTile.
 #include "e2e_common.h"
 #include "e2e_split.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -175,8 +181,8 @@ __global__ __launch_bounds__(256) void convT_dgrad_kernel(const float* __restric
 // the voxel: it lives inside the MFMA K dimension and in the loop, so no cross-lane reduction is needed.
 // Partial sums per chunk go to a slab; a second kernel adds the slabs in fixed order (deterministic).
 
-constexpr int WG_TPX = 64;                 // voxels staged per step
-constexpr int WG_ZS = WG_TPX + 2;          // channel stride in LDS, == 2 (mod 32): conflict-free A/B fragment reads
+constexpr int WG_TV = 64;                 // voxels staged per step
+constexpr int WG_ZS = WG_TV + 2;          // channel stride in LDS, == 2 (mod 32): conflict-free A/B fragment reads
 
 template <int KT>
 __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ scale,
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
   const int cblocks = e2e::cdiv(Cin, 32);
   const int cb = blockIdx.y % cblocks, ob = blockIdx.y / cblocks;
   const long long spatial = (long long)D * H * W;
-  const long long tiles_per_n = e2e::cdivll(spatial, WG_TPX);
+  const long long tiles_per_n = e2e::cdivll(spatial, WG_TV);
   const long long total_tiles = tiles_per_n * B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ch = wave & 1, oh = wave >> 1;
@@ -204,10 +210,10 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
     const long long tile = (long long)chunk * tiles_per_chunk + ti;
     if (tile >= total_tiles) break;
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TPX;
+    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TV;
     // stage z[32 c][64 v]
-    for (int idx = tid; idx < 32 * WG_TPX; idx += 256) {
-      const int cl = idx / WG_TPX, pv = idx - cl * WG_TPX;
+    for (int idx = tid; idx < 32 * WG_TV; idx += 256) {
+      const int cl = idx / WG_TV, pv = idx - cl * WG_TV;
       const int c = cb * 32 + cl;
       const long long vi = vbase + pv;
       float val = 0.f;
@@ -218,9 +224,9 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
       zs[cl * WG_ZS + pv] = val;
     }
     // stage dy[32 o][KT][64 v]
-    for (int idx = tid; idx < 32 * KT * WG_TPX; idx += 256) {
-      const int pv = idx % WG_TPX;
-      const int rest = idx / WG_TPX;
+    for (int idx = tid; idx < 32 * KT * WG_TV; idx += 256) {
+      const int pv = idx % WG_TV;
+      const int rest = idx / WG_TV;
       const int t = rest % KT, ol = rest / KT;
       const int o = ob * 32 + ol;
       const long long vi = vbase + pv;
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
     const float* ap = zs + (ch * 16 + li) * WG_ZS + lk;
     const float* bp = ds + ((oh * 16 + li) * KT) * WG_ZS + lk;
 #pragma unroll 4
-    for (int k0 = 0; k0 < WG_TPX; k0 += 4) {
+    for (int k0 = 0; k0 < WG_TV; k0 += 4) {
       const float a = ap[k0];
 #pragma unroll
       for (int t = 0; t < KT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * WG_ZS + k0], acc[t], 0, 0, 0);
@@ -258,6 +264,71 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const float* __restric
     }
 }
 
+// ---- where the dy of one tile lives (kw == 2, even W): every matrix-pipe kernel that reads dy asks here -------------------
+// A tile is TV consecutive input voxels of one sample, starting at vbase.  Its dy is fetched as aligned float4 "units": unit
+// (rr, vp) of an output channel = output row rr = i * kh + j of the KDH = kd * kh rows an input row produces, voxel pair vp.
+// The float4 holds taps (rr, k = 0), (rr, k = 1) of voxel 2 vp and then of voxel 2 vp + 1.  A channel has UPC units, vp
+// fastest, so consecutive units are consecutive float4 of one output row.
+template <int KDH, int TV>
+struct DyTile {
+  static constexpr int KT = 2 * KDH;
+  static constexpr int VP = TV / 2;
+  static constexpr int UPC = KDH * VP;
+  struct Unit { int rr, vp; };
+  int Cout, H, W, kd, kh, Ho, Wo;
+  long long spatial, ospatial;                           // voxels of an input / output channel
+
+  __device__ __forceinline__ DyTile(int Cout_, int D, int H_, int W_, int kd_, int kh_)
+      : Cout(Cout_), H(H_), W(W_), kd(kd_), kh(kh_), Ho(H_ * kh_), Wo(W_ * 2), spatial((long long)D * H_ * W_), ospatial(spatial * KT) {}
+
+  // r-th unit of a channel (in the caller's index type: signed or unsigned division, as the caller's other arithmetic is)
+  template <class I>
+  static __device__ __forceinline__ Unit unit(I r) { return Unit{(int)(r / VP), (int)(r % VP)}; }
+
+  // W % TV == 0: a tile never crosses an input row, and spatial % TV == 0, so there is no ragged last tile.  Then a unit's
+  // offset is row_base (wave uniform, changes with the tile) + chan_off + row_off (per thread, never change), and every
+  // voxel of the tile exists: chan_ok alone decides whether the unit is read.
+  __device__ __forceinline__ bool row_tiles() const { return (W % TV) == 0; }
+  // A thread's offsets from its row_base span fewer than 64 channel planes of `spatial` floats in any of these kernels, so
+  // below 2^24 voxels they fit 32 bits as BYTE offsets (64 x 2^24 x 4 B = 2^32).
+  __device__ __forceinline__ bool byte_offsets_fit_32() const { return spatial < (1ll << 24); }
+  // channel o0 + ol (a block's first channel + the caller's place in it) of sample n
+  __device__ __forceinline__ long long row_base(int n, int o0, int ol, long long vbase) const {
+    int dv, hv, w0;
+    decode_dhw(vbase, W, H, dv, hv, w0);
+    return ((long long)n * Cout + o0 + ol) * ospatial + ((long long)dv * kd * Ho + (long long)hv * kh) * Wo + 2 * w0;
+  }
+  __device__ __forceinline__ long long chan_off(int ol) const { return (long long)ol * ospatial; }      // ol channels further on
+  __device__ __forceinline__ long long row_off(Unit u) const {
+    const int ii = u.rr / kh, jj = u.rr - ii * kh;
+    return ((long long)ii * Ho + jj) * Wo + 4 * u.vp;
+  }
+  // the validity rule: the channel exists and so do both voxels of the pair (spatial is even: a pair is never half inside)
+  __device__ __forceinline__ bool chan_ok(int o) const { return o < Cout; }
+  __device__ __forceinline__ bool valid(int o, long long vbase, Unit u) const { return o < Cout && vbase + 2 * u.vp + 1 < spatial; }
+  // any tile: the offset in dy of the unit of channel o, or 0 (a readable address whose value the commit drops) where it is not valid
+  __device__ __forceinline__ long long offset(int n, int o, long long vbase, Unit u) const {
+    const long long vi = vbase + 2 * u.vp;
+    const bool ok = o < Cout && vi + 1 < spatial;
+    long long off = 0;
+    if (ok) {
+      int dv, hv, wv;
+      decode_dhw(vi, W, H, dv, hv, wv);
+      const int ii = u.rr / kh, jj = u.rr - ii * kh;
+      off = ((long long)n * Cout + o) * ospatial + ((long long)(dv * kd + ii) * Ho + (hv * kh + jj)) * Wo + 2 * wv;
+    }
+    return off;
+  }
+  // where the unit's values go in an LDS image of 32 channels, as an index into it (ol = the channel's place in the image,
+  // EPV = index steps per staged value, STRIDE = index steps per row):
+  //   [tap][channel][voxel]: tap (rr, K) of voxels 2 vp, 2 vp + 1 (adjacent)
+  template <int K, int STRIDE, int EPV>
+  static __device__ __forceinline__ int tap_major(int ol, Unit u) { return ((u.rr * 2 + K) * 32 + ol) * STRIDE + 2 * EPV * u.vp; }
+  //   [voxel][channel x KT taps]: taps (rr, 0), (rr, 1) (adjacent) of voxel 2 vp; voxel 2 vp + 1 one row on
+  template <int STRIDE, int EPV>
+  static __device__ __forceinline__ int voxel_major(int ol, Unit u) { return (2 * u.vp) * STRIDE + (ol * KT + 2 * u.rr) * EPV; }
+};
+
 // ---- v2 (kw == 2, even W): software-pipelined staging ---------------------------------------------------------------
 // The op is HBM-bound when every byte is read once (25.6 FLOP/B at 64 -> 32 channels), so the workgroup covers NCB
 // blocks of 32 input channels against one block of 32 output channels and stages the dy tile once for all of them.
@@ -272,9 +343,10 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
                                                                    int B, int Cin, int Cout, int D, int H, int W, int kd, int kh,
                                                                    int tiles_per_chunk, int cgroups) {
   constexpr int KT = 2 * KDH;
-  constexpr int TS = WG_TPX + 2;                       // 66 == 2 (mod 32)
+  constexpr int TS = WG_TV + 2;                       // 66 == 2 (mod 32)
   constexpr int YCW = 32 / (4 * NCB);                  // dy channels staged per wave
-  constexpr int YIT = KDH * 32 / 64;                   // wave iterations per dy channel (KDH rows x 32 voxel pairs)
+  using Tile = DyTile<KDH, WG_TV>;
+  constexpr int YIT = Tile::UPC / 64;                  // wave iterations per dy channel
   static_assert(KDH == 2 || KDH == 4, "kd*kh in {2,4}");
   __shared__ __attribute__((aligned(16))) float zs[NCB * 32 * TS];
   __shared__ __attribute__((aligned(16))) float ds[KT * 32 * TS];
@@ -282,13 +354,12 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
   const int chunk = blockIdx.x;
   const int cg = blockIdx.y % cgroups, ob = blockIdx.y / cgroups;
   const long long spatial = (long long)D * H * W;
-  const long long tiles_per_n = e2e::cdivll(spatial, WG_TPX);
+  const long long tiles_per_n = e2e::cdivll(spatial, WG_TV);
   const long long total_tiles = tiles_per_n * B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cbl = wave >> 2, ch = wave & 1, oh = (wave >> 1) & 1;
-  const int Ho = H * kh, Wo = W * 2;
-  const long long ospatial = spatial * KT;
+  const Tile yt(Cout, D, H, W, kd, kh);
   const int cbase = cg * NCB * 32;
 
   f32x4_t acc[KT];
@@ -302,18 +373,13 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
   // z: each wave stages 8 channels x 64 voxels = 128 float4 -> 2 iterations; lane -> (channel k = g / 16, group g % 16)
   f32x4_t vz[2], vy[YCW][YIT];
   float za[2], zb[2];
-  const bool row_tiles = (W % WG_TPX) == 0;            // => spatial % 64 == 0 as well: no ragged last tile
+  const bool row_tiles = yt.row_tiles();
   long long yoff[YIT];
 #pragma unroll
-  for (int it = 0; it < YIT; ++it) {
-    const int g = lane + 64 * it;
-    const int rr = g >> 5, vp = g & 31;
-    const int i = rr / kh, j = rr - i * kh;
-    yoff[it] = ((long long)i * Ho + j) * Wo + 4 * vp;
-  }
+  for (int it = 0; it < YIT; ++it) yoff[it] = yt.row_off(Tile::unit(lane + 64u * it));
   auto prefetch = [&](long long tile) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TPX;
+    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TV;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int g = lane + 64 * it;
@@ -325,43 +391,26 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
       za[it] = 1.f; zb[it] = 0.f;
       if (scale != nullptr && c < Cin) { za[it] = scale[(long long)n * Cin + c]; zb[it] = shift[(long long)n * Cin + c]; }
     }
-    if (row_tiles) {      // the 64-voxel tile lies inside one input row: wave-uniform base + per-thread constant offsets
-      int dv, hv, w0;
-      decode_dhw(vbase, W, H, dv, hv, w0);
-      const long long tbase = ((long long)n * Cout + ob * 32 + wave * YCW) * ospatial +
-                              ((long long)dv * kd * Ho + (long long)hv * kh) * Wo + 2 * w0;
+    if (row_tiles) {
+      const long long tbase = yt.row_base(n, ob * 32, wave * YCW, vbase);
+      const int yo0 = ob * 32 + wave * YCW;            // this wave fetches dy channels yo0 .. yo0 + YCW
 #pragma unroll
       for (int k = 0; k < YCW; ++k)
 #pragma unroll
-        for (int it = 0; it < YIT; ++it) {
-          const bool ok = ob * 32 + wave * YCW + k < Cout;
-          vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (ok ? tbase + k * ospatial + yoff[it] : 0));
-        }
+        for (int it = 0; it < YIT; ++it)
+          vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (yt.chan_ok(yo0 + k) ? tbase + yt.chan_off(k) + yoff[it] : 0));
       return;
     }
 #pragma unroll
     for (int k = 0; k < YCW; ++k) {
       const int o = ob * 32 + wave * YCW + k;
 #pragma unroll
-      for (int it = 0; it < YIT; ++it) {
-        const int g = lane + 64 * it;                 // (row rr = g / 32, voxel pair vp = g % 32)
-        const int rr = g >> 5, vp = g & 31;
-        const long long vi = vbase + 2 * vp;
-        const bool ok = o < Cout && vi + 1 < spatial;
-        long long off = 0;
-        if (ok) {
-          int dv, hv, wv;
-          decode_dhw(vi, W, H, dv, hv, wv);
-          const int i = rr / kh, j = rr - i * kh;
-          off = ((long long)n * Cout + o) * ospatial + ((long long)(dv * kd + i) * Ho + (hv * kh + j)) * Wo + 2 * wv;
-        }
-        vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + off);
-      }
+      for (int it = 0; it < YIT; ++it) vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + yt.offset(n, o, vbase, Tile::unit(lane + 64u * it)));
     }
   };
   auto commit = [&](long long tile) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TPX;
+    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TV;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int g = lane + 64 * it;
@@ -384,12 +433,11 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
       const int ol = wave * YCW + k;
 #pragma unroll
       for (int it = 0; it < YIT; ++it) {
-        const int g = lane + 64 * it;
-        const int rr = g >> 5, vp = g & 31;
-        const bool ok = ob * 32 + ol < Cout && vbase + 2 * vp + 1 < spatial;
-        const f32x4_t q = vy[k][it];                  // (k=0,v) (k=1,v) (k=0,v+1) (k=1,v+1)
-        float2* d0 = reinterpret_cast<float2*>(ds + ((rr * 2 + 0) * 32 + ol) * TS + 2 * vp);
-        float2* d1 = reinterpret_cast<float2*>(ds + ((rr * 2 + 1) * 32 + ol) * TS + 2 * vp);
+        const typename Tile::Unit u = Tile::unit(lane + 64u * it);
+        const bool ok = yt.valid(ob * 32 + ol, vbase, u);
+        const f32x4_t q = vy[k][it];
+        float2* d0 = reinterpret_cast<float2*>(ds + Tile::template tap_major<0, TS, 1>(ol, u));
+        float2* d1 = reinterpret_cast<float2*>(ds + Tile::template tap_major<1, TS, 1>(ol, u));
         *d0 = ok ? make_float2(q[0], q[2]) : make_float2(0.f, 0.f);
         *d1 = ok ? make_float2(q[1], q[3]) : make_float2(0.f, 0.f);
       }
@@ -406,7 +454,7 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
       const float* ap = zs + (cbl * 32 + ch * 16 + li) * TS + lk;
       const float* bp = ds + (oh * 16 + li) * TS + lk;
 #pragma unroll 4
-      for (int k0 = 0; k0 < WG_TPX; k0 += 4) {
+      for (int k0 = 0; k0 < WG_TV; k0 += 4) {
         const float a = ap[k0];
 #pragma unroll
         for (int t = 0; t < KT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 32 * TS + k0], acc[t], 0, 0, 0);
@@ -426,7 +474,7 @@ __global__ __launch_bounds__(256 * NCB) void convT_wgrad_v2_kernel(const float* 
     }
 }
 
-// ---- v3 of the weight gradient (kw == 2, even W): the v2 pipeline on the bf16 matrix pipe with fp32-exact operands -------
+// ---- weight gradient, split operands (kw == 2, even W): the v2 pipeline on the bf16 / fp16 matrix pipe, fp32-exact operands ----
 // v2 is bound by its fp32 MFMAs (128 x 32 cycles per 64-voxel tile and wave, two waves per SIMD: 0.125 ms of a 0.25 ms
 // launch at 64 -> 32 @64^3).  Both operands are split into three bf16 pieces when they are staged ([piece][row][64 voxels]
 // bf16, row stride 144 B); the reduction dimension (voxels) is contiguous in both images, so an A / B fragment is one
@@ -501,26 +549,25 @@ __device__ __forceinline__ int ct_scale_exp(const unsigned* wa, const unsigned* 
   return scale_exp<LIM_CT>(__builtin_bit_cast(unsigned, b));
 }
 
-// TPX = input voxels per tile: 64 (one 138 KB workgroup per CU) or, for KDH = 4, 32: two 77 KB workgroups per CU, one converting
-// and committing its tile while the other issues its matrix instructions (the phases of ONE workgroup are serial: commit, barrier,
-// matrix phase, barrier, with a single LDS image).
-template <int KDH, int NCB, int TPX, int NP>     // KDH = kd * kh (output rows per input voxel row), KT = 2 * KDH; NP pieces per operand
-__global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+// A tile = WG_TV = 64 input voxels: one workgroup per CU (up to 138 KB of LDS), its phases serial (commit, barrier, matrix phase,
+// barrier, with a single LDS image).
+template <int KDH, int NCB, int NP>     // KDH = kd * kh (output rows per input voxel row), KT = 2 * KDH; NP pieces per operand
+__global__ __launch_bounds__(256 * NCB, 1) void convT_wgrad_bf3_kernel(const float* __restrict__ x, const float* __restrict__ scale,
                                                                    const float* __restrict__ shift, float slope,
                                                                    const float* __restrict__ dy, float* __restrict__ slab,
                                                                    int B, int Cin, int Cout, int D, int H, int W, int kd, int kh,
                                                                    int tiles_per_chunk, int cgroups, const unsigned* __restrict__ x_word,
                                                                    const unsigned* __restrict__ dy_word_a, const unsigned* __restrict__ dy_word_b) {
   constexpr int KT = 2 * KDH;
-  constexpr int RS = TPX * 2 + 16;                     // bytes per staged row (TPX voxels bf16 + 16: odd multiple of 16, conflict-free b128)
-  constexpr int ZG = TPX / 4;                          // float4 groups per input channel row
-  constexpr int ZIT = 8 * ZG / 64;                     // wave iterations over its 8 input channels
-  constexpr int VP = TPX / 2;                          // voxel pairs (= float4 of dy) per output row
+  using Tile = DyTile<KDH, WG_TV>;
+  constexpr int RS = WG_TV * 2 + 16;                   // 144 bytes per staged row (64 voxels bf16 + 16: odd multiple of 16, conflict-free b128)
+  constexpr int ZG = WG_TV / 4;                        // 16 float4 groups per input channel row
+  constexpr int ZIT = 8 * ZG / 64;                     // 2 wave iterations over its 8 input channels
   constexpr int ZP = NCB * 32 * RS, YP = KT * 32 * RS;  // bytes per piece
   constexpr int YCW = 32 / (4 * NCB);                  // dy channels staged per wave
-  constexpr int YIT = KDH * VP / 64;                   // wave iterations per dy channel (KDH rows x VP voxel pairs)
-  static_assert((KDH == 2 || KDH == 4) && (TPX == 64 || (TPX == 32 && KDH == 4)), "kd*kh in {2,4}; 32-voxel tiles for kd*kh = 4");
-  static_assert((TPX == 32 ? 2 : 1) * NP * (NCB * 32 + 2 * KDH * 32) * RS <= 163840, "LDS budget");
+  constexpr int YIT = Tile::UPC / 64;                  // wave iterations per dy channel
+  static_assert(KDH == 2 || KDH == 4, "kd*kh in {2,4}");
+  static_assert(NP * (NCB * 32 + 2 * KDH * 32) * RS <= 163840, "LDS budget");
   __shared__ __attribute__((aligned(16))) unsigned char zs[NP * ZP];     // [piece][channel][voxel] bf16 / fp16
   __shared__ __attribute__((aligned(16))) unsigned char ds[NP * YP];     // [piece][tap][out channel][voxel]
   // fp16 two-piece form: operand scales 2^kx (activations) and 2^ky (dy), the slab un-scaled by the two exact factors
@@ -530,13 +577,12 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
   const int chunk = blockIdx.x;
   const int cg = blockIdx.y % cgroups, ob = blockIdx.y / cgroups;
   const long long spatial = (long long)D * H * W;
-  const long long tiles_per_n = e2e::cdivll(spatial, TPX);
+  const long long tiles_per_n = e2e::cdivll(spatial, WG_TV);
   const long long total_tiles = tiles_per_n * B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cbl = wave >> 2, ch = wave & 1, oh = (wave >> 1) & 1;
-  const int Ho = H * kh, Wo = W * 2;
-  const long long ospatial = spatial * KT;
+  const Tile yt(Cout, D, H, W, kd, kh);
   const int cbase = cg * NCB * 32;
 
   f32x4_t acc[KT];
@@ -550,20 +596,14 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
   // z: each wave stages 8 channels x 64 voxels = 128 float4 -> 2 iterations; lane -> (channel k = g / 16, group g % 16)
   f32x4_t vz[ZIT], vy[YCW][YIT];
   float za[ZIT], zb[ZIT];
-  // (=> spatial % 64 == 0 as well: no ragged last tile; the fast path keeps per-lane byte offsets in 32 bits: 96 spatial x 4 B)
-  const bool row_tiles = (W % TPX) == 0 && spatial < (1ll << 24);
+  const bool row_tiles = yt.row_tiles() && yt.byte_offsets_fit_32();
   long long yoff[YIT];
 #pragma unroll
-  for (int it = 0; it < YIT; ++it) {
-    const int g = lane + 64 * it;
-    const int rr = g / VP, vp = g % VP;
-    const int i = rr / kh, j = rr - i * kh;
-    yoff[it] = ((long long)i * Ho + j) * Wo + 4 * vp;
-  }
-  // row tiles (W % 64 == 0): a tile's addresses are a wave-uniform base (scalar arithmetic) plus per-lane byte offsets that
-  // never change; the normalise-on-load coefficients change only with the batch item.  (s_memtime stamps: issuing the ten
-  // float4 loads of a tile with per-lane 64-bit index arithmetic, two integer divisions and four coefficient loads took
-  // ~2500 cycles, as long as the tile's matrix phase.)
+  for (int it = 0; it < YIT; ++it) yoff[it] = yt.row_off(Tile::unit(lane + 64 * it));
+  // row tiles: a tile's addresses are a wave-uniform base (scalar arithmetic) plus per-lane byte offsets that never change;
+  // the normalise-on-load coefficients change only with the batch item.  (Clock stamps: issuing the ten float4 loads of a
+  // tile with per-lane 64-bit index arithmetic, two integer divisions and four coefficient loads took ~2500 cycles, as long
+  // as the tile's matrix phase.)
   unsigned zoffb[ZIT], yoffb[YCW][YIT];
   bool zcok[ZIT];
 #pragma unroll
@@ -576,11 +616,11 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
   for (int k = 0; k < YCW; ++k)
 #pragma unroll
     for (int it = 0; it < YIT; ++it)
-      yoffb[k][it] = (ob * 32 + wave * YCW + k < Cout) ? (unsigned)(((long long)k * ospatial + yoff[it]) * 4) : 0u;
+      yoffb[k][it] = yt.chan_ok(ob * 32 + wave * YCW + k) ? (unsigned)((yt.chan_off(k) + yoff[it]) * 4) : 0u;
   int cur_n = -1;
   auto prefetch = [&](long long tile) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-    const long long vbase = (tile - (long long)n * tiles_per_n) * TPX;
+    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TV;
     if (row_tiles) {
       if (n != cur_n) {
         cur_n = n;
@@ -591,12 +631,10 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
           if (scale != nullptr && c < Cin) { za[it] = scale[(long long)n * Cin + c]; zb[it] = shift[(long long)n * Cin + c]; }
         }
       }
-      int dv, hv, w0;
-      decode_dhw(vbase, W, H, dv, hv, w0);
-      const char* zb8 = reinterpret_cast<const char*>(x + ((long long)n * Cin + cbase) * spatial + vbase);
       const int ych = ob * 32 + wave * YCW < Cout ? ob * 32 + wave * YCW : 0;      // (waves past the last channel read channel 0 and drop it)
-      const char* yb8 = reinterpret_cast<const char*>(dy + ((long long)n * Cout + ych) * ospatial +
-                                                      ((long long)dv * kd * Ho + (long long)hv * kh) * Wo + 2 * w0);
+      const long long ybase = yt.row_base(n, ych, 0, vbase);
+      const char* zb8 = reinterpret_cast<const char*>(x + ((long long)n * Cin + cbase) * spatial + vbase);
+      const char* yb8 = reinterpret_cast<const char*>(dy + ybase);
 #pragma unroll
       for (int it = 0; it < ZIT; ++it) vz[it] = *reinterpret_cast<gf4_p>((gfloat_p)(zb8 + zoffb[it]));
 #pragma unroll
@@ -620,25 +658,12 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
     for (int k = 0; k < YCW; ++k) {
       const int o = ob * 32 + wave * YCW + k;
 #pragma unroll
-      for (int it = 0; it < YIT; ++it) {
-        const int g = lane + 64 * it;                 // (row rr = g / VP, voxel pair vp = g % VP)
-        const int rr = g / VP, vp = g % VP;
-        const long long vi = vbase + 2 * vp;
-        const bool ok = o < Cout && vi + 1 < spatial;
-        long long off = 0;
-        if (ok) {
-          int dv, hv, wv;
-          decode_dhw(vi, W, H, dv, hv, wv);
-          const int i = rr / kh, j = rr - i * kh;
-          off = ((long long)n * Cout + o) * ospatial + ((long long)(dv * kd + i) * Ho + (hv * kh + j)) * Wo + 2 * wv;
-        }
-        vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + off);
-      }
+      for (int it = 0; it < YIT; ++it) vy[k][it] = *reinterpret_cast<gf4_p>((gfloat_p)dy + yt.offset(n, o, vbase, Tile::unit(lane + 64 * it)));
     }
   };
   auto commit = [&](long long tile) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-    const long long vbase = (tile - (long long)n * tiles_per_n) * TPX;
+    const long long vbase = (tile - (long long)n * tiles_per_n) * WG_TV;
 #pragma unroll
     for (int it = 0; it < ZIT; ++it) {
       const int g = lane + 64 * it;
@@ -661,43 +686,31 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
       const int ol = wave * YCW + k;
 #pragma unroll
       for (int it = 0; it < YIT; ++it) {
-        const int g = lane + 64 * it;
-        const int rr = g / VP, vp = g % VP;
-        const bool ok = ob * 32 + ol < Cout && vbase + 2 * vp + 1 < spatial;
-        f32x4_t q = vy[k][it];                        // (k=0,v) (k=1,v) (k=0,v+1) (k=1,v+1)
+        const typename Tile::Unit u = Tile::unit(lane + 64 * it);
+        const bool ok = yt.valid(ob * 32 + ol, vbase, u);
+        f32x4_t q = vy[k][it];
         if (!ok) q = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (NP == 2) q *= ysc;
-        unsigned char* d0 = ds + ((rr * 2 + 0) * 32 + ol) * RS + 4 * vp;      // tap (rr, 0): voxels 2 vp, 2 vp + 1
-        unsigned char* d1 = ds + ((rr * 2 + 1) * 32 + ol) * RS + 4 * vp;
+        unsigned char* d0 = ds + Tile::template tap_major<0, RS, 2>(ol, u);
+        unsigned char* d1 = ds + Tile::template tap_major<1, RS, 2>(ol, u);
         store_pair<NP>(d0, YP, q[0], q[2]);
         store_pair<NP>(d1, YP, q[1], q[3]);
       }
     }
   };
 
-#ifdef CT_DIAG
-  unsigned long long stamp[16]; int ns = 0;
-#define CSTAMP() do { if (ns < 16) stamp[ns++] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define CSTAMP() do {} while (0)
-#endif
   if (tile_lo < tile_hi) {
-    CSTAMP();
     prefetch(tile_lo);
     for (long long tile = tile_lo; tile < tile_hi; ++tile) {
-      CSTAMP();
       commit(tile);
-      CSTAMP();
       __syncthreads();
-      CSTAMP();
       if (tile + 1 < tile_hi) prefetch(tile + 1);
-      CSTAMP();
       const int li = lane & 15, lk = lane >> 4;
       // A: channel row, 8 consecutive voxels 32 kb + 8 lk ..; B: out channel row of tap t, the same voxels
       const unsigned char* ap = zs + (cbl * 32 + ch * 16 + li) * RS + lk * 16;
       const unsigned char* bp = ds + (oh * 16 + li) * RS + lk * 16;
 #pragma unroll
-      for (int kb = 0; kb < TPX / 32; ++kb) {
+      for (int kb = 0; kb < WG_TV / 32; ++kb) {
         bf16x8_t af[NP];
 #pragma unroll
         for (int sp = 0; sp < NP; ++sp) af[sp] = *reinterpret_cast<const bf16x8_t*>(ap + sp * ZP + kb * 64);
@@ -709,17 +722,9 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
           acc[t] = mma_pieces<NP>(af, bf, acc[t]);
         }
       }
-      CSTAMP();
       __syncthreads();
     }
   }
-#ifdef CT_DIAG
-  if (tid == 64 && blockIdx.y == 0 && (blockIdx.x == 100 || blockIdx.x == 101))
-    printf("WG %d tiles %d | pre %u | t0: wait+commit %u bar %u pf %u mma %u | t1: bar %u commit %u bar %u pf %u mma %u | t2: bar %u commit %u bar %u\n", blockIdx.x, (int)(tile_hi - tile_lo),
-           (unsigned)(stamp[1]-stamp[0]), (unsigned)(stamp[2]-stamp[1]), (unsigned)(stamp[3]-stamp[2]), (unsigned)(stamp[4]-stamp[3]), (unsigned)(stamp[5]-stamp[4]),
-           (unsigned)(stamp[6]-stamp[5]), (unsigned)(stamp[7]-stamp[6]), (unsigned)(stamp[8]-stamp[7]), (unsigned)(stamp[9]-stamp[8]), (unsigned)(stamp[10]-stamp[9]),
-           (unsigned)(stamp[11]-stamp[10]), (unsigned)(stamp[12]-stamp[11]), (unsigned)(stamp[13]-stamp[12]));
-#endif
   // D[i = c][j = o]: col = lane & 15 -> o, row = (lane >> 4) * 4 + reg -> c
   float* sp = slab + (long long)chunk * Cin * Cout * KT;
   const int o = ob * 32 + oh * 16 + (lane & 15);
@@ -732,93 +737,6 @@ __global__ __launch_bounds__(256 * NCB, TPX == 32 ? 2 : 1) void convT_wgrad_bf3_
     }
 }
 
-
-// ---- data gradient v2 (kw == 2, even W): dy tile staged once in LDS ---------------------------------------------------
-// dx[c, v] = sum_o sum_t W[c, o, t] * dy[o, out(v, t)].  A tile = 64 consecutive input voxels (lane = voxel); the dy
-// values of 32 output channels x KT taps are loaded as aligned float4 and scattered to an LDS image [tap][o][voxel];
-// each wave then walks its input channels and, per channel, the live output channels (scalar bit ops), reading dy
-// from LDS conflict free.  dy is read from HBM once instead of once per live (c, o) pair.
-template <int KDH>
-__global__ __launch_bounds__(256) void convT_dgrad_v2_kernel(const float* __restrict__ dy, const float* __restrict__ w,
-                                                             const unsigned* __restrict__ live_t, float* __restrict__ dx,
-                                                             int accumulate, int B, int Cin, int Cout, int D, int H, int W,
-                                                             int kd, int kh) {
-  constexpr int KT = 2 * KDH;
-  constexpr int OC = 32;                               // output channels per staged chunk
-  constexpr int TS = 64;                               // lane = voxel: consecutive lanes, consecutive banks
-  constexpr int NUY = OC * KDH * 32 / 256;             // float4 loads per thread per chunk
-  __shared__ __attribute__((aligned(16))) float ds[KT * OC * TS];
-
-  const long long spatial = (long long)D * H * W;
-  const long long tiles_per_n = e2e::cdivll(spatial, 64);
-  const long long tile = blockIdx.x;
-  const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
-  const long long vbase = (tile - (long long)n * tiles_per_n) * 64;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int Ho = H * kh, Wo = W * 2;
-  const long long ospatial = spatial * KT;
-  const int words = e2e::cdiv(Cout, 32);
-  const long long vi_lane = vbase + lane;
-
-  for (int o0 = 0; o0 < Cout; o0 += OC) {
-    // ---- stage dy[o0 .. o0+32) for this tile: unit = (o, output row rr, voxel pair vp) ----
-    f32x4_t v[NUY];
-#pragma unroll
-    for (int i = 0; i < NUY; ++i) {
-      const int u = tid + i * 256;
-      const int ol = u / (KDH * 32);
-      const int rem = u - ol * (KDH * 32);
-      const int rr = rem >> 5, vp = rem & 31;
-      const long long vi = vbase + 2 * vp;
-      const int o = o0 + ol;
-      const bool ok = o < Cout && vi + 1 < spatial;
-      long long off = 0;
-      if (ok) {
-        int dv, hv, wv;
-        decode_dhw(vi, W, H, dv, hv, wv);
-        const int ii = rr / kh, jj = rr - ii * kh;
-        off = ((long long)n * Cout + o) * ospatial + ((long long)(dv * kd + ii) * Ho + (hv * kh + jj)) * Wo + 2 * wv;
-      }
-      v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + off);
-    }
-    if (o0 > 0) __syncthreads();                       // previous chunk fully consumed
-#pragma unroll
-    for (int i = 0; i < NUY; ++i) {
-      const int u = tid + i * 256;
-      const int ol = u / (KDH * 32);
-      const int rem = u - ol * (KDH * 32);
-      const int rr = rem >> 5, vp = rem & 31;
-      const bool ok = o0 + ol < Cout && vbase + 2 * vp + 1 < spatial;
-      float2* d0 = reinterpret_cast<float2*>(ds + ((rr * 2 + 0) * OC + ol) * TS + 2 * vp);
-      float2* d1 = reinterpret_cast<float2*>(ds + ((rr * 2 + 1) * OC + ol) * TS + 2 * vp);
-      *d0 = ok ? make_float2(v[i][0], v[i][2]) : make_float2(0.f, 0.f);
-      *d1 = ok ? make_float2(v[i][1], v[i][3]) : make_float2(0.f, 0.f);
-    }
-    __syncthreads();
-    // ---- compute: wave w owns input channels w, w+4, ... ----
-    for (int c = wave; c < Cin; c += 4) {
-      unsigned bits = live_t ? live_t[(long long)c * words + (o0 >> 5)] : 0xffffffffu;
-      const int remain = Cout - o0;
-      if (remain < 32) bits &= (1u << remain) - 1u;
-      bits = __builtin_amdgcn_readfirstlane(bits);
-      float acc = 0.f;
-      while (bits) {
-        const int ol = __builtin_ctz(bits);
-        bits &= bits - 1;
-        const float* wp = w + ((long long)c * Cout + o0 + ol) * KT;
-        const float* dp = ds + ol * TS + lane;
-#pragma unroll
-        for (int t = 0; t < KT; ++t) acc = fmaf(wp[t], dp[t * OC * TS], acc);
-      }
-      if (vi_lane < spatial) {
-        float* dst = dx + ((long long)n * Cin + c) * spatial + vi_lane;
-        if (accumulate || o0 > 0) *dst += acc;
-        else *dst = acc;
-      }
-    }
-  }
-}
 
 // DSFF liveness of the (in channel c, out channel o) kernel from the bit tables of e2e_dsff_expand (null = all alive).  The
 // GEMM kernels below multiply whole tiles, so a pruned kernel is dropped where the weight enters a fragment -- the result
@@ -833,9 +751,10 @@ __device__ __forceinline__ bool ct_alive_cols(const unsigned* live, int Cin, int
 // ---- data gradient v3 (kw == 2): dense GEMM on the fp32 matrix cores ----------------------------------------------------
 // dx[c, v] = sum_{(t, o)} W[c, o, t] * dy[o, out(v, t)]:  M = 64 input channels per workgroup (16 per wave), N = 32
 // consecutive input voxels per tile, K = 32 output channels x KT taps per chunk.  At DSFF density 0.2 the dense GEMM does
-// 5x the useful FLOPs, but the sparse walk of v2 issues one scalar weight load and KT dependent LDS reads per live (c, o)
-// pair with two waves per SIMD -- latency bound at ~4x the HBM time of this op -- while the matrix pipe runs the dense
-// product in less time than that (dead kernels enter the fragments as zeros, so the result is the same sum).
+// 5x the useful FLOPs, but a walk over the live (c, o) pairs issues one scalar weight load and KT dependent reads per pair
+// -- latency bound at ~4x the HBM time of this op -- while the matrix pipe runs the dense product in less time than that
+// (dead kernels enter the fragments as zeros, so the result is the same sum).  E2E_CT_BF3=0, or a W that is no multiple
+// of 32, selects this kernel; the split-operand form below serves the rest.
 //   * a wave keeps its 16 x K slice of W in registers (K/4 A fragments) for the whole run of tiles;
 //   * the dy tile [K][32 voxels] is staged through LDS (row stride 48: the two k-rows of a 32-lane read group land on
 //     disjoint banks), software pipelined: the float4 loads of the next tile are issued before the MFMA phase.
@@ -846,8 +765,9 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
                                                              int D, int H, int W, int kd, int kh, int tiles_per_wg) {
   constexpr int KT = 2 * KDH;
   constexpr int OC = 32, TV = 32, TS = 48;
+  using Tile = DyTile<KDH, TV>;
   constexpr int K = OC * KT, KS = K / 4;               // k-steps per chunk
-  constexpr int NUY = OC * KDH * (TV / 2) / 256;       // float4 loads per thread per tile
+  constexpr int NUY = OC * Tile::UPC / 256;            // float4 loads per thread per tile: unit tid + 256 i -> channel / UPC, unit % UPC
   __shared__ __attribute__((aligned(16))) float ds[K * TS];
 
   const long long spatial = (long long)D * H * W;
@@ -856,8 +776,7 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lk = lane >> 4;
-  const int Ho = H * kh, Wo = W * 2;
-  const long long ospatial = spatial * KT;
+  const Tile yt(Cout, D, H, W, kd, kh);
   const int cbase = blockIdx.y * 64 + wave * 16;
   const long long tile_lo = (long long)blockIdx.x * tiles_per_wg;
   long long tile_hi = tile_lo + tiles_per_wg;
@@ -865,54 +784,33 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
   if (tile_lo >= tile_hi) return;
 
   f32x4_t v[NUY];
-  // per-thread part of the dy offsets, constant over the tiles when a tile (32 consecutive voxels) never crosses a row
-  // (W % 32 == 0): unit = (o, output row rr, voxel pair vp) -> o * ospatial + (ii * Ho + jj) * Wo + 4 vp; the tile adds
-  // a wave-uniform base.  (The general path below re-derives (d, h, w) per unit with 64-bit divisions: ~1000 vector
-  // instructions per tile and thread, more than the MFMA phase.)
-  const bool row_tiles = (W % TV) == 0;
+  // row tiles: the per-thread part of the dy offsets is constant over the tiles.  (The general path re-derives (d, h, w)
+  // per unit with 64-bit divisions: ~1000 vector instructions per tile and thread, more than the MFMA phase.)
+  const bool row_tiles = yt.row_tiles();
   long long uoff[NUY];
 #pragma unroll
   for (int i = 0; i < NUY; ++i) {
     const int u = tid + i * 256;
-    const int ol = u / (KDH * (TV / 2));
-    const int rem = u - ol * (KDH * (TV / 2));
-    const int rr = rem / (TV / 2), vp = rem - rr * (TV / 2);
-    const int ii = rr / kh, jj = rr - ii * kh;
-    uoff[i] = (long long)ol * ospatial + ((long long)ii * Ho + jj) * Wo + 4 * vp;
+    const int ol = u / Tile::UPC;
+    uoff[i] = yt.chan_off(ol) + yt.row_off(Tile::unit(u - ol * Tile::UPC));
   }
   auto prefetch = [&](long long tile, int o0) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
     const long long vbase = (tile - (long long)n * tiles_per_n) * TV;
     if (row_tiles) {
-      int dv, hv, w0;
-      decode_dhw(vbase, W, H, dv, hv, w0);
-      const long long tbase = ((long long)n * Cout + o0) * ospatial + ((long long)dv * kd * Ho + (long long)hv * kh) * Wo + 2 * w0;
+      const long long tbase = yt.row_base(n, o0, 0, vbase);
 #pragma unroll
       for (int i = 0; i < NUY; ++i) {
-        const int u = tid + i * 256;
-        const int ol = u / (KDH * (TV / 2));
-        const bool ok = o0 + ol < Cout;                  // (spatial % 32 == 0 here: no ragged last tile)
-        v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (ok ? tbase + uoff[i] : 0));
+        const int ol = (tid + i * 256) / Tile::UPC;
+        v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (yt.chan_ok(o0 + ol) ? tbase + uoff[i] : 0));
       }
       return;
     }
 #pragma unroll
     for (int i = 0; i < NUY; ++i) {
-      const int u = tid + i * 256;                       // unit = (o, output row rr, voxel pair vp)
-      const int ol = u / (KDH * (TV / 2));
-      const int rem = u - ol * (KDH * (TV / 2));
-      const int rr = rem / (TV / 2), vp = rem - rr * (TV / 2);
-      const long long vi = vbase + 2 * vp;
-      const int o = o0 + ol;
-      const bool ok = o < Cout && vi + 1 < spatial;
-      long long off = 0;
-      if (ok) {
-        int dv, hv, wv;
-        decode_dhw(vi, W, H, dv, hv, wv);
-        const int ii = rr / kh, jj = rr - ii * kh;
-        off = ((long long)n * Cout + o) * ospatial + ((long long)(dv * kd + ii) * Ho + (hv * kh + jj)) * Wo + 2 * wv;
-      }
-      v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + off);
+      const int u = tid + i * 256;
+      const int ol = u / Tile::UPC;
+      v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + yt.offset(n, o0 + ol, vbase, Tile::unit(u - ol * Tile::UPC)));
     }
   };
   auto commit = [&](long long tile, int o0) {
@@ -921,12 +819,11 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
 #pragma unroll
     for (int i = 0; i < NUY; ++i) {
       const int u = tid + i * 256;
-      const int ol = u / (KDH * (TV / 2));
-      const int rem = u - ol * (KDH * (TV / 2));
-      const int rr = rem / (TV / 2), vp = rem - rr * (TV / 2);
-      const bool ok = o0 + ol < Cout && vbase + 2 * vp + 1 < spatial;
-      float2* d0 = reinterpret_cast<float2*>(ds + ((rr * 2 + 0) * OC + ol) * TS + 2 * vp);
-      float2* d1 = reinterpret_cast<float2*>(ds + ((rr * 2 + 1) * OC + ol) * TS + 2 * vp);
+      const int ol = u / Tile::UPC;
+      const typename Tile::Unit un = Tile::unit(u - ol * Tile::UPC);
+      const bool ok = yt.valid(o0 + ol, vbase, un);
+      float2* d0 = reinterpret_cast<float2*>(ds + Tile::template tap_major<0, TS, 1>(ol, un));
+      float2* d1 = reinterpret_cast<float2*>(ds + Tile::template tap_major<1, TS, 1>(ol, un));
       *d0 = ok ? make_float2(v[i][0], v[i][2]) : make_float2(0.f, 0.f);
       *d1 = ok ? make_float2(v[i][1], v[i][3]) : make_float2(0.f, 0.f);
     }
@@ -996,7 +893,7 @@ __global__ __launch_bounds__(256) void convT_dgrad_v3_kernel(const float* __rest
   }
 }
 
-// ---- forward v2 (kw == 2, W % 32 == 0, Cin <= 256): dense GEMM on the bf16 matrix pipe with fp32-exact operands ------------
+// ---- forward GEMM (kw == 2, W % 32 == 0, Cin <= 256): dense GEMM on the bf16 / fp16 matrix pipe with fp32-exact operands ----
 // y[v, (o, t)] = sum_c z[v, c] W[c, (o, t)]:  M = 32 consecutive input voxels of a row per tile, K = Cin (NKB blocks of 32),
 // N = Cout x KT output columns.  The gather kernel above re-reads the input once per output channel (through L2) and is
 // bound by scalar weight loads and the per-voxel FMA chains (2.9 TB/s at 64 -> 32 @64^3); here
@@ -1124,6 +1021,7 @@ __global__ __launch_bounds__(256, 2) void convT_fwd_bf3_kernel(const float* __re
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = mma_pieces<NP>(af, bfr[nt][kb], acc[mt][nt]);
       }
+    // (The store side is not DyTile's unit map: a lane owns four consecutive voxels of one result column (o, t), not a voxel pair.)
     // D: row (voxel) = 16 mt + 4 lk + i, column = lane & 15.  Lanes 2p, 2p + 1 hold taps k = 0, 1 of one (o, i, j): after the
     // pair swap lane k = 0 owns output floats [2 v .. 2 v + 3] and lane k = 1 the next four of the interleaved row.
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
@@ -1149,7 +1047,7 @@ __global__ __launch_bounds__(256, 2) void convT_fwd_bf3_kernel(const float* __re
   }
 }
 
-// ---- data gradient v4 (kw == 2, W % 32 == 0): the v3 GEMM on the bf16 matrix pipe with fp32-exact operands ----------------
+// ---- data gradient, split operands (kw == 2, W % 32 == 0): the v3 GEMM on the bf16 / fp16 matrix pipe, fp32-exact operands ----
 // v3 is bound by its fp32 MFMAs (128 x 32 cycles per 32-voxel tile and wave: ~0.15 ms of a 0.31 ms launch at 64 -> 32 @64^3,
 // the staging and the HBM stream not overlapped with them).  Every fp32 value is split without error into three bf16
 // pieces (hi, mid, lo) and a product is rebuilt from the six leading cross terms, as in conv133_wgrad_bf3.hip / conv133_dense.hip
@@ -1167,22 +1065,22 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
                                                                  const unsigned* __restrict__ dy_word_b) {
   constexpr int KT = 2 * KDH;
   constexpr int OC = 32, TV = 32;
+  using Tile = DyTile<KDH, TV>;
   constexpr int K = OC * KT, NKB = K / 32;             // 16x16x32 k-blocks per chunk
   constexpr int S = K * 2 + 16;                        // bytes per staged voxel and piece (528 / 272: odd multiples of 16)
   constexpr int PSZ = TV * S;
-  constexpr int NUY = OC * KDH * (TV / 2) / 256;       // float4 loads per thread per tile
+  constexpr int NUY = OC * Tile::UPC / 256;            // float4 loads per thread per tile: unit tid + 256 i -> channel / UPC, unit % UPC
   __shared__ __attribute__((aligned(16))) unsigned char ds[NP * PSZ];
   const int kwt = NP == 2 ? ct_scale_exp(w_word, nullptr) : 0, ky = NP == 2 ? ct_scale_exp(dy_word_a, dy_word_b) : 0;
   const float wsc = pow2f(kwt), ysc = pow2f(ky), unw = pow2f(-kwt), uny = pow2f(-ky);
 
   const long long spatial = (long long)D * H * W;
-  const long long tiles_per_n = spatial / TV;          // (W % 32 == 0: a tile is 32 consecutive voxels of one row)
+  const long long tiles_per_n = spatial / TV;          // (launched on row tiles only)
   const long long total_tiles = tiles_per_n * B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lk = lane >> 4;
-  const int Ho = H * kh, Wo = W * 2;
-  const long long ospatial = spatial * KT;
+  const Tile yt(Cout, D, H, W, kd, kh);
   const int cbase = blockIdx.y * 64 + wave * 16;
   const long long tile_lo = (long long)blockIdx.x * tiles_per_wg;
   long long tile_hi = tile_lo + tiles_per_wg;
@@ -1191,34 +1089,30 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
 
   f32x4_t v[NUY];
   long long uoff[NUY];
-  int ulds[NUY];
+  int ulds[NUY];                                       // where the unit goes in the LDS image
 #pragma unroll
   for (int i = 0; i < NUY; ++i) {
-    const int u = tid + i * 256;                        // unit = (o, output row rr, voxel pair vp), vp fastest (coalesced float4s)
-    const int ol = u / (KDH * (TV / 2));
-    const int rem = u - ol * (KDH * (TV / 2));
-    const int rr = rem / (TV / 2), vp = rem - rr * (TV / 2);
-    const int ii = rr / kh, jj = rr - ii * kh;
-    uoff[i] = (long long)ol * ospatial + ((long long)ii * Ho + jj) * Wo + 4 * vp;
-    ulds[i] = (2 * vp) * S + (ol * KT + 2 * rr) * 2;
+    const int u = tid + i * 256;
+    const int ol = u / Tile::UPC;
+    const typename Tile::Unit un = Tile::unit(u - ol * Tile::UPC);
+    uoff[i] = yt.chan_off(ol) + yt.row_off(un);
+    ulds[i] = Tile::template voxel_major<S, 2>(ol, un);
   }
   auto prefetch = [&](long long tile, int o0) {
     const int n = (int)((unsigned)tile / (unsigned)tiles_per_n);
     const long long vbase = (tile - (long long)n * tiles_per_n) * TV;
-    int dv, hv, w0;
-    decode_dhw(vbase, W, H, dv, hv, w0);
-    const long long tbase = ((long long)n * Cout + o0) * ospatial + ((long long)dv * kd * Ho + (long long)hv * kh) * Wo + 2 * w0;
+    const long long tbase = yt.row_base(n, o0, 0, vbase);
 #pragma unroll
     for (int i = 0; i < NUY; ++i) {
-      const int ol = (tid + i * 256) / (KDH * (TV / 2));
-      v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (o0 + ol < Cout ? tbase + uoff[i] : 0));
+      const int ol = (tid + i * 256) / Tile::UPC;
+      v[i] = *reinterpret_cast<gf4_p>((gfloat_p)dy + (yt.chan_ok(o0 + ol) ? tbase + uoff[i] : 0));
     }
   };
   auto commit = [&](int o0) {
 #pragma unroll
     for (int i = 0; i < NUY; ++i) {
-      const int ol = (tid + i * 256) / (KDH * (TV / 2));
-      const bool ok = o0 + ol < Cout;
+      const int ol = (tid + i * 256) / Tile::UPC;
+      const bool ok = yt.chan_ok(o0 + ol);
       f32x4_t q = ok ? v[i] : f32x4_t{0.f, 0.f, 0.f, 0.f};
       if (NP == 2) q *= ysc;
       unsigned char* d0 = ds + ulds[i];
@@ -1300,14 +1194,12 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_bf3_kernel(const float* __
 
 }  // namespace
 
-#define DISPATCH_KT(KTV, ...)                  \
-  switch (KTV) {                               \
-    case 1: { constexpr int KT = 1; __VA_ARGS__; break; } \
-    case 2: { constexpr int KT = 2; __VA_ARGS__; break; } \
-    case 4: { constexpr int KT = 4; __VA_ARGS__; break; } \
-    case 8: { constexpr int KT = 8; __VA_ARGS__; break; } \
-    default: e2e::set_error("convT: kernel volume %d unsupported", KTV); return E2E_ERR_UNSUPPORTED; \
-  }
+// calls f(std::integral_constant<int, V>{}) for the V among Vs that equals v: the one place a run-time plan value becomes a
+// template argument.  The entry points and plans only produce listed values (check_k; nkb, ncb, np below).
+template <int... Vs, class F>
+static void with_const(int v, F&& f) {
+  (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 static int check_k(int kd, int kh, int kw) {
   return (kd == 1 || kd == 2) && (kh == 1 || kh == 2) && (kw == 1 || kw == 2);
@@ -1318,6 +1210,109 @@ static int ct_h2_env() { static const int v = getenv("E2E_CT_H2") ? atoi(getenv(
 // E2E_CT_BF3=0 keeps the round-2 kernels (gather forward, fp32-MFMA gradients) instead of the split-operand matrix-pipe ones
 static int ct_bf3_env() { static const int v = getenv("E2E_CT_BF3") ? atoi(getenv("E2E_CT_BF3")) : 1; return v; }
 
+// ---- plans: which kernel serves a shape, on what grid ---------------------------------------------------------------------
+enum CtPath {
+  CT_PLAIN,      // gather forward / data gradient, v1 weight gradient: any kernel in {1,2}^3
+  CT_FP32,       // fp32 matrix instructions: data gradient v3, weight gradient v2
+  CT_SPLIT       // split operands on the bf16 / fp16 matrix pipe: *_bf3_kernel, np pieces per operand
+};
+
+// A GEMM kernel can serve the shape: kw == 2 and an even W make the taps (k = 0, 1) of a voxel pair one aligned float4 of an
+// output row (the unit of DyTile, and what the forward stores), KDH = kd * kh such rows per input row are instantiated for
+// 2 and 4, and the input is read as float4 (spatial % 4 == 0).
+static bool ct_gemm_shape(long long spatial, int W, int kd, int kh, int kw) {
+  return kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0;
+}
+// pieces per operand: 2 (fp16) where the caller handed over both range words, else 3 (bf16)
+static int ct_pieces(bool words) { return (ct_h2_env() && words) ? 2 : 3; }
+
+// forward / data gradient on a run of 32-voxel tiles per workgroup
+struct CtTilePlan {
+  CtPath path;
+  int np;                // CT_SPLIT: pieces per operand
+  int nkb;               // forward, CT_SPLIT: 32-channel k-blocks (template argument)
+  int vpl;               // forward, CT_PLAIN: voxels per thread (template argument)
+  int cgroups;           // launch grid y
+  int tiles_per_wg;
+  unsigned wgs;          // launch grid x
+};
+// about `target` workgroups over all channel groups, at least 4 tiles each
+static void ct_tile_grid(CtTilePlan& pl, long long total_tiles, int target) {
+  long long wgs = target / pl.cgroups;
+  if (wgs < 1) wgs = 1;
+  pl.tiles_per_wg = (int)e2e::cdivll(total_tiles, wgs);
+  if (pl.tiles_per_wg < 4) pl.tiles_per_wg = 4;
+  pl.wgs = (unsigned)e2e::cdivll(total_tiles, pl.tiles_per_wg);
+}
+
+static CtTilePlan plan_convT_fwd(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw, bool words) {
+  CtTilePlan pl{};
+  const long long spatial = (long long)D * H * W;
+  const int kt = kd * kh * kw;
+  const long long total_tiles = (spatial / 32) * B;
+  // the forward GEMM has the row-tile path only (W % 32 == 0) and keeps all of Cin in a wave's registers
+  if (!(ct_bf3_env() && ct_gemm_shape(spatial, W, kd, kh, kw) && W % 32 == 0 && Cin <= 256 && total_tiles >= 256)) {
+    pl.path = CT_PLAIN;
+    pl.vpl = spatial >= 4096 ? (kt <= 4 ? 4 : 2) : 1;
+    return pl;
+  }
+  pl.path = CT_SPLIT;
+  pl.np = ct_pieces(words);
+  pl.nkb = Cin <= 64 ? 2 : (Cin <= 128 ? 4 : 8);
+  const int cols_per_wg = 4 * (8 / pl.nkb) * 16;
+  pl.cgroups = e2e::cdiv(Cout * kt, cols_per_wg);
+  // two 4-wave workgroups per CU, one round; the fp16 two-piece form with <= 64 input channels needs 164 registers: THREE
+  // workgroups per CU, i.e. half again as many requests in flight on a kernel bound by the CU's request path (64 -> 32 @64^3 x 2:
+  // 0.189 -> 0.165 ms; 1024 workgroups 0.193; the 128-channel form does not move: profiles/r06_kbench_convt.txt)
+  ct_tile_grid(pl, total_tiles, (pl.np == 2 && pl.nkb == 2) ? 768 : 512);
+  return pl;
+}
+
+static CtTilePlan plan_convT_dgrad(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw, bool words) {
+  CtTilePlan pl{};
+  const long long spatial = (long long)D * H * W;
+  const long long total_tiles = e2e::cdivll(spatial, 32) * B;
+  const int min_tiles = 256;                                // 256 tiles (16^3 x 2) still win over the gather kernel, 64 do not
+  if (!(ct_gemm_shape(spatial, W, kd, kh, kw) && total_tiles >= min_tiles)) {
+    pl.path = CT_PLAIN;
+    return pl;
+  }
+  // dense GEMM on the matrix cores for the large planes; the split-operand kernel has the row-tile path only, and
+  // E2E_CT_BF3=0 keeps the fp32 matrix instructions
+  pl.path = (ct_bf3_env() && W % 32 == 0) ? CT_SPLIT : CT_FP32;
+  pl.np = ct_pieces(words);
+  pl.cgroups = e2e::cdiv(Cin, 64);
+  ct_tile_grid(pl, total_tiles, 512);   // two 4-wave workgroups fit a CU (218 VGPRs): exactly one round (768: 0.174 -> 0.203 ms)
+  return pl;
+}
+
+// What e2e_convT_wgrad_ws_bytes and e2e_convT_wgrad share: the launch writes `slabs` slabs of Cin x Cout x kt floats into a
+// workspace that carries no size, so the size query is this plan's slab count and nothing else.
+struct CtWgPlan {
+  CtPath path;
+  int ncb;               // 32-channel input blocks per workgroup
+  int cgroups, pairs;    // input-channel groups; launch grid y
+  int tiles_per_chunk;
+  int slabs;             // launch grid x = slabs the main kernel writes = slabs the reduction reads
+};
+static CtWgPlan plan_convT_wgrad(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw) {
+  CtWgPlan pl{};
+  const long long spatial = (long long)D * H * W;
+  const bool mfma = ct_gemm_shape(spatial, W, kd, kh, kw);
+  pl.path = !mfma ? CT_PLAIN : (ct_bf3_env() ? CT_SPLIT : CT_FP32);
+  pl.ncb = (mfma && Cin > 32) ? 2 : 1;
+  pl.cgroups = e2e::cdiv(Cin, 32 * pl.ncb);
+  pl.pairs = pl.cgroups * e2e::cdiv(Cout, 32);
+  // aim at ~256 workgroups (one 84 KB workgroup per CU, equal work each) and keep the slabs few: every chunk is a slab the
+  // reduction has to read (1024 chunks cost 14 % more on the 64 -> 32 @64^3 layer); at least 8 tiles per chunk.  Tiles are
+  // WG_TV = 64 voxels on every path: 32-voxel tiles of the bf16x3 weight gradient, two workgroups per CU, were measured
+  // SLOWER than one workgroup per CU with 64-voxel tiles on every level but the 8^3 one (0.215 -> 0.27 ms at 64 -> 32 @64^3,
+  // profiles/r04_convt_wgrad_tiles.txt).
+  pl.slabs = e2e::split_tiles(e2e::cdivll(spatial, WG_TV) * B, pl.pairs, 256, 8, &pl.tiles_per_chunk);
+  return pl;
+}
+
+// ---- entry points: validate, plan, note, launch ---------------------------------------------------------------------------
 extern "C" int e2e_convT_fwd(const float* x, const float* scale, const float* shift, float slope, const float* w,
                              const unsigned* live, float* y, int B, int Cin, int Cout, int D, int H, int W, int kd,
                              int kh, int kw, const unsigned* x_absmax, const unsigned* w_absmax, void* stream) {
@@ -1326,50 +1321,23 @@ extern "C" int e2e_convT_fwd(const float* x, const float* scale, const float* sh
   E2E_REQUIRE((long long)D * H * W * kd * kh * kw < (1ll << 31), "convT_fwd: a sample must have fewer than 2^31 output voxels");
   E2E_REQUIRE((scale == nullptr) == (shift == nullptr), "convT_fwd: scale/shift must both be given");
   hipStream_t st = (hipStream_t)stream;
-  const long long spatial = (long long)D * H * W;
-  const int kt = kd * kh * kw;
-  const int kdh = kd * kh;
-  if (ct_bf3_env() && kw == 2 && (kdh == 2 || kdh == 4) && W % 32 == 0 && Cin <= 256 && (spatial / 32) * B >= 256) {
-    const int nkb = Cin <= 64 ? 2 : (Cin <= 128 ? 4 : 8);
-    const int cols_per_wg = 4 * (8 / nkb) * 16;
-    const int cgroups = e2e::cdiv(Cout * kt, cols_per_wg);
-    const long long total_tiles = (spatial / 32) * B;
-    const bool h2 = ct_h2_env() && x_absmax != nullptr && w_absmax != nullptr;
-    // two 4-wave workgroups per CU, one round; the fp16 two-piece form with <= 64 input channels needs 164 registers: THREE
-    // workgroups per CU, i.e. half again as many requests in flight on a kernel bound by the CU's request path (64 -> 32 @64^3 x 2:
-    // 0.189 -> 0.165 ms; 1024 workgroups 0.193; the 128-channel form does not move: profiles/r06_kbench_convt.txt)
-    long long wgs = ((h2 && nkb == 2) ? 768 : 512) / cgroups;
-    if (wgs < 1) wgs = 1;
-    int tpw = (int)e2e::cdivll(total_tiles, wgs);
-    if (tpw < 4) tpw = 4;
-    dim3 grid((unsigned)e2e::cdivll(total_tiles, tpw), cgroups);
-    e2e::note_kernel("convT_fwd_%s<%d,%d> wgs=%u cgroups=%d tiles_per_wg=%d", h2 ? "h2" : "bf3", kdh, nkb, grid.x, cgroups, tpw);
-#define LAUNCH_F3(KDH, NKB, NP) hipLaunchKernelGGL((convT_fwd_bf3_kernel<KDH, NKB, NP>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y, \
-                                                   B, Cin, Cout, D, H, W, kd, kh, tpw, x_absmax, w_absmax)
-    if (h2) {
-      if (kdh == 4) { if (nkb == 2) LAUNCH_F3(4, 2, 2); else if (nkb == 4) LAUNCH_F3(4, 4, 2); else LAUNCH_F3(4, 8, 2); }
-      else { if (nkb == 2) LAUNCH_F3(2, 2, 2); else if (nkb == 4) LAUNCH_F3(2, 4, 2); else LAUNCH_F3(2, 8, 2); }
-    } else {
-      if (kdh == 4) { if (nkb == 2) LAUNCH_F3(4, 2, 3); else if (nkb == 4) LAUNCH_F3(4, 4, 3); else LAUNCH_F3(4, 8, 3); }
-      else { if (nkb == 2) LAUNCH_F3(2, 2, 3); else if (nkb == 4) LAUNCH_F3(2, 4, 3); else LAUNCH_F3(2, 8, 3); }
-    }
-#undef LAUNCH_F3
+  const CtTilePlan pl = plan_convT_fwd(B, Cin, Cout, D, H, W, kd, kh, kw, x_absmax != nullptr && w_absmax != nullptr);
+  const int kt = kd * kh * kw, kdh = kd * kh, tpw = pl.tiles_per_wg;
+  if (pl.path == CT_SPLIT) {
+    const dim3 grid(pl.wgs, pl.cgroups);
+    e2e::note_kernel("convT_fwd_%s<%d,%d> wgs=%u cgroups=%d tiles_per_wg=%d", pl.np == 2 ? "h2" : "bf3", kdh, pl.nkb, grid.x, pl.cgroups, tpw);
+    with_const<2, 4>(kdh, [&](auto KDH) { with_const<2, 4, 8>(pl.nkb, [&](auto NKB) { with_const<2, 3>(pl.np, [&](auto NP) {
+      hipLaunchKernelGGL((convT_fwd_bf3_kernel<KDH(), NKB(), NP()>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y,
+                         B, Cin, Cout, D, H, W, kd, kh, tpw, x_absmax, w_absmax);
+    }); }); });
     return e2e::check_launch("convT_fwd_bf3_kernel");
   }
-  e2e::note_kernel("convT_fwd_gather<%d,%d>", kt, spatial >= 4096 ? (kt <= 4 ? 4 : 2) : 1);
-  if (spatial >= 4096 && kt <= 4) {
-    dim3 grid((unsigned)e2e::cdivll(spatial, 256 * 4), Cout, B);
-    DISPATCH_KT(kt, hipLaunchKernelGGL((convT_fwd_kernel<KT, 4>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y,
-                                       Cin, Cout, D, H, W, kd, kh, kw));
-  } else if (spatial >= 4096) {
-    dim3 grid((unsigned)e2e::cdivll(spatial, 256 * 2), Cout, B);
-    DISPATCH_KT(kt, hipLaunchKernelGGL((convT_fwd_kernel<KT, 2>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y,
-                                       Cin, Cout, D, H, W, kd, kh, kw));
-  } else {
-    dim3 grid((unsigned)e2e::cdivll(spatial, 256), Cout, B);
-    DISPATCH_KT(kt, hipLaunchKernelGGL((convT_fwd_kernel<KT, 1>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y,
-                                       Cin, Cout, D, H, W, kd, kh, kw));
-  }
+  const dim3 grid((unsigned)e2e::cdivll((long long)D * H * W, 256 * pl.vpl), Cout, B);
+  e2e::note_kernel("convT_fwd_gather<%d,%d>", kt, pl.vpl);
+  with_const<1, 2, 4, 8>(kt, [&](auto KT) { with_const<1, 2, 4>(pl.vpl, [&](auto VPL) {
+    hipLaunchKernelGGL((convT_fwd_kernel<KT(), VPL()>), grid, dim3(256), 0, st, x, scale, shift, slope, w, live, y,
+                       Cin, Cout, D, H, W, kd, kh, kw);
+  }); });
   return e2e::check_launch("convT_fwd_kernel");
 }
 
@@ -1380,77 +1348,32 @@ extern "C" int e2e_convT_dgrad(const float* dy, const float* w, const unsigned* 
   E2E_REQUIRE(check_k(kd, kh, kw), "convT_dgrad: kernel must be in {1,2}^3");
   E2E_REQUIRE((long long)D * H * W * kd * kh * kw < (1ll << 31), "convT_dgrad: a sample must have fewer than 2^31 output voxels");
   hipStream_t st = (hipStream_t)stream;
-  const long long spatial = (long long)D * H * W;
-  // v3 / v4 (dense GEMM on the matrix cores) for the large planes; E2E_CT_BF3=0 keeps the fp32 matrix instructions (v3)
-  const int min_tiles = 256;                                // 256 tiles (16^3 x 2) still win over the gather kernel, 64 do not
-  if (kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0 && e2e::cdivll(spatial, 32) * B >= min_tiles) {
-    const long long total_tiles = e2e::cdivll(spatial, 32) * B;
-    const int cgroups = e2e::cdiv(Cin, 64);
-    const int target = 512;                                 // two 4-wave workgroups fit a CU (218 VGPRs): exactly one round (768: 0.174 -> 0.203 ms)
-    long long wgs = target / cgroups;
-    if (wgs < 1) wgs = 1;
-    int tpw = (int)e2e::cdivll(total_tiles, wgs);
-    if (tpw < 4) tpw = 4;
-    dim3 grid((unsigned)e2e::cdivll(total_tiles, tpw), cgroups);
-    if (ct_bf3_env() && W % 32 == 0) {
-      const bool h2 = ct_h2_env() && w_absmax != nullptr && dy_bound_a != nullptr;
-      e2e::note_kernel("convT_dgrad_%s<%d> wgs=%u cgroups=%d tiles_per_wg=%d", h2 ? "h2" : "bf3", kd * kh, grid.x, cgroups, tpw);
-#define LAUNCH_D3(KDH, NP) hipLaunchKernelGGL((convT_dgrad_bf3_kernel<KDH, NP>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, \
-                                              D, H, W, kd, kh, tpw, w_absmax, dy_bound_a, dy_bound_b)
-      if (h2) { if (kd * kh == 4) LAUNCH_D3(4, 2); else LAUNCH_D3(2, 2); }
-      else { if (kd * kh == 4) LAUNCH_D3(4, 3); else LAUNCH_D3(2, 3); }
-#undef LAUNCH_D3
+  const CtTilePlan pl = plan_convT_dgrad(B, Cin, Cout, D, H, W, kd, kh, kw, w_absmax != nullptr && dy_bound_a != nullptr);
+  const int kdh = kd * kh, tpw = pl.tiles_per_wg;
+  const dim3 grid(pl.wgs, pl.cgroups);
+  switch (pl.path) {
+    case CT_SPLIT:
+      e2e::note_kernel("convT_dgrad_%s<%d> wgs=%u cgroups=%d tiles_per_wg=%d", pl.np == 2 ? "h2" : "bf3", kdh, grid.x, pl.cgroups, tpw);
+      with_const<2, 4>(kdh, [&](auto KDH) { with_const<2, 3>(pl.np, [&](auto NP) {
+        hipLaunchKernelGGL((convT_dgrad_bf3_kernel<KDH(), NP()>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout,
+                           D, H, W, kd, kh, tpw, w_absmax, dy_bound_a, dy_bound_b);
+      }); });
       return e2e::check_launch("convT_dgrad_bf3_kernel");
-    }
-    e2e::note_kernel("convT_dgrad_v3<%d> wgs=%u cgroups=%d tiles_per_wg=%d", kd * kh, grid.x, cgroups, tpw);
-    if (kd * kh == 4)
-      hipLaunchKernelGGL((convT_dgrad_v3_kernel<4>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, D, H, W, kd, kh, tpw);
-    else
-      hipLaunchKernelGGL((convT_dgrad_v3_kernel<2>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, D, H, W, kd, kh, tpw);
-    return e2e::check_launch("convT_dgrad_v3_kernel");
+    case CT_FP32:
+      e2e::note_kernel("convT_dgrad_v3<%d> wgs=%u cgroups=%d tiles_per_wg=%d", kdh, grid.x, pl.cgroups, tpw);
+      with_const<2, 4>(kdh, [&](auto KDH) {
+        hipLaunchKernelGGL((convT_dgrad_v3_kernel<KDH()>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, D, H, W, kd, kh, tpw);
+      });
+      return e2e::check_launch("convT_dgrad_v3_kernel");
+    case CT_PLAIN:
+      break;
   }
-  // v2 needs enough 64-voxel tiles to fill the chip (one workgroup per tile); small planes keep the gather kernel
-  if (kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0 && e2e::cdivll(spatial, 64) * B >= 1024) {
-    const unsigned tiles = (unsigned)(e2e::cdivll(spatial, 64) * B);
-    e2e::note_kernel("convT_dgrad_v2<%d> tiles=%u", kd * kh, tiles);
-    if (kd * kh == 4)
-      hipLaunchKernelGGL((convT_dgrad_v2_kernel<4>), dim3(tiles), dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, D, H, W, kd, kh);
-    else
-      hipLaunchKernelGGL((convT_dgrad_v2_kernel<2>), dim3(tiles), dim3(256), 0, st, dy, w, live_t, dx, accumulate, B, Cin, Cout, D, H, W, kd, kh);
-    return e2e::check_launch("convT_dgrad_v2_kernel");
-  }
-  dim3 grid((unsigned)e2e::cdivll(spatial, 256), Cin, B);
-  e2e::note_kernel("convT_dgrad_gather<%d>", kd * kh * kw);
-  DISPATCH_KT(kd * kh * kw, hipLaunchKernelGGL((convT_dgrad_kernel<KT>), grid, dim3(256), 0, st, dy, w, live_t, dx, accumulate,
-                                               Cin, Cout, D, H, W, kd, kh, kw));
+  e2e::note_kernel("convT_dgrad_gather<%d>", kdh * kw);
+  with_const<1, 2, 4, 8>(kdh * kw, [&](auto KT) {
+    hipLaunchKernelGGL((convT_dgrad_kernel<KT()>), dim3((unsigned)e2e::cdivll((long long)D * H * W, 256), Cin, B), dim3(256), 0, st, dy, w, live_t,
+                       dx, accumulate, Cin, Cout, D, H, W, kd, kh, kw);
+  });
   return e2e::check_launch("convT_dgrad_kernel");
-}
-
-// What e2e_convT_wgrad_ws_bytes and e2e_convT_wgrad share: the launch writes `slabs` slabs of Cin x Cout x kt floats into a
-// workspace that carries no size, so the size query is this plan's slab count and nothing else.
-enum CtWgPath { CT_WG_V1, CT_WG_V2, CT_WG_BF3 };
-struct CtWgPlan {
-  CtWgPath path;
-  int ncb;               // 32-channel input blocks per workgroup
-  int cgroups, pairs;    // input-channel groups; launch grid y
-  int tiles_per_chunk;
-  int slabs;             // launch grid x = slabs the main kernel writes = slabs the reduction reads
-};
-static CtWgPlan plan_convT_wgrad(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw) {
-  CtWgPlan pl{};
-  const long long spatial = (long long)D * H * W;
-  const bool mfma = kw == 2 && (kd * kh == 2 || kd * kh == 4) && (W % 2) == 0 && spatial % 4 == 0;
-  pl.path = !mfma ? CT_WG_V1 : (ct_bf3_env() ? CT_WG_BF3 : CT_WG_V2);
-  pl.ncb = (mfma && Cin > 32) ? 2 : 1;
-  pl.cgroups = e2e::cdiv(Cin, 32 * pl.ncb);
-  pl.pairs = pl.cgroups * e2e::cdiv(Cout, 32);
-  // aim at ~256 workgroups (one 84 KB workgroup per CU, equal work each) and keep the slabs few: every chunk is a slab the
-  // reduction has to read (1024 chunks cost 14 % more on the 64 -> 32 @64^3 layer); at least 8 tiles per chunk
-  // (32-voxel tiles of the bf16x3 weight gradient, two workgroups per CU, were measured SLOWER than one workgroup per CU with
-  // 64-voxel tiles on every level but the 8^3 one -- 0.215 -> 0.27 ms at 64 -> 32 @64^3, profiles/r04_convt_wgrad_tiles.txt --
-  // and removed in round 5)
-  pl.slabs = e2e::split_tiles(e2e::cdivll(spatial, WG_TPX) * B, pl.pairs, 256, 8, &pl.tiles_per_chunk);
-  return pl;
 }
 
 extern "C" long long e2e_convT_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W, int kd, int kh, int kw) {
@@ -1465,37 +1388,31 @@ extern "C" int e2e_convT_wgrad(const float* x, const float* scale, const float* 
   E2E_REQUIRE((long long)D * H * W * kd * kh * kw < (1ll << 31), "convT_wgrad: a sample must have fewer than 2^31 output voxels");
   hipStream_t st = (hipStream_t)stream;
   const CtWgPlan pl = plan_convT_wgrad(B, Cin, Cout, D, H, W, kd, kh, kw);
-  const int kt = kd * kh * kw, kdh = kd * kh, ncb = pl.ncb, tpc = pl.tiles_per_chunk, cgroups = pl.cgroups;
+  const int kt = kd * kh * kw, kdh = kd * kh, tpc = pl.tiles_per_chunk, cgroups = pl.cgroups;
+  const int np = ct_pieces(x_absmax != nullptr && dy_bound_a != nullptr);
   float* slab = reinterpret_cast<float*>(ws);
   const dim3 grid(pl.slabs, pl.pairs);
   switch (pl.path) {
-    case CT_WG_BF3: {
-      const bool h2 = ct_h2_env() && x_absmax != nullptr && dy_bound_a != nullptr;
-      e2e::note_kernel("convT_wgrad_%s<%d,%d> chunks=%d pairs=%d", h2 ? "h2" : "bf3", kdh, ncb, pl.slabs, pl.pairs);
-#define LAUNCH_B3(KDH, NCB, TPX, NP) hipLaunchKernelGGL((convT_wgrad_bf3_kernel<KDH, NCB, TPX, NP>), grid, dim3(256 * NCB), 0, st, x, scale, shift, \
-                                                        slope, dy, slab, B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups, x_absmax, dy_bound_a, dy_bound_b)
-      if (h2) {
-        if (kdh == 4) { if (ncb == 2) LAUNCH_B3(4, 2, 64, 2); else LAUNCH_B3(4, 1, 64, 2); }
-        else { if (ncb == 2) LAUNCH_B3(2, 2, 64, 2); else LAUNCH_B3(2, 1, 64, 2); }
-      } else {
-        if (kdh == 4) { if (ncb == 2) LAUNCH_B3(4, 2, 64, 3); else LAUNCH_B3(4, 1, 64, 3); }
-        else { if (ncb == 2) LAUNCH_B3(2, 2, 64, 3); else LAUNCH_B3(2, 1, 64, 3); }
-      }
-#undef LAUNCH_B3
+    case CT_SPLIT:
+      e2e::note_kernel("convT_wgrad_%s<%d,%d> chunks=%d pairs=%d", np == 2 ? "h2" : "bf3", kdh, pl.ncb, pl.slabs, pl.pairs);
+      with_const<2, 4>(kdh, [&](auto KDH) { with_const<1, 2>(pl.ncb, [&](auto NCB) { with_const<2, 3>(np, [&](auto NP) {
+        hipLaunchKernelGGL((convT_wgrad_bf3_kernel<KDH(), NCB(), NP()>), grid, dim3(256 * NCB()), 0, st, x, scale, shift, slope, dy, slab,
+                           B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups, x_absmax, dy_bound_a, dy_bound_b);
+      }); }); });
       break;
-    }
-    case CT_WG_V2:
-      e2e::note_kernel("convT_wgrad_v2<%d,%d> chunks=%d pairs=%d", kdh, ncb, pl.slabs, pl.pairs);
-#define LAUNCH_V2(KDH, NCB) hipLaunchKernelGGL((convT_wgrad_v2_kernel<KDH, NCB>), grid, dim3(256 * NCB), 0, st, x, scale, shift, \
-                                               slope, dy, slab, B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups)
-      if (kdh == 4) { if (ncb == 2) LAUNCH_V2(4, 2); else LAUNCH_V2(4, 1); }
-      else { if (ncb == 2) LAUNCH_V2(2, 2); else LAUNCH_V2(2, 1); }
-#undef LAUNCH_V2
+    case CT_FP32:
+      e2e::note_kernel("convT_wgrad_v2<%d,%d> chunks=%d pairs=%d", kdh, pl.ncb, pl.slabs, pl.pairs);
+      with_const<2, 4>(kdh, [&](auto KDH) { with_const<1, 2>(pl.ncb, [&](auto NCB) {
+        hipLaunchKernelGGL((convT_wgrad_v2_kernel<KDH(), NCB()>), grid, dim3(256 * NCB()), 0, st, x, scale, shift, slope, dy, slab,
+                           B, Cin, Cout, D, H, W, kd, kh, tpc, cgroups);
+      }); });
       break;
-    case CT_WG_V1:
+    case CT_PLAIN:
       e2e::note_kernel("convT_wgrad_v1<%d> chunks=%d pairs=%d", kt, pl.slabs, pl.pairs);
-      DISPATCH_KT(kt, hipLaunchKernelGGL((convT_wgrad_kernel<KT>), grid, dim3(256), 0, st, x, scale, shift, slope, dy, slab, B,
-                                         Cin, Cout, D, H, W, kd, kh, kw, tpc, pl.slabs));
+      with_const<1, 2, 4, 8>(kt, [&](auto KT) {
+        hipLaunchKernelGGL((convT_wgrad_kernel<KT()>), grid, dim3(256), 0, st, x, scale, shift, slope, dy, slab, B,
+                           Cin, Cout, D, H, W, kd, kh, kw, tpc, pl.slabs);
+      });
       break;
   }
   const int rc = e2e::check_launch("convT_wgrad");

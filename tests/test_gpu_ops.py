@@ -250,6 +250,7 @@ def test_conv133_fwd_bwd(case):
     (2, 20, 70, (32, 32, 34), (1, 2, 2), 0.5, False),      # same path (fp32 matrix instructions: W % 32 != 0), [1,2,2] kernel, three output-channel chunks
     (2, 20, 70, (8, 32, 32), (1, 2, 2), 0.5, False),       # bf16 three-piece data gradient, [1,2,2] kernel, three output-channel chunks
     (1, 136, 24, (8, 32, 32), (2, 2, 2), 0.3, True),       # forward GEMM with eight 32-channel k-blocks (one column tile per wave), ragged Cin
+    (4, 20, 12, (6, 10, 34), (2, 2, 2), 0.5, True),        # 2040 voxels x 4 = exactly the 256-tile GEMM threshold; W % 32 != 0: general tile path, ragged last tile (24 / 56 voxels)
 ])
 def test_convT_fwd_bwd(B, cin, cout, dims, kernel, density, normed):
     from e2enet_medical_amd.engine import UpOp
@@ -518,19 +519,22 @@ def test_conv133_persistent_run_loop_forced():
     assert "passed" in r.stdout
 
 
-@pytest.mark.parametrize("env", [{"E2E_WG_H2": "0"}, {"E2E_WG_BF3": "0"}, {"E2E_CONV_MM": "0"}, {"E2E_MM_GRID": "8"}])
+@pytest.mark.parametrize("env", [{"E2E_WG_H2": "0"}, {"E2E_WG_BF3": "0"}, {"E2E_CONV_MM": "0"}, {"E2E_MM_GRID": "8"},
+                                 {"E2E_CT_BF3": "0"}, {"E2E_CT_H2": "0"}])
 def test_conv133_wgrad_alternative_paths_forced(env):
     """The dense weight gradient of stride-1 planes at least 16 voxels wide runs on the matrix pipe with split fp32 operands
     (conv133_wgrad_bf3v5_kernel<G, NPC>): by default on fp16 two-piece operands (three products), scaled from the max |dy| that
     e2e_in_lrelu_bwd records.  E2E_WG_H2=0 keeps the bf16 three-piece form (six products; also what a caller without the recorded
     maximum gets), E2E_WG_BF3=0 the fp32-MFMA kernels.  E2E_CONV_MM=0: forward / data gradient of the 16 x 32 tile class on the
     round-4 kernels (sparse plan walk, bf16x3 dense kernel) instead of conv133_mm_kernel; E2E_MM_GRID=8: that kernel as eight
-    persistent workgroups (long item runs per workgroup: every pipeline transition).  The knobs are read once per process: run the
-    operator cases and the workspace-bound cases again in a child process."""
+    persistent workgroups (long item runs per workgroup: every pipeline transition).  E2E_CT_BF3=0: the transposed conv on its
+    gather forward and fp32-MFMA gradients (convT_wgrad_v2, convT_dgrad_v3 on row tiles), E2E_CT_H2=0: on the bf16 three-piece
+    forms.  The knobs are read once per process: run the operator cases and the workspace-bound cases again in a child process."""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k",
-                        "test_conv133_fwd_bwd or test_wgrad_stays_inside_the_workspace_it_asked_for", "-p", "no:cacheprovider"],
+                        "test_conv133_fwd_bwd or test_wgrad_stays_inside_the_workspace_it_asked_for or test_convT_fwd_bwd",
+                        "-p", "no:cacheprovider"],
                        env=dict(os.environ, **env), capture_output=True, text=True, timeout=900,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
