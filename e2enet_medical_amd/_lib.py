@@ -235,6 +235,8 @@ SIGNATURES = {
     "e2e_fingerprint_stats": (I, [P, LL, P, I, P, P, P]),
     "e2e_loader_crop_max_batch": (I, []),
     "e2e_loader_crop": (I, [P, I, I, I, I, I, P, P, I, F, F, P]),
+    "e2e_nifti_decode_f32": (I, [P, LL, I, I, I, C.c_double, C.c_double, P, P]),
+    "e2e_nifti_decode_u8": (I, [P, LL, I, I, I, C.c_double, C.c_double, P, P, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
@@ -281,7 +283,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 24          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 25          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -8,7 +8,7 @@ import json
 import os
 import shutil
 
-from . import paths
+from . import nifti, paths
 from .experiment_planning.DatasetAnalyzer import DEFAULT_NUM_THREADS, DatasetAnalyzer
 from .experiment_planning.utils import crop
 from .utilities.task_name_id_conversion import convert_id_to_task_name
@@ -21,7 +21,13 @@ def build_parser():
                         help='host threads that write cropped cases and read them again (at most 16); the GPU work is one process')
     parser.add_argument('--override', action='store_true',
                         help='empty the cropped folder and crop every case again, and recompute the intensity properties')
+    nifti.add_argument(parser)
     return parser
+
+
+def select_reader(args, reader=None):
+    """the ``reader`` the cropping is handed: the caller's; with ``--native_nifti`` and none given, ``nifti.reader``"""
+    return nifti.reader if (args.native_nifti and reader is None) else reader
 
 
 def main(argv=None, reader=None):
@@ -31,7 +37,7 @@ def main(argv=None, reader=None):
         task_name = convert_id_to_task_name(int(task_name))
     raw = os.path.join(paths.nnUNet_raw_data, task_name)
     assert os.path.isfile(os.path.join(raw, "dataset.json")), "dataset.json not found. Expected: %s" % os.path.join(raw, "dataset.json")
-    crop(task_name, args.override, args.tf, reader=reader)
+    crop(task_name, args.override, args.tf, reader=select_reader(args, reader))
     cropped = os.path.join(paths.nnUNet_cropped_data, task_name)
     preprocessed = os.path.join(paths.preprocessing_output_dir, task_name)
     # the intensity properties are collected only when one of the modalities is CT

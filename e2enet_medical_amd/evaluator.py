@@ -123,6 +123,13 @@ def default_reader(path):
     return sitk.GetArrayFromImage(img), tuple(float(v) for v in img.GetSpacing())[::-1]
 
 
+def _decoded(volume):
+    """what a reader returned as the volume: a ``nifti.NiftiRaw`` (the host half of ``nifti.evaluator_reader``, possibly from a
+    read-ahead thread) is decoded here, on the calling thread, into a device uint8 tensor; anything else is the volume"""
+    from . import nifti
+    return nifti.decode_u8(volume) if isinstance(volume, nifti.NiftiRaw) else volume
+
+
 class NiftiEvaluator(Evaluator):
     """``Evaluator`` whose test and reference are file names, read through ``reader(path) -> (array, spacing or None)``"""
 
@@ -136,7 +143,7 @@ class NiftiEvaluator(Evaluator):
         """``loaded``: what ``reader(test)`` returned, when somebody read the file ahead"""
         if test is not None:
             array, self.test_spacing = self.reader(test) if loaded is None else loaded
-            super().set_test(array)
+            super().set_test(_decoded(array))
         else:
             self.test_spacing = None
             super().set_test(test)
@@ -144,7 +151,7 @@ class NiftiEvaluator(Evaluator):
     def set_reference(self, reference, loaded=None):
         if reference is not None:
             array, self.reference_spacing = self.reader(reference) if loaded is None else loaded
-            super().set_reference(array)
+            super().set_reference(_decoded(array))
         else:
             self.reference_spacing = None
             super().set_reference(reference)
@@ -231,15 +238,18 @@ def pair_files(folder_with_gts, folder_with_predictions):
     return pairs
 
 
-def evaluate_folder(folder_with_gts, folder_with_predictions, labels, num_threads=8, **metric_kwargs):
-    """writes summary.json into ``folder_with_predictions`` and returns the scores"""
+def evaluate_folder(folder_with_gts, folder_with_predictions, labels, num_threads=8, reader=None, **metric_kwargs):
+    """writes summary.json into ``folder_with_predictions`` and returns the scores.  ``reader``: the ``NiftiEvaluator``'s (None:
+    ``default_reader``)"""
     pairs = pair_files(folder_with_gts, folder_with_predictions)
-    return aggregate_scores(pairs, json_output_file=os.path.join(folder_with_predictions, "summary.json"), num_threads=num_threads,
+    evaluator = NiftiEvaluator if reader is None else NiftiEvaluator(reader=reader)
+    return aggregate_scores(pairs, evaluator=evaluator, json_output_file=os.path.join(folder_with_predictions, "summary.json"), num_threads=num_threads,
                             labels=labels, **metric_kwargs)
 
 
-def main(argv=None):
+def build_parser():
     import argparse
+    from . import nifti
     parser = argparse.ArgumentParser(description="Evaluates the segmentations located in the folder pred. Output of this script is a json "
                                                  "file. At the very bottom of the json file is going to be a 'mean' entry with averages "
                                                  "metrics across all cases")
@@ -252,13 +262,26 @@ def main(argv=None):
     parser.add_argument("--nsd_tolerance", type=float, default=None, metavar="MM", help="add the Normalized Surface Dice at this "
                                                                                         "tolerance (implies --advanced)")
     parser.add_argument("-tf", type=int, default=8, metavar="N", help="host threads that read files ahead of the device (default 8)")
-    args = parser.parse_args(argv)
+    nifti.add_argument(parser)
+    return parser
+
+
+def select_reader(args):
+    """the ``reader`` handed to ``evaluate_folder``: None (``default_reader``); with ``--native_nifti``, ``nifti.evaluator_reader``"""
+    if args.native_nifti:
+        from . import nifti
+        return nifti.evaluator_reader
+    return None
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     kw = {}
     if args.advanced or args.nsd_tolerance is not None:
         kw["advanced"] = True
     if args.nsd_tolerance is not None:
         kw["nsd_tolerance"] = args.nsd_tolerance
-    return evaluate_folder(args.ref, args.pred, tuple(args.l), num_threads=args.tf, **kw)
+    return evaluate_folder(args.ref, args.pred, tuple(args.l), num_threads=args.tf, reader=select_reader(args), **kw)
 
 
 if __name__ == "__main__":

@@ -232,13 +232,23 @@ def build_parser():
                         help="postprocessing.json of the ensemble; the raw results then go to <output_folder>/not_postprocessed")
     parser.add_argument('--npz', action="store_true", required=False,
                         help="also store the averaged probabilities (<case>.npz) and the list of properties (<case>.pkl)")
+    from .. import nifti
+    nifti.add_argument(parser)
     return parser
+
+
+def select_writer(args, writer=None):
+    """the ``writer`` handed to ``merge``: the caller's; with ``--native_nifti`` and none given, ``nifti.writer``"""
+    if args.native_nifti and writer is None:
+        from .. import nifti
+        return nifti.writer
+    return writer
 
 
 def main(argv=None, writer=None):
     args = build_parser().parse_args(argv)
     merge(args.folders, args.output_folder, args.threads, override=True, postprocessing_file=args.postprocessing_file,
-          store_npz=args.npz, writer=writer)
+          store_npz=args.npz, writer=select_writer(args, writer))
 
 
 if __name__ == "__main__":

@@ -210,10 +210,18 @@ def load_case(data_files, seg_file, reader, what):
     return data, None, properties
 
 
+def _as_float32(a):
+    """what a reader returned as fp32: a device tensor stays where it is (``ImageCropper.crop`` and ``to_device`` take one), anything
+    else becomes a numpy array"""
+    if hasattr(a, "is_cuda"):
+        return a.float()
+    return np.asarray(a, dtype=np.float32)
+
+
 def load_seg_with_reader(seg_file, reader):
     """``seg [1, X, Y, Z]`` fp32 of a segmentation file: ``reader`` is handed the one-file list and the first channel is kept"""
     seg, _ = reader([seg_file])
-    return np.asarray(seg[0:1], dtype=np.float32)
+    return _as_float32(seg[0:1])
 
 
 def load_case_with_reader(data_files, seg_file, reader, what):
@@ -222,7 +230,7 @@ def load_case_with_reader(data_files, seg_file, reader, what):
     assert isinstance(data_files, (list, tuple)), "case must be either a list or a tuple"
     reader = require_reader(reader, what)
     data, properties = reader(list(data_files))
-    data = np.asarray(data, dtype=np.float32)
+    data = _as_float32(data)
     properties.setdefault("original_size_of_raw_data", np.array([int(v) for v in data.shape[1:]]))
     properties.setdefault("list_of_data_files", data_files)
     properties["seg_file"] = seg_file

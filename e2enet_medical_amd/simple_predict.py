@@ -6,7 +6,7 @@ over a process group instead).  The input folder holds preprocessed cases (``<ca
 import argparse
 import os
 
-from . import paths
+from . import nifti, paths
 from .inference.predict import predict_from_folder
 from .utilities.task_name_id_conversion import convert_id_to_task_name
 
@@ -40,12 +40,22 @@ def build_parser():
                         default='model_final_checkpoint')
     parser.add_argument('--disable_mixed_precision', default=False, action='store_true', required=False)
     parser.add_argument('--Tconv', type=str, required=False, default='shiftConvPP', help='ori;shiftConvPP')
+    nifti.add_argument(parser)
     return parser
+
+
+def select_callbacks(args, reader=None, writer=None):
+    """``(reader, writer)`` handed to ``predict_from_folder``: the caller's; with ``--native_nifti``, ``nifti.reader`` and
+    ``nifti.writer`` where none was given"""
+    if args.native_nifti:
+        return (nifti.reader if reader is None else reader), (nifti.writer if writer is None else writer)
+    return reader, writer
 
 
 def main(argv=None, reader=None, writer=None):
     """``reader`` / ``writer``: handed to ``predict_from_folder`` unchanged (None: its SimpleITK defaults)"""
     args = build_parser().parse_args(argv)
+    reader, writer = select_callbacks(args, reader, writer)
     folds, lowres_segmentations, all_in_gpu, model = args.folds, args.lowres_segmentations, args.all_in_gpu, args.model
     task_name = args.task_name
     args.chk = f"{args.Tconv}_{args.chk}"                       # simple_predict.py:152

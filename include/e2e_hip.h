@@ -754,6 +754,26 @@ int e2e_loader_crop_max_batch(void);
 int e2e_loader_crop(const e2e_loader_rec_t* recs, int B, int C, int pd, int ph, int pw, float* out_data, float* out_seg,
                     int data_mode, float data_fill, float seg_fill, void* stream);
 
+/* ---- N4: decoding of NIfTI-1 voxel payloads (csrc/nifti.hip) -------------------------------------------------------------
+ * Replaces: the host pass of e2enet/preprocessing/cropping.py:61-81 (sitk.GetArrayFromImage, np.vstack, astype(np.float32)) and
+ * the upload of its fp32 copy.  raw: nvox elements on the device exactly as the file stores them (the host has inflated the file
+ * and parsed the header, e2enet_medical_amd/nifti.py), aligned to the element size.  datatype: the NIfTI-1 code, one of 2 uint8,
+ * 4 int16, 8 int32, 16 float32, 64 float64, 256 int8, 512 uint16, 768 uint32, 1024 int64, 1280 uint64.  swap != 0: the bytes of
+ * every element are reversed first (a file of the other byte order).
+ *   scale == 0: out[i] = the element converted with one rounding to nearest even (ndarray.astype(np.float32)): the 32- and 64-bit
+ *     integers directly, not through fp64; float32 bit for bit; NaN and Inf of float64 pass through.  slope and inter are not read.
+ *   scale != 0: out[i] = fp32(fp64(element) * slope + inter), the product and the sum each rounded to fp64 (never an FMA), then one
+ *     rounding to fp32: numpy's (raw.astype(np.float64) * slope + inter).astype(np.float32).
+ *   decode_f32: out fp32, nvox elements (a channel of a [C, Z, Y, X] tensor: only these nvox floats are written).
+ *   decode_u8: out uint8; the fp32 value above when it is a whole number in [0, 255], else 0 and *rejected (device, 64-bit, zeroed
+ *     by the caller) is incremented: one integer atomic per workgroup that rejected something, the same total on every run.
+ * elsize bytes read and 4 or 1 written per voxel.  Refused with E2E_ERR_ARG before anything is launched: another datatype, nvox < 0
+ * or > 2^40, a null pointer, raw not aligned to the element size.  nvox == 0 launches nothing.                                  */
+int e2e_nifti_decode_f32(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter, float* out,
+                         void* stream);
+int e2e_nifti_decode_u8(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
+                        unsigned char* out, unsigned long long* rejected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
