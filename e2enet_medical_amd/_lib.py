@@ -206,6 +206,9 @@ SIGNATURES = {
     "e2e_surface_border_set": (I, [P, P, P, P, I, I, I, P]),
     "e2e_cc_ws_bytes": (LL, [I, I, I]),
     "e2e_cc_remove_all_but_largest": (I, [P, I, I, I, P, C.c_double, C.c_double, P, P, P]),
+    "e2e_ct_ws_bytes": (LL, [I, I, I]),
+    "e2e_ct_label": (I, [P, P, I, I, I, P, P, P, P]),
+    "e2e_ct_emit": (I, [P, I, I, I, P, P, LL, LL, P, LL, LL, P]),
     "e2e_pp_nonzero_ws_bytes": (LL, [I, I, I]),
     "e2e_pp_nonzero_mask": (I, [P, I, I, I, I, P, P, P, P]),
     "e2e_pp_bbox": (I, [P, I, I, I, I, P, P]),
@@ -241,7 +244,7 @@ SIGNATURES = {
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
               "e2e_convT_wgrad_ws_bytes", "e2e_conv133_input_ranges_ws_bytes", "e2e_in_lrelu_bwd_ws_doubles", "e2e_head1x1_wgrad_ws_bytes", "e2e_loss_ws_bytes", "e2e_aug_stats_ws_bytes",
-              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
+              "e2e_surface_max_line", "e2e_surface_distances_ws_bytes", "e2e_cc_ws_bytes", "e2e_ct_ws_bytes", "e2e_pp_nonzero_ws_bytes", "e2e_pp_label_hist_bins",
               "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes",
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
               "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
@@ -283,7 +286,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 25          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 26          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -7,6 +7,8 @@
 //   merge_back  every mask voxel unites with its mask neighbours at i - W and i - H W: find both roots, atomicMin(&parent[larger
 //               root], smaller root), and go on from the returned value when another thread linked that root first
 //   find_root   after merge_back has run to its end (a kernel boundary), the root of i is its component's smallest voxel
+//   init_runs_labelled, merge_back_labelled (at the end of the file): the same two passes where voxels belong together only when
+//               they carry the same non-zero value, so that every class of a set is labelled at once (components.hip, P5)
 //
 // Invariants.
 //   * parent[i] <= i at all times, equality exactly at roots: a link is only ever written by atomicMin with a smaller index, so every
@@ -120,6 +122,69 @@ __device__ __forceinline__ void merge_back(unsigned* parent, unsigned* giveup, u
   const bool left = w > 0u && parent[i - 1u] != NONE;
   if (i % HW >= W && parent[i - W] != NONE && !(left && parent[i - W - 1u] != NONE)) unite(parent, i, i - W, budget, giveup);
   if (i >= HW && parent[i - HW] != NONE && !(left && parent[i - HW - 1u] != NONE)) unite(parent, i, i - HW, budget, giveup);
+}
+
+// ---- labelled variants: every value of a class set is labelled in the same pass (the component table of components.hip) -----
+// value(j) is the voxel's label when it is in the class set and 0 when it is not (0 is never in a set); two voxels belong together
+// only when both carry the same non-zero value.  find_root and unite are the ones above: the invariants hold unchanged, because a
+// link is still only ever written by atomicMin with a smaller index of the same component.
+
+// parent[i] = first voxel of i's run of EQUAL non-zero values along W, NONE where value is 0.  Every thread of the 256-thread block
+// calls it (it votes across the wave); value(j) is asked only for j < V.
+template <class Val>
+__device__ __forceinline__ void init_runs_labelled(Val value, unsigned* __restrict__ parent, unsigned V, unsigned W) {
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  const bool live = i64 < V;
+  const unsigned i = (unsigned)i64;
+  const unsigned base = i - lane;                              // the wave's first voxel (< V whenever any lane is live)
+  const unsigned v = live ? value(i) : 0u;
+  const unsigned left = __shfl_up(v, 1, 64);
+  // a run begins where the row begins or the voxel to the left carries another value; lane 0 always cuts, its run is traced below
+  const unsigned long long cuts = __ballot(lane == 0u || i % W == 0u || left != v);
+  const unsigned v0 = __shfl(v, 0, 64);
+  // where the run that reaches lane 0 begins: the wave steps left through lane 0's row, 64 voxels at a time
+  unsigned start0 = base;
+  if (v0 != 0u) {
+    const unsigned row0 = base - base % W;
+    while (start0 > row0) {
+      const bool valid = start0 - row0 >= 64u - lane;          // start0 - 64 + lane >= row0
+      const bool same = valid && value(start0 - 64u + lane) == v0;
+      const unsigned long long inv = ~__ballot(same);
+      if (inv == 0ull) {
+        start0 -= 64u;
+        continue;
+      }
+      start0 -= (unsigned)__clzll(inv);                        // voxels of lane 0's value directly left of start0
+      break;
+    }
+  }
+  if (live) {
+    unsigned p = NONE;
+    if (v != 0u) {
+      const unsigned long long upto = cuts & (~0ull >> (63u - lane));     // cuts at or left of this lane; bit 0 is always set
+      const unsigned c = 63u - (unsigned)__clzll(upto);
+      p = c ? base + c : start0;
+    }
+    parent[i] = p;
+  }
+}
+
+// Unite voxel i = blockIdx.x * 256 + threadIdx.x with the neighbours one row and one plane back that carry i's value.  With
+// x[i] == x[i - s], the union with (i - s) is implied, and skipped, when x[i - 1] == x[i] and x[i - s - 1] == x[i - s] (all four in
+// the set): i ~ i - 1 and i - s ~ i - s - 1 by their runs of equal values, and i - 1 ~ i - s - 1 by the same rule one voxel to
+// the left, where the four values are again equal.
+template <class Val>
+__device__ __forceinline__ void merge_back_labelled(Val value, unsigned* parent, unsigned* giveup, unsigned V, unsigned W, unsigned HW) {
+  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  if (i64 >= V) return;
+  const unsigned i = (unsigned)i64;
+  const unsigned v = value(i);
+  if (v == 0u) return;
+  unsigned budget = V + 64u;
+  const bool left = i % W > 0u && value(i - 1u) == v;
+  if (i % HW >= W && value(i - W) == v && !(left && value(i - W - 1u) == v)) unite(parent, i, i - W, budget, giveup);
+  if (i >= HW && value(i - HW) == v && !(left && value(i - HW - 1u) == v)) unite(parent, i, i - HW, budget, giveup);
 }
 
 }  // namespace uf

@@ -281,7 +281,7 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
         else:
             print("WARNING! Cannot run postprocessing because the postprocessing file is missing. Make sure to run "
                   "consolidate_folds in the output folder of the model first!\nThe folder you need to run this in is "
-                  "%s" % model)
+                  "%s\n(python -m e2enet_medical_amd.postprocessing.consolidate_postprocessing -f %s)" % (model, model))
 
     def cases():
         for c, out in zip(case_ids, output_files):

@@ -5,8 +5,11 @@ whole volume per class entry plus one ``(lmap == id).sum()`` per object.
   remove_all_but_the_largest_connected_component   :50-107, same name, arguments and return value
   load_postprocessing                              :110-121
   determine_postprocessing                         :124-399, the same search on the in-memory cases ``validate()`` holds (no
-                                                   temp folders, no NIfTI round trips, no worker pool)
+                                                   temp folders, no NIfTI round trips, no worker pool); called with a folder
+                                                   name, the reference's folder form: one component table per case
+                                                   (component_table.py) instead of one removed volume per case and sweep
   apply_postprocessing                             what ``load_remove_save`` (:32-47) does to one volume
+  apply_postprocessing_to_folder                   :402-423
 
 The label volume is uploaded once per call; a class entry's mask is formed on load from a 256-bit class set, so a joint region such
 as (1, 2, 3) needs no mask volume.  Sizes are ``voxels * volume_per_voxel`` in fp64, which is numpy's ``int64 * float``.  There is
@@ -144,9 +147,25 @@ def _fold_sizes(results):
     return max_size_removed, min_size_kept
 
 
-def determine_postprocessing(cases, classes, base, raw_subfolder_name="validation_raw", final_subf_name="validation_final",
-                             dice_threshold=0, advanced_postprocessing=False, pp_filename="postprocessing.json", writer=None,
-                             remove=None):
+def determine_postprocessing(*args, **kwargs):
+    """Reference :124-399, in two forms told apart by the first argument.
+
+    A folder name (``str``): the reference's own signature, ``determine_postprocessing(base, gt_labels_folder, raw_subfolder_name=
+    "validation_raw", temp_folder="temp", final_subf_name="validation_final", processes=8, dice_threshold=0, debug=False,
+    advanced_postprocessing=False, pp_filename="postprocessing.json", reader=None, writer=None)``: the search over the label files of
+    ``<base>/<raw_subfolder_name>``, from one component table per case (``determine_postprocessing_folder``).
+
+    A list of cases: ``determine_postprocessing(cases, classes, base, ...)``, the search on the volumes ``validate()`` holds in
+    memory (``determine_postprocessing_in_memory``), unchanged."""
+    first = args[0] if args else kwargs.get("cases", kwargs.get("base"))
+    if isinstance(first, str):
+        return determine_postprocessing_folder(*args, **kwargs)
+    return determine_postprocessing_in_memory(*args, **kwargs)
+
+
+def determine_postprocessing_in_memory(cases, classes, base, raw_subfolder_name="validation_raw", final_subf_name="validation_final",
+                                       dice_threshold=0, advanced_postprocessing=False, pp_filename="postprocessing.json", writer=None,
+                                       remove=None):
     """Reference :124-399 on in-memory cases: decide for which classes removing all but the largest component improves the mean
     Dice, apply that decision to every case, and record it.
 
@@ -267,3 +286,165 @@ def determine_postprocessing(cases, classes, base, raw_subfolder_name="validatio
         json.dump(pp_results, f, sort_keys=True, indent=4)
     print("done")
     return pp_results, final
+
+
+# ---- the folder forms: label files in, label files out -------------------------------------------------------------------------
+def default_reader(path):
+    """``reader(path) -> (volume, properties or None)`` of the folder functions.  ``.npy`` is read natively and has no geometry
+    (``volume_per_voxel`` 1); everything else goes through SimpleITK, the geometry under the reference's ``itk_*`` keys."""
+    if path.endswith(".npy"):
+        return np.load(path), None
+    try:
+        import SimpleITK as sitk
+    except ImportError:
+        raise ImportError("reading %s needs SimpleITK (only .npy volumes are read without it): pass reader=native_reader and "
+                          "writer=nifti.writer, or --native_nifti on the command line" % path)
+    img = sitk.ReadImage(path)
+    return sitk.GetArrayFromImage(img), {'itk_spacing': img.GetSpacing(), 'itk_origin': img.GetOrigin(), 'itk_direction': img.GetDirection()}
+
+
+def native_reader(path):
+    """``default_reader`` with this package's own NIfTI-1 code: the host half (header and gzip; safe in a read-ahead thread) returns
+    the ``nifti.NiftiRaw``, which the thread that owns the GPU decodes to a device uint8 tensor"""
+    from .. import nifti
+    if path.endswith(".npy"):
+        return np.load(path), None
+    raw = nifti.read_raw(path)
+    return raw, nifti.properties_of(raw)
+
+
+def default_writer(seg, path, properties):
+    """``writer(seg_uint8, path, properties)``: ``.npy`` natively, everything else through SimpleITK with the input file's geometry"""
+    if path.endswith(".npy"):
+        np.save(path, seg)
+        return
+    try:
+        import SimpleITK as sitk
+    except ImportError:
+        raise ImportError("writing %s needs SimpleITK: pass writer=nifti.writer, or --native_nifti on the command line" % path)
+    img = sitk.GetImageFromArray(np.asarray(seg).astype(np.uint8))
+    if properties is not None:
+        img.SetSpacing(properties['itk_spacing'])
+        img.SetOrigin(properties['itk_origin'])
+        img.SetDirection(properties['itk_direction'])
+    sitk.WriteImage(img, path)
+
+
+def label_files(folder):
+    """the label files of a folder, sorted: ``.nii.gz``, or ``.npy`` when the folder holds no ``.nii.gz`` (``pair_files``' rule)"""
+    files = sorted(f for f in os.listdir(folder) if os.path.isfile(os.path.join(folder, f)))
+    suffix = ".nii.gz" if any(f.endswith(".nii.gz") for f in files) else ".npy"
+    return [f for f in files if f.endswith(suffix)]
+
+
+def _volume_per_voxel(properties):
+    """reference :38, ``np.prod(img.GetSpacing())``; a file without geometry: 1"""
+    if properties is None or properties.get('itk_spacing') is None:
+        return 1.0
+    return float(np.prod(properties['itk_spacing'], dtype=np.float64))
+
+
+def _cases_of(pairs, reader, num_threads, on_device):
+    """yields ``(prediction, ground truth or None, properties of the prediction)`` per pair of file names, read ``num_threads`` files
+    ahead; ``on_device``: a pair comes as two device uint8 tensors of one shape, each uploaded once"""
+    from ..evaluator import _read_ahead, _decoded
+    from ..evaluation.evaluator import _device_pair
+    for _, _, (pred, properties), gt in _read_ahead(pairs, reader, num_threads):
+        pred, gt = _decoded(pred), (None if gt is None else _decoded(gt[0]))
+        if on_device and gt is not None:
+            pred, gt = _device_pair(pred, gt)
+        yield pred, gt, properties
+
+
+def _host_u8(seg):
+    return seg.cpu().numpy() if hasattr(seg, "cpu") else np.asarray(seg)
+
+
+def determine_postprocessing_folder(base, gt_labels_folder, raw_subfolder_name="validation_raw", temp_folder="temp",
+                                    final_subf_name="validation_final", processes=8, dice_threshold=0, debug=False,
+                                    advanced_postprocessing=False, pp_filename="postprocessing.json", reader=None, writer=None,
+                                    table=None, remove=None):
+    """Reference :124-399 on folders, with the reference's arguments: decide from the raw predictions in
+    ``<base>/<raw_subfolder_name>`` and the ground truths of the same names in ``gt_labels_folder`` for which classes removing all
+    but the largest component improves the mean Dice, apply the decision to every raw prediction, and record it.
+
+    The classes and ``num_samples`` come from ``<base>/<raw_subfolder_name>/summary.json``.  Every file is read twice and no
+    intermediate volume is written: the first pass (``processes`` host threads read ahead of the device) builds one component table
+    per case (``component_table``), the search is arithmetic on the tables (``component_table.search``), the second pass applies
+    the decision with the device removal and writes ``<base>/<final_subf_name>/<name>`` through ``writer(seg, path, properties)``
+    with the input file's geometry, scored into ``<base>/<final_subf_name>/summary.json``.  ``<base>/<pp_filename>`` has the
+    reference's keys.  ``debug``: the two intermediate summary.json files stay, in ``<base>/<temp_folder>_allClasses`` and
+    ``<base>/<temp_folder>_perClass``.
+
+    ``reader(path) -> (volume, properties or None)``: default ``default_reader``; ``native_reader`` with ``writer=nifti.writer`` reads
+    and writes ``.nii.gz`` without SimpleITK.  ``table(pred, gt, classes)`` and ``remove``: the table builder and the removal
+    (defaults: the device ones); with a ``table`` of the caller's the volumes stay where the reader put them and are scored on the
+    host.  Returns ``pp_results``."""
+    import shutil
+    from .component_table import component_table, search
+    from ..evaluation.evaluator import evaluate_pair, evaluate_pair_device, summarise_scores
+    raw_folder, final_folder = os.path.join(base, raw_subfolder_name), os.path.join(base, final_subf_name)
+    assert os.path.isfile(os.path.join(raw_folder, "summary.json")), "join(base, raw_subfolder_name) does not contain a summary.json"
+    with open(os.path.join(raw_folder, "summary.json"), 'r') as f:
+        summary = json.load(f)['results']
+    classes = [int(i) for i in summary['mean'].keys() if int(i) != 0]
+    on_device = table is None
+    table = component_table if table is None else table
+    remove = remove_all_but_the_largest_connected_component if remove is None else remove
+    reader = default_reader if reader is None else reader
+    writer = default_writer if writer is None else writer
+    fnames = label_files(raw_folder)
+    pairs = [(os.path.join(raw_folder, f), os.path.join(gt_labels_folder, f)) for f in fnames]
+    missing = [g for _, g in pairs if not os.path.isfile(g)]
+    if missing:
+        raise FileNotFoundError("%d ground-truth file(s) missing: %s" % (len(missing), ", ".join(missing)))
+    temp = {"allClasses": os.path.join(base, temp_folder + "_allClasses"), "perClass": os.path.join(base, temp_folder + "_perClass")}
+    for folder in temp.values():
+        if os.path.isdir(folder):
+            shutil.rmtree(folder)
+        if debug:
+            os.makedirs(folder)
+    os.makedirs(final_folder, exist_ok=True)
+
+    tables, vpv = [], []
+    for pred, gt, properties in _cases_of(pairs, reader, processes, on_device):
+        tables.append(table(pred, gt, classes))
+        vpv.append(_volume_per_voxel(properties))
+    pp_results = search(tables, vpv, classes, dice_threshold, advanced_postprocessing,
+                        names=pairs,                # (the raw file: the volume a record stands for is never written)
+                        json_files={k: os.path.join(v, "summary.json") for k, v in temp.items()} if debug else None)
+    pp_results['num_samples'] = len(summary['all'])
+    pp_results['validation_raw'] = raw_subfolder_name
+    pp_results['validation_final'] = final_subf_name
+
+    # the decision applied to the raw predictions
+    records = []
+    cases = _cases_of(pairs, reader, processes, on_device)
+    for f, (_, gt_name), v, (pred, gt, properties) in zip(fnames, pairs, vpv, cases):
+        final = remove(pred, pp_results['for_which_classes'], v, pp_results['min_valid_object_sizes'])[0]
+        res = (evaluate_pair_device if on_device else evaluate_pair)(final, gt, classes)
+        res["test"], res["reference"] = os.path.join(final_folder, f), gt_name
+        records.append(res)
+        writer(_host_u8(final), os.path.join(final_folder, f), properties)
+    summarise_scores(records, json_output_file=os.path.join(final_folder, "summary.json"), json_author="Fabian")
+    pp_results['min_valid_object_sizes'] = str(pp_results['min_valid_object_sizes'])
+    with open(os.path.join(base, pp_filename), 'w') as f:
+        json.dump(pp_results, f, sort_keys=True, indent=4)
+    print("done")
+    return pp_results
+
+
+def apply_postprocessing_to_folder(input_folder, output_folder, for_which_classes, min_valid_object_size=None, num_processes=8,
+                                   reader=None, writer=None, remove=None):
+    """Reference :402-423: the removal applied to every label file of ``input_folder``, written under the same name into
+    ``output_folder`` with the input file's geometry.  ``num_processes`` host threads read ahead of the device; ``reader``,
+    ``writer``, ``remove`` as in ``determine_postprocessing_folder``."""
+    remove = remove_all_but_the_largest_connected_component if remove is None else remove
+    reader = default_reader if reader is None else reader
+    writer = default_writer if writer is None else writer
+    os.makedirs(output_folder, exist_ok=True)
+    fnames = label_files(input_folder)
+    cases = _cases_of([(os.path.join(input_folder, f), None) for f in fnames], reader, num_processes, False)
+    for f, (seg, _, properties) in zip(fnames, cases):
+        seg = remove(seg, for_which_classes, _volume_per_voxel(properties), min_valid_object_size)[0]
+        writer(_host_u8(seg), os.path.join(output_folder, f), properties)

@@ -1028,8 +1028,9 @@ class nnUNetTrainer_simple(object):
                    final_subf_name=validation_folder_name + "_postprocessed",
                    writer=lambda vol, path, i: writer(vol, path, case_properties[i]))
         elif run_postprocessing_on_folds:
-            self.print_to_log_file("validate: determine_postprocessing (connected-component search, e2enet/postprocessing) is outside "
-                                   "the MI355X hot path and was skipped; run it with the reference package on %s" % output_folder)
+            self.print_to_log_file("validate: determine_postprocessing (connected-component search) was skipped: pass "
+                                   "determine_postprocessing=True for this fold's own decision, or, once every fold is validated, run "
+                                   "python -m e2enet_medical_amd.postprocessing.consolidate_postprocessing -f %s" % self.output_folder_base)
         if self.gt_niftis_folder and os.path.isdir(self.gt_niftis_folder) and self.output_folder_base:
             gt_nifti_folder = join(self.output_folder_base, "gt_niftis")                 # reference :1455-1477
             os.makedirs(gt_nifti_folder, exist_ok=True)

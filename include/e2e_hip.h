@@ -621,6 +621,28 @@ int e2e_cc_remove_all_but_largest(unsigned char* volume, int D, int H, int W, co
                                   double volume_per_voxel, double min_valid, void* ws, unsigned long long* result,
                                   void* stream);
 
+/* ---- P5: the component table of a prediction, for the post-processing search over a folder ---------------------------------
+ * Replaces: what determine_postprocessing (connected_components.py:124-399) gets from removing, writing, reading and scoring every
+ * case once per sweep: the confusion counts after a removal follow from the prediction's components, their sizes and their own
+ * true positives.  pred, gt: uint8 [D,H,W], W contiguous, read only.  class_words: the foreground classes S as in P1 (8 HOST words).
+ * Two labellings of pred in one call: the foreground components (x in S as one mask, the kernels of P1) and the class components
+ * (two 6-neighbours unite only when both are in S and carry the same value), the latter with size and tp = voxels with gt == pred.
+ *   ct_ws_bytes: bytes of `ws`: 20 per voxel (five 32-bit arrays) plus 128 for the two sets of result words; 0 for a refused shape
+ *   ct_label: result (device, four 64-bit words, written by the callee): number of class components, number of foreground
+ *     components, give-up flag (non-zero: the call failed, see P1; never retried), 0
+ *   ct_emit: after ct_label on the same ws and pred, and after the caller has read its result: class_records [class_count][5]
+ *     32-bit words (first voxel = flat index of the component's first voxel in raster order, label, size, tp, first voxel of the
+ *     foreground component it lies in), fg_records [fg_count][2] (first voxel, size).  The order of the records is not fixed; sorted
+ *     by first voxel the table is the same bits on every run (integer atomics only).  Nothing is truncated: a capacity (in records)
+ *     below its count is E2E_ERR_ARG, and no record is written at or past its count.
+ *   Refused before anything is launched: an axis < 1, a null pointer, an empty set, class 0 in the set, counts that are no
+ *     component counts of the shape (E2E_ERR_ARG); more than 2^31 - 2 voxels (E2E_ERR_UNSUPPORTED)                              */
+long long e2e_ct_ws_bytes(int D, int H, int W);
+int e2e_ct_label(const unsigned char* pred, const unsigned char* gt, int D, int H, int W, const unsigned* class_words, void* ws,
+                 unsigned long long* result, void* stream);
+int e2e_ct_emit(const unsigned char* pred, int D, int H, int W, void* ws, unsigned* class_records, long long class_capacity,
+                long long class_count, unsigned* fg_records, long long fg_capacity, long long fg_count, void* stream);
+
 /* ---- P2: preprocessing of a raw case (crop to non-zero, resample, normalise) ----------------------------------------
  * Replaces: e2enet/preprocessing/cropping.py (create_nonzero_mask, get_bbox_from_mask, crop_to_nonzero) and
  * e2enet/preprocessing/preprocessing.py (resample_data_or_seg, GenericPreprocessor.resample_and_normalize).  Volumes are fp32,
