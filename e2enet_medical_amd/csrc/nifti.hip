@@ -3,6 +3,8 @@
 // [C, Z, Y, X] tensor, or the uint8 label volume of the census and component kernels.  A pure stream: elsize bytes read per voxel,
 // 4 or 1 written, 16 bytes of payload per lane and load.  Built with -ffp-contract=off: the scaling is numpy's, a fp64 multiply and
 // a fp64 add, each rounded, then one rounding to fp32.
+// The integrity scan (e2e_nifti_scan, below the decode) reads the same bytes through the same decode1 and writes 260 words: NaN and
+// non-label counts with their first raster indices, and the 256 label counts.
 #include "e2e_common.h"
 
 #include <cstdint>
@@ -177,7 +179,202 @@ int decode(const char* what, const void* raw, long long nvox, int datatype, int 
   return e2e::check_launch("nifti_decode_kernel");
 }
 
+// ---- the integrity scan: one pass over the stored bytes, 260 words written -------------------------------------------------------
+constexpr int SCAN_WORDS = 4 + 256;        // NaN count, first NaN, non-label count, first non-label, 256 label counts
+constexpr int SCAN_COPIES = 16;            // sub-histograms of a workgroup: lane l adds into copy l % 16
+constexpr int SCAN_UNROLL = 4;             // vectors a lane requests before it looks at the first: the loads in flight per lane
+constexpr int SCAN_MAX_BLOCKS = 1024;      // 256 CUs x 4 workgroups, each lane with SCAN_UNROLL loads in flight
+
+__global__ void nifti_scan_init_kernel(unsigned long long* __restrict__ out) {
+  for (int i = threadIdx.x; i < SCAN_WORDS; i += blockDim.x) out[i] = (i == 1 || i == 3) ? ~0ull : 0ull;
+}
+
+// What one lane has seen.  The label counts go to the workgroup's LDS histogram, run by run: a lane that keeps meeting the value
+// it met last only counts, and adds the run when the value changes (and once at the end), so a volume of one value -- background --
+// costs a lane one LDS atomic, not one per voxel.  Everything is an integer sum or a minimum: no order of arrival shows.
+struct ScanLane {
+  unsigned nan = 0, bad = 0, run = 0;
+  int cur = 0;
+  unsigned long long first_nan = ~0ull, first_bad = ~0ull;
+  unsigned* hist;                          // this lane's copy: bin v at hist[v * SCAN_COPIES]
+
+  __device__ __forceinline__ void flush() {
+    if (run) atomicAdd(hist + cur * SCAN_COPIES, run);
+    run = 0;
+  }
+  __device__ __forceinline__ void take(float r, long long i) {
+    unsigned rejected = 0;
+    const int v = label_of(r, rejected);   // the rule of decode_u8
+    if (!rejected) {
+      if (v != cur) {
+        flush();
+        cur = v;
+      }
+      ++run;
+    } else if (r != r) {
+      ++nan;
+      if ((unsigned long long)i < first_nan) first_nan = (unsigned long long)i;
+    } else {
+      ++bad;
+      if ((unsigned long long)i < first_bad) first_bad = (unsigned long long)i;
+    }
+  }
+};
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// head: the elements in front of the first 16-byte boundary of the payload (fewer than 16 / sizeof(T), or all of a short volume);
+// then `chunks` aligned 16-byte vectors, a grid stride apart, SCAN_UNROLL of them requested at a time (the kernel waits on memory,
+// not on arithmetic: what counts is the loads in flight), the last fewer than SCAN_UNROLL steps of a lane one by one; then the tail.  Head and tail go element by element to the first lanes
+// of workgroup 0.
+template <typename T, bool SWAP, bool SCALE>
+__global__ __launch_bounds__(256) void nifti_scan_kernel(const unsigned char* __restrict__ raw, long long nvox, long long head,
+                                                         double slope, double inter, unsigned long long* __restrict__ out) {
+  typedef typename Bits<sizeof(T)>::type U;
+  constexpr int PER = VEC_BYTES / (int)sizeof(T);
+  typedef U uvec __attribute__((ext_vector_type(PER)));
+  __shared__ unsigned hist[256 * SCAN_COPIES];
+  __shared__ unsigned long long wave_part[4][4];
+  for (int i = threadIdx.x; i < 256 * SCAN_COPIES; i += 256) hist[i] = 0u;
+  __syncthreads();
+
+  ScanLane lane;
+  lane.hist = hist + (threadIdx.x % SCAN_COPIES);
+  const long long chunks = (nvox - head) / PER, tail0 = head + chunks * PER;
+  const uvec* body = (const uvec*)(raw + head * (long long)sizeof(T));          // 16-byte aligned by the choice of head
+  const long long stride = (long long)gridDim.x * 256;
+  long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; t + (SCAN_UNROLL - 1) * stride < chunks; t += SCAN_UNROLL * stride) {
+    uvec v[SCAN_UNROLL];
+#pragma unroll
+    for (int k = 0; k < SCAN_UNROLL; ++k) v[k] = body[t + k * stride];
+#pragma unroll
+    for (int k = 0; k < SCAN_UNROLL; ++k) {
+      const long long i0 = head + (t + k * stride) * PER;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) lane.take(decode1<T, SWAP, SCALE>(v[k][j], slope, inter), i0 + j);
+    }
+  }
+  for (; t < chunks; t += stride) {
+    const uvec v = body[t];
+    const long long i0 = head + t * PER;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) lane.take(decode1<T, SWAP, SCALE>(v[j], slope, inter), i0 + j);
+  }
+  if (blockIdx.x == 0) {
+    // (at most PER - 1 elements on either side, PER <= 16: one element per lane)
+    const long long edge[2] = {threadIdx.x < head ? (long long)threadIdx.x : -1ll,
+                               tail0 + threadIdx.x < nvox ? tail0 + threadIdx.x : -1ll};
+    for (int k = 0; k < 2; ++k) {
+      if (edge[k] < 0) continue;
+      U b;
+      __builtin_memcpy(&b, raw + edge[k] * (long long)sizeof(T), sizeof(b));
+      lane.take(decode1<T, SWAP, SCALE>(b, slope, inter), edge[k]);
+    }
+  }
+  lane.flush();
+
+  // the two counts and the two first indices: wave, then workgroup, then one atomic each and only where there is something to say
+  unsigned long long nan = lane.nan, bad = lane.bad;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    nan += __shfl_xor(nan, off, 64);
+    bad += __shfl_xor(bad, off, 64);
+  }
+  const unsigned long long first_nan = wave_min_u64(lane.first_nan), first_bad = wave_min_u64(lane.first_bad);
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long* w = wave_part[threadIdx.x >> 6];
+    w[0] = nan, w[1] = first_nan, w[2] = bad, w[3] = first_bad;
+  }
+  __syncthreads();                         // (also: every lane's histogram adds are done)
+  if (threadIdx.x == 0) {
+    unsigned long long n = 0, b = 0, fn = ~0ull, fb = ~0ull;
+    for (int w = 0; w < 4; ++w) {
+      n += wave_part[w][0];
+      b += wave_part[w][2];
+      fn = wave_part[w][1] < fn ? wave_part[w][1] : fn;
+      fb = wave_part[w][3] < fb ? wave_part[w][3] : fb;
+    }
+    if (n) {
+      atomicAdd(out + 0, n);
+      atomicMin(out + 1, fn);
+    }
+    if (b) {
+      atomicAdd(out + 2, b);
+      atomicMin(out + 3, fb);
+    }
+  }
+  // the workgroup's one flush of the histogram: lane v owns bin v (the copies read in a rotated order: 16 banks, not one)
+  unsigned long long total = 0;
+#pragma unroll
+  for (int c = 0; c < SCAN_COPIES; ++c) total += hist[threadIdx.x * SCAN_COPIES + ((c + threadIdx.x) % SCAN_COPIES)];
+  if (total) atomicAdd(out + 4 + threadIdx.x, total);
+}
+
+template <typename T>
+void launch_scan(const void* raw, long long nvox, bool swap, bool scale, double slope, double inter, unsigned long long* out,
+                 hipStream_t st) {
+  constexpr long long PER = VEC_BYTES / (long long)sizeof(T);
+  long long head = (long long)((0 - (uintptr_t)raw) % VEC_BYTES) / (long long)sizeof(T);
+  if (head > nvox) head = nvox;
+  // a lane takes SCAN_UNROLL vectors per step also where one workgroup is enough (workgroup 0 always runs: head and tail are its)
+  long long blocks = e2e::cdivll((nvox - head) / PER, 256 * SCAN_UNROLL);
+  blocks = blocks < 1 ? 1 : (blocks < SCAN_MAX_BLOCKS ? blocks : SCAN_MAX_BLOCKS);
+  const dim3 grid((unsigned)blocks), block(256);
+  const unsigned char* p = (const unsigned char*)raw;
+  swap = swap && sizeof(T) > 1;
+#define E2E_NIFTI_SCAN(SW, SC) hipLaunchKernelGGL((nifti_scan_kernel<T, SW, SC>), grid, block, 0, st, p, nvox, head, slope, inter, out)
+  if (swap && scale) E2E_NIFTI_SCAN(true, true);
+  else if (swap) E2E_NIFTI_SCAN(true, false);
+  else if (scale) E2E_NIFTI_SCAN(false, true);
+  else E2E_NIFTI_SCAN(false, false);
+#undef E2E_NIFTI_SCAN
+}
+
 }  // namespace
+
+extern "C" long long e2e_nifti_scan_grid_voxels(int datatype) {
+  const int elsize = elsize_of(datatype);
+  return elsize ? (long long)SCAN_MAX_BLOCKS * 256 * SCAN_UNROLL * (VEC_BYTES / elsize) : 0;
+}
+
+extern "C" int e2e_nifti_scan(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
+                              unsigned long long* out, void* stream) {
+  const char* what = "nifti_scan";
+  const hipStream_t st = (hipStream_t)stream;
+  const int elsize = elsize_of(datatype);
+  E2E_REQUIRE(elsize != 0, "%s: datatype %d is not one of 2, 4, 8, 16, 64, 256, 512, 768, 1024, 1280", what, datatype);
+  E2E_REQUIRE(nvox >= 0, "%s: %lld voxels", what, nvox);
+  E2E_REQUIRE(nvox <= (1ll << 40), "%s: %lld voxels, at most 2^40", what, nvox);
+  E2E_REQUIRE(out != nullptr, "%s: null pointer", what);
+  E2E_REQUIRE((uintptr_t)out % 8 == 0, "%s: out at %p is not aligned to its 64-bit words", what, (const void*)out);
+  E2E_REQUIRE(nvox == 0 || raw != nullptr, "%s: null pointer", what);
+  E2E_REQUIRE((uintptr_t)raw % (uintptr_t)elsize == 0, "%s: the payload at %p is not aligned to its %d-byte elements", what, raw,
+              elsize);
+  hipLaunchKernelGGL(nifti_scan_init_kernel, dim3(1), dim3(SCAN_WORDS), 0, st, out);
+  if (nvox == 0) return e2e::check_launch("nifti_scan_init_kernel");
+  const bool sw = swap != 0, sc = scale != 0;
+  switch (datatype) {
+    case 2: launch_scan<unsigned char>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 256: launch_scan<signed char>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 4: launch_scan<short>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 512: launch_scan<unsigned short>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 8: launch_scan<int>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 768: launch_scan<unsigned int>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 16: launch_scan<float>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 64: launch_scan<double>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 1024: launch_scan<long long>(raw, nvox, sw, sc, slope, inter, out, st); break;
+    case 1280: launch_scan<unsigned long long>(raw, nvox, sw, sc, slope, inter, out, st); break;
+  }
+  return e2e::check_launch("nifti_scan_kernel");
+}
 
 extern "C" int e2e_nifti_decode_f32(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
                                     float* out, void* stream) {

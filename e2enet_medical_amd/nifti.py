@@ -4,7 +4,7 @@ The host does what only the host can: gzip and the 348-byte header (``read_raw``
 device).  The voxel payload is uploaded as the file stores it -- 1 to 8 bytes per voxel, in the file's byte order -- and decoded on
 the device (csrc/nifti.hip) into the tensors the other kernels take: fp32 in a channel of the case's ``[C, Z, Y, X]`` tensor
 (``decode_f32``, ``reader``) or the uint8 label volume of the census and component kernels (``decode_u8``, ``gt_reader``,
-``evaluator_reader``).
+``evaluator_reader``).  ``scan`` reads the same bytes once for the dataset integrity check and brings back 260 words.
 
 Read: single-file NIfTI-1 (``.nii``, ``.nii.gz``; magic ``n+1``, either byte order), three spatial dimensions (``dim[0]`` 3, or 4-7
 with every further dimension 1), the ten scalar datatypes of ``DATATYPES``.  Everything else -- NIfTI-2, ``.hdr``/``.img`` pairs, RGB
@@ -46,6 +46,13 @@ NiftiRaw.__doc__ = """One file as ``read_raw`` leaves it on the host.
   scale          apply ``value * slope + inter`` (off for scl_slope 0 or non-finite, and for slope 1 with inter 0)
   payload        uint8 host array of prod(shape) * elsize bytes: the voxels as the file stores them
   itk_spacing, itk_origin, itk_direction   what SimpleITK's GetSpacing / GetOrigin / GetDirection report (x, y, z; LPS; mm)"""
+
+NiftiScan = namedtuple("NiftiScan", "nan_count first_nan non_label_count first_non_label histogram")
+NiftiScan.__doc__ = """What ``scan`` says about a payload (fp32 values, the header's scaling applied).
+  nan_count, first_nan              voxels that are NaN; raster index of the first, -1 without one
+  non_label_count, first_non_label  voxels that are not NaN and no whole number in [0, 255]; raster index of the first, or -1
+  histogram                         np.int64[256]: voxels per label value"""
+SCAN_WORDS = 4 + 256
 
 
 def _refuse(path, field, what):
@@ -276,6 +283,19 @@ def decode_u8(raw):
     if bad:
         raise ValueError("%s: %d voxel(s) are no whole-number labels in [0, 255]: not a label volume" % (raw.path, bad))
     return out
+
+
+def scan(raw):
+    """The integrity scan of a ``NiftiRaw`` (``e2e_nifti_scan``): one upload of the stored bytes, one pass over them on the device,
+    260 words back.  Returns a ``NiftiScan``."""
+    import torch
+    from ._lib import lib
+    dev = _upload(raw)
+    out = torch.empty(SCAN_WORDS, dtype=torch.int64, device=dev.device)
+    lib().nifti_scan(dev.data_ptr(), dev.numel() // raw.elsize, raw.datatype, int(raw.swap), int(raw.scale), raw.slope, raw.inter,
+                     out.data_ptr(), _stream())
+    words = out.cpu().numpy()                                    # (~0 of the two index words reads -1)
+    return NiftiScan(int(words[0]), int(words[1]), int(words[2]), int(words[3]), words[4:].copy())
 
 
 # ------------------------------------------------------------------------------------------------------------------ callbacks

@@ -796,6 +796,26 @@ int e2e_nifti_decode_f32(const void* raw, long long nvox, int datatype, int swap
 int e2e_nifti_decode_u8(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
                         unsigned char* out, unsigned long long* rejected, void* stream);
 
+/* The integrity scan of a payload: what np.isnan, np.unique and the label rule of decode_u8 say about a volume, from one pass over the
+ * stored bytes (same arguments, same per-voxel value as decode_f32) with nothing of volume size written.
+ * Replaces: np.any(np.isnan(sitk.GetArrayFromImage(...))) and np.unique of e2enet/preprocessing/sanity_checks.py:79-87, 136-145.
+ * out: 4 + 256 64-bit words on the device, written whole by the call (no need to zero them):
+ *   [0] voxels whose fp32 value is NaN               [1] raster index of the first of them, ~0 when there is none
+ *   [2] voxels that are not NaN and are no whole number in [0, 255] (what decode_u8 rejects, less the NaNs)
+ *   [3] raster index of the first of them, ~0 when there is none
+ *   [4 + v] voxels whose value is the label v
+ * so [0] + [2] + sum [4..259] == nvox.  Integer sums and minima only: the words are the same on every run.  The 256 counts are kept
+ * in LDS, 16 copies per workgroup, each lane adding a run of equal values at once; a workgroup adds its counts to out once.  16 bytes
+ * per lane and load, four loads requested at a time, from the first 16-byte boundary of raw on; the elements in front of it and behind the last whole vector are read
+ * one by one.  elsize bytes read per voxel.  One small kernel sets out before the scan; nvox == 0 runs only that one (raw is not
+ * read and may be null).  Refused with E2E_ERR_ARG before anything is launched: another datatype, nvox < 0 or > 2^40, a null pointer,
+ * raw not aligned to the element size, out not aligned to 8 bytes.
+ * e2e_nifti_scan_grid_voxels: the voxels one full grid of the scan takes in one step of its walk, four vectors per lane (0 for a
+ * datatype that is not decoded): in a larger volume lanes take a second step.                                                  */
+long long e2e_nifti_scan_grid_voxels(int datatype);
+int e2e_nifti_scan(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
+                   unsigned long long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
