@@ -127,11 +127,14 @@ __global__ __launch_bounds__(256) void dc_ce_reduce_kernel(const float* __restri
     const int t = (int)tp_[v];
     // cross entropy as torch's log_softmax forms it: (l_t - max) - log(sum exp(l - max)); -log(p_t) would turn into +Inf where
     // p_t underflows (logits apart by more than ~100: large InstanceNorm weights) although the loss is finite
-    float lt = (unsigned)t < (unsigned)K ? 0.f : NAN;     // label outside [0, K): torch's CrossEntropyLoss raises; here the loss turns NaN
+    // label outside [0, K): torch's CrossEntropyLoss raises; here the loss turns NaN.  Such a label matches no slot (tc = -1) and
+    // lt keeps its NaN: a label in [K, KB) would otherwise pick up the -INF of a padded slot and turn the loss into +Inf
+    const int tc = (unsigned)t < (unsigned)K ? t : -1;
+    float lt = NAN;
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
-      if (k == t) lt = l[k] - m;
+      if (k == tc) lt = l[k] - m;
       l[k] = (k < K) ? expf(l[k] - m) : 0.f;
       s += l[k];
     }

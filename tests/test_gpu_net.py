@@ -89,14 +89,16 @@ def test_tiny_forward_backward_vs_reference_golden():
     assert abs(full.double().sum().item() - float(g["logits_nods_sum"])) < 5e-2
 
 
-def test_tiny_engine_fastpath_matches_oracle_all_grads():
-    """Engine fast path (fused loss kernels + backward) against the oracle's autograd for every parameter."""
-    net, shapes, params = tiny_net()
-    spec = oracle.make_spec(TINY["cin"], TINY["base"], TINY["k"], TINY["pools"], 2, TINY["max_feat"])
+def engine_fastpath_vs_oracle(k):
+    """The tiny network with k classes: engine fast path (fused loss kernels + backward) against the oracle's autograd for every
+    parameter, per-sample and batch dice.  Returns (engine, full-resolution targets) after the last loss_backward."""
+    net = build_net(TINY["patch"], TINY["cin"], TINY["base"], k, TINY["pools"], TINY["max_feat"])
+    shapes, params = load_closed_form(net)
+    spec = oracle.make_spec(TINY["cin"], TINY["base"], k, TINY["pools"], 2, TINY["max_feat"])
     x = seeded_input((2, TINY["cin"]) + TINY["patch"], seed=77)
     eng = net.engine(x.cuda())
     outs = eng.forward(x.cuda(), True)
-    targets = [seeded_labels((o.shape[0], 1) + tuple(o.shape[2:]), TINY["k"], seed=80 + i) for i, o in enumerate(outs)]
+    targets = [seeded_labels((o.shape[0], 1) + tuple(o.shape[2:]), k, seed=80 + i) for i, o in enumerate(outs)]
     w = oracle.ds_weights(5)
     for bd in (False, True):
         loss = eng.loss_backward([t.cuda() for t in targets], w, batch_dice=bd)
@@ -111,6 +113,12 @@ def test_tiny_engine_fastpath_matches_oracle_all_grads():
             rg = leaves[n].grad
             err = (eng.grads[n].cpu() - rg).abs().max().item()
             assert err <= 2e-4 * max(1.0, rg.abs().max().item()) + 1e-6, (n, err)
+    return eng, targets[0]
+
+
+def test_tiny_engine_fastpath_matches_oracle_all_grads():
+    """Engine fast path (fused loss kernels + backward) against the oracle's autograd for every parameter."""
+    engine_fastpath_vs_oracle(TINY["k"])
 
 
 @pytest.mark.parametrize("shift_size", [1, 3, 7])
