@@ -141,7 +141,7 @@ __device__ __forceinline__ void load_row(const float* __restrict__ src, float* _
   for (; c < NC; ++c) dst[c] = src[c];
 }
 
-template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW, int PIPE, int PERSIST>
+template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW, int PERSIST>
 __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
   using C = Cfg<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG>;
   static_assert((OPW == 4 || OPW == 8) && CK % 8 == 0 && CK <= 16, "liveness quad words: 4 output planes x 8 input planes per word");
@@ -1033,63 +1033,192 @@ __global__ __launch_bounds__(256) void conv133_dgrad_strided_kernel(const float*
   else *dst = acc;
 }
 
-template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW, int PIPE, int PERSIST>
-int launch_cfg_impl(ConvParams p, hipStream_t st);
+// ---- host: one plan per entry point ---------------------------------------------------------------------------------
+// The live template tuples of conv133_kernel: every instantiation in the code object is a row of this table (float4-staged
+// rows twice: one item per workgroup, and the persistent run loop).  _V = float4 staging (rows that are multiples of 4 floats),
+// _E = element staging.  16x32 tile at stride 1: 97 VGPRs -> two 512-thread workgroups per CU (measured best; see DESIGN.md §5
+// for the variants that were measured against it).  The strided forward variants ("convolutional pooling", 5 layers) stage
+// with register prefetch; DGD = data gradient of a stride-(2,2) conv read zero-dilated, SUB = its sub-pixel form (MODE 2).
+//  X(name,         MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW)
+#define K1_CONFIGS(X)                                              \
+  X(FWD_32_V,     0, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 1, 4)   \
+  X(FWD_32_E,     0, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 0, 4)   \
+  X(FWD_16_V,     0, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 1, 1)   \
+  X(FWD_16_E,     0, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 0, 1)   \
+  X(FWD_8_V,      0, 1, 1, 1, 1,  8,  8, 8,  8, 4, 8, 16, 1, 1)   \
+  X(FWD_8_E,      0, 1, 1, 1, 1,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(FWD_S22_32_V, 0, 2, 2, 1, 1, 16, 32, 4, 16, 4, 8,  8, 1, 1)   \
+  X(FWD_S22_32_E, 0, 2, 2, 1, 1, 16, 32, 4, 16, 4, 8,  8, 0, 1)   \
+  X(FWD_S22_8_E,  0, 2, 2, 1, 1,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(FWD_S12_32_E, 0, 1, 2, 1, 1, 16, 32, 4, 16, 4, 8,  8, 0, 1)   \
+  X(FWD_S12_8_E,  0, 1, 2, 1, 1,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(FWD_S21_32_E, 0, 2, 1, 1, 1, 16, 32, 4, 16, 4, 8,  8, 0, 1)   \
+  X(FWD_S21_8_E,  0, 2, 1, 1, 1,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(DG_32_V,      1, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 1, 4)   \
+  X(DG_32_E,      1, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 0, 4)   \
+  X(DG_16_V,      1, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 1, 1)   \
+  X(DG_16_E,      1, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 0, 1)   \
+  X(DG_8_V,       1, 1, 1, 1, 1,  8,  8, 8,  8, 4, 8, 16, 1, 1)   \
+  X(DG_8_E,       1, 1, 1, 1, 1,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(DGD_32_E,     1, 1, 1, 2, 2, 16, 32, 8,  8, 4, 8,  8, 0, 4)   \
+  X(DGD_16_E,     1, 1, 1, 2, 2, 16, 16, 8,  8, 4, 8, 16, 0, 1)   \
+  X(DGD_8_E,      1, 1, 1, 2, 2,  8,  8, 8,  8, 4, 8, 16, 0, 1)   \
+  X(SUB_32_V,     2, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 1, 4)   \
+  X(SUB_32_E,     2, 1, 1, 1, 1, 16, 32, 8,  8, 4, 8,  8, 0, 4)   \
+  X(SUB_16_V,     2, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 1, 1)   \
+  X(SUB_16_E,     2, 1, 1, 1, 1, 16, 16, 8,  8, 4, 8, 16, 0, 1)
 
-// persistent grid: 4 workgroup slots' worth per CU (256 CUs x 2 resident workgroups x 2 rounds); E2E_CONV_WGS overrides (A/B)
-inline int persist_knob() {
-  static const int v = getenv("E2E_CONV_PERSIST") ? atoi(getenv("E2E_CONV_PERSIST")) : 0;
-  return v;
-}
-inline int persist_wgs() {
-  static const int v = getenv("E2E_CONV_WGS") ? atoi(getenv("E2E_CONV_WGS")) : 1024;
-  return v > 8 ? v : 8;
-}
+#define K1_ENUM(name, ...) name,
+enum K1Config { K1_CONFIGS(K1_ENUM) };
+#undef K1_ENUM
+struct K1Tuple { int mode, sh, sw, dh, dw, th, tw, ly, lx, opw, nw, ck, stg, minw; };
+#define K1_ROW(name, ...) {__VA_ARGS__},
+constexpr K1Tuple k1_tuples[] = {K1_CONFIGS(K1_ROW)};
+#undef K1_ROW
 
-template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW = 1, int PIPE = 0>
-int launch_cfg(ConvParams p, hipStream_t st) {
+enum K1Path { K1_TILED, K1_SUBPIXEL, K1_GATHER };   // conv133_kernel MODE 0 / 1, MODE 2, conv133_dgrad_strided_kernel
+struct K1Shape { int B, Cin, Cout, Di, Hi, Wi, sd, sh, sw; };   // of the convolution, whichever direction runs
+
+// What a launch and the three size queries share.  The kernel's P input planes and Q output planes of Do x Ho x Wo voxels are
+// (Cin, Cout, output dims) in the forward and (Cout, Cin, input dims) in the data gradient.
+struct K1Plan {
+  K1Path path;
+  K1Config cfg;
+  int TH, TW, CK, OCG, NT, stg;   // of cfg: tile, input planes per chunk, output planes per workgroup, threads, float4 staging
+  bool persist;                   // workgroups walk runs of items_per_wg consecutive items
+  int ksplit;                     // workgroups that share the input-plane chunks of one tile; 1 = off
+  int tiles_x, tiles_y, tiles_per_n, groups;
+  int total, items_per_wg, wgs;   // total = B * tiles_per_n * groups * ksplit work items on wgs workgroups
+  int num_partials;               // forward: InstanceNorm (count, mean, M2) records per (n, c), one per tile
+  long long ws_bytes;             // raw partial sums [ksplit][B][Q][Do][Ho][Wo]; 0 when ksplit == 1
+};
+
+// tile grid, persistence, split-K and launch grid of configuration `cfg`
+inline void plan_k1_grid(K1Plan& pl, K1Config cfg, int B, int P, int Q, int Do, int Ho, int Wo, bool have_ws) {
+  const K1Tuple& t = k1_tuples[cfg];
+  pl.cfg = cfg;
+  pl.TH = t.th; pl.TW = t.tw; pl.CK = t.ck; pl.OCG = t.opw * t.nw; pl.NT = t.nw * 64; pl.stg = t.stg;
+  pl.tiles_x = e2e::cdiv(Wo, pl.TW);
+  pl.tiles_y = e2e::cdiv(Ho, pl.TH);
+  pl.tiles_per_n = Do * pl.tiles_y * pl.tiles_x;
+  pl.groups = e2e::cdiv(Q, pl.OCG);
+  const long long items = (long long)B * pl.tiles_per_n * pl.groups;
   // thin layers (a single input chunk, e.g. the 4-modal network input): per-tile start-up dominates -> persistent
   // workgroups that walk runs of consecutive items and request the next item's planes under the current epilogue.
   // For multi-chunk layers the run loop was measured SLOWER than one workgroup per item (0.91 vs 0.83 ms on 64->32
   // @128^3: the hardware dispatcher hides the start-up of the next workgroup behind the running ones, and runs that
   // start together stay in phase); E2E_CONV_PERSIST=1 forces it for A/B runs.  (Element staging keeps one item per
-  // workgroup: the run loop would spill there.)
-  if constexpr (STG == 1) {
-    const long long total = (long long)p.B * p.Do * e2e::cdiv(p.Ho, TH) * e2e::cdiv(p.Wo, TW) * e2e::cdiv(p.Q, Cfg<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG>::OCG);
-    if ((p.P <= CK || persist_knob()) && total > persist_wgs())
-      return launch_cfg_impl<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW, PIPE, 1>(p, st);
+  // workgroup: the run loop would spill there.)  Budget: 4 workgroup slots' worth per CU (256 CUs x 2 resident
+  // workgroups x 2 rounds); E2E_CONV_WGS overrides (A/B).
+  static const int persist_knob = getenv("E2E_CONV_PERSIST") ? atoi(getenv("E2E_CONV_PERSIST")) : 0;
+  static const int wgs_knob = getenv("E2E_CONV_WGS") ? atoi(getenv("E2E_CONV_WGS")) : 1024;
+  const int budget = wgs_knob > 8 ? wgs_knob : 8;
+  pl.persist = pl.stg == 1 && (P <= pl.CK || persist_knob) && items > budget;
+  // split-K (deep levels only: planes no larger than a 16 x 16 tile, and a caller that brought a workspace): enough parts
+  // for 1024 workgroups, at most 8, each with at least two of the ceil(P / CK) chunks.  E2E_CONV_KSPLIT: 0/1 = off, n = force n (A/B)
+  static const int ksplit_knob = getenv("E2E_CONV_KSPLIT") ? atoi(getenv("E2E_CONV_KSPLIT")) : -1;
+  pl.ksplit = 1;
+  if (have_ws && !pl.persist && pl.TW <= 16 && ksplit_knob != 0 && ksplit_knob != 1) {
+    long long ks = ksplit_knob > 1 ? ksplit_knob : 1024 / (items > 0 ? items : 1);
+    if (ks > 8) ks = 8;
+    if (ks > e2e::cdiv(P, pl.CK) / 2) ks = e2e::cdiv(P, pl.CK) / 2;
+    if (ks >= 2) pl.ksplit = (int)ks;
   }
-  return launch_cfg_impl<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW, PIPE, 0>(p, st);
+  pl.ws_bytes = pl.ksplit > 1 ? (long long)pl.ksplit * B * Q * Do * Ho * Wo * 4 : 0;
+  pl.total = (int)items * pl.ksplit;
+  int wgs = pl.persist ? budget : pl.total;
+  if (wgs > pl.total) wgs = pl.total;
+  pl.items_per_wg = e2e::cdiv(pl.total, wgs > 0 ? wgs : 1);
+  pl.wgs = (e2e::cdiv(pl.total, pl.items_per_wg > 0 ? pl.items_per_wg : 1) + 7) & ~7;
 }
 
-template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW, int PIPE, int PERSIST>
-int launch_cfg_impl(ConvParams p, hipStream_t st) {
-  using C = Cfg<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG>;
-  p.tiles_x = e2e::cdiv(p.Wo, TW);
-  p.tiles_y = e2e::cdiv(p.Ho, TH);
-  p.tiles_per_n = p.Do * p.tiles_y * p.tiles_x;
-  p.groups = e2e::cdiv(p.Q, C::OCG);
-  if (p.ksplit < 1 || PERSIST) p.ksplit = 1;
+// tile by the smaller plane side: 16 x 32, 16 x 16, 8 x 8
+inline K1Config by_plane(int m, K1Config t32, K1Config t16, K1Config t8) { return m > 16 ? t32 : (m > 8 ? t16 : t8); }
+
+inline K1Plan plan_k1_fwd(const K1Shape& s, bool have_ws) {
+  K1Plan pl{};
+  const int Do = (s.Di - 1) / s.sd + 1, Ho = (s.Hi - 1) / s.sh + 1, Wo = (s.Wi - 1) / s.sw + 1;
+  const int m = Ho < Wo ? Ho : Wo;
+  const bool vec = s.Wi % 4 == 0;
+  pl.path = K1_TILED;
+  K1Config cfg;
+  if (s.sh == 1 && s.sw == 1) cfg = vec ? by_plane(m, FWD_32_V, FWD_16_V, FWD_8_V) : by_plane(m, FWD_32_E, FWD_16_E, FWD_8_E);
+  else if (s.sh == 2 && s.sw == 2) cfg = m > 8 ? (vec ? FWD_S22_32_V : FWD_S22_32_E) : FWD_S22_8_E;
+  else if (s.sh == 1) cfg = m > 8 ? FWD_S12_32_E : FWD_S12_8_E;
+  else cfg = m > 8 ? FWD_S21_32_E : FWD_S21_8_E;
+  plan_k1_grid(pl, cfg, s.B, s.Cin, s.Cout, Do, Ho, Wo, have_ws);
+  pl.num_partials = pl.tiles_per_n;
+  return pl;
+}
+
+// The forward kernel with transposed, tap-reversed weights.  Its "input planes" are dy's channels (a plain tensor,
+// no shift; for a strided conv dy is read zero-dilated: only positions that are multiples of the stride carry a
+// value, and only every sd-th depth slice is non-zero), its output planes are the virtual-concat input channels
+// (un-shift on store).
+inline K1Plan plan_k1_dgrad(const K1Shape& s, bool have_ws) {
+  K1Plan pl{};
+  pl.ksplit = 1;
+  if (s.sh != s.sw) {     // in-plane anisotropic strides: rare, plain gather kernel
+    pl.path = K1_GATHER;
+    return pl;
+  }
+  const int m = s.Hi < s.Wi ? s.Hi : s.Wi;
+  const int Wo = (s.Wi - 1) / s.sw + 1;
+  K1Config cfg;
+  if (s.sh == 1) {
+    pl.path = K1_TILED;
+    cfg = s.Wi % 4 == 0 ? by_plane(m, DG_32_V, DG_16_V, DG_8_V) : by_plane(m, DG_32_E, DG_16_E, DG_8_E);
+  } else if (m > 8 && s.Hi % 2 == 0 && s.Wi % 2 == 0) {
+    // sub-pixel data gradient (stride (2,2) convs, weights read un-reversed); dx planes of 8x8 and smaller and odd planes
+    // keep the zero-dilated MODE 1 path
+    pl.path = K1_SUBPIXEL;
+    cfg = Wo % 4 == 0 ? (m > 16 ? SUB_32_V : SUB_16_V) : (m > 16 ? SUB_32_E : SUB_16_E);
+  } else {
+    pl.path = K1_TILED;
+    cfg = by_plane(m, DGD_32_E, DGD_16_E, DGD_8_E);
+  }
+  plan_k1_grid(pl, cfg, s.B, s.Cout, s.Cin, s.Di, s.Hi, s.Wi, have_ws);
+  return pl;
+}
+
+template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG, int MINW>
+void launch_k1(const K1Plan& pl, const ConvParams& p, hipStream_t st) {
+  const size_t lds = (size_t)p.P * sizeof(PlaneDesc);
+  if constexpr (STG == 1) {
+    if (pl.persist) {
+      hipLaunchKernelGGL((conv133_kernel<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW, 1>), dim3(pl.wgs), dim3(pl.NT), lds, st, p);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((conv133_kernel<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW, 0>), dim3(pl.wgs), dim3(pl.NT), lds, st, p);
+}
+
+// fills the launch fields of `p` from the plan, launches the planned configuration and the split-K tail
+int run_k1(const K1Plan& pl, ConvParams p, float* ws, hipStream_t st) {
+  const K1Tuple& t = k1_tuples[pl.cfg];
+  p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.tiles_per_n = pl.tiles_per_n; p.groups = pl.groups;
+  p.ksplit = pl.ksplit;
+  p.kpart = pl.ksplit > 1 ? ws : nullptr;
   double* const part_out = p.part;
-  if (p.ksplit > 1) p.part = nullptr;                 // raw partial sums: statistics come from conv133_ksum_kernel
-  p.total = p.B * p.tiles_per_n * p.groups * p.ksplit;
-  p.padded_total = (p.total + 7) & ~7;
+  if (pl.ksplit > 1) p.part = nullptr;                 // raw partial sums: statistics come from conv133_ksum_kernel
+  p.total = pl.total;
+  p.padded_total = (pl.total + 7) & ~7;
+  p.items_per_wg = pl.items_per_wg;
   static const int dbg_knob = getenv("E2E_CONV_DBG") ? atoi(getenv("E2E_CONV_DBG")) : 0;
   p.dbg = dbg_knob;
-  int wgs = PERSIST ? persist_wgs() : p.total;
-  if (wgs > p.total) wgs = p.total;
-  p.items_per_wg = e2e::cdiv(p.total, wgs);
-  wgs = (e2e::cdiv(p.total, p.items_per_wg) + 7) & ~7;
-  e2e::note_kernel("conv133_kernel<mode=%d,s=%dx%d,dil=%dx%d,tile=%dx%d,opw=%d,nw=%d,ck=%d,stg=%d,persist=%d> wgs=%d ksplit=%d", MODE, SH, SW, DH, DW,
-                   TH, TW, OPW, NW, CK, STG, PERSIST, wgs, p.ksplit);
-  hipLaunchKernelGGL((conv133_kernel<MODE, SH, SW, DH, DW, TH, TW, LY, LX, OPW, NW, CK, STG, MINW, PIPE, PERSIST>), dim3(wgs),
-                     dim3(C::NT), (size_t)p.P * sizeof(PlaneDesc), st, p);
-  if (p.ksplit > 1 && MODE == 0)
+  e2e::note_kernel("conv133_kernel<mode=%d,s=%dx%d,dil=%dx%d,tile=%dx%d,opw=%d,nw=%d,ck=%d,stg=%d,persist=%d> wgs=%d ksplit=%d", t.mode, t.sh, t.sw,
+                   t.dh, t.dw, t.th, t.tw, t.opw, t.nw, t.ck, t.stg, (int)pl.persist, pl.wgs, pl.ksplit);
+  switch (pl.cfg) {     // the one place where a configuration becomes a template instantiation
+#define K1_CASE(name, ...) case name: launch_k1<__VA_ARGS__>(pl, p, st); break;
+    K1_CONFIGS(K1_CASE)
+#undef K1_CASE
+  }
+  if (pl.ksplit > 1 && t.mode == 0)
     hipLaunchKernelGGL(conv133_ksum_kernel, dim3(p.B * p.Q * p.tiles_per_n), dim3(64), 0, st, p.kpart, p.bias, p.y, part_out,
-                       p.ksplit, p.B, p.Q, p.Do, p.Ho, p.Wo, TH, TW, p.tiles_x, p.tiles_y);
-  if (p.ksplit > 1 && MODE != 0)
+                       p.ksplit, p.B, p.Q, p.Do, p.Ho, p.Wo, pl.TH, pl.TW, p.tiles_x, p.tiles_y);
+  if (pl.ksplit > 1 && t.mode != 0)
     hipLaunchKernelGGL(conv133_dsum_kernel, dim3(p.B * p.Q * p.tiles_per_n), dim3(64), 0, st, p.kpart, p.outs, p.ksplit, p.B,
-                       p.Q, p.Do, p.Ho, p.Wo, TH, TW, p.tiles_x, p.tiles_y);
+                       p.Q, p.Do, p.Ho, p.Wo, pl.TH, pl.TW, p.tiles_x, p.tiles_y);
 #ifdef E2E_CONV_DEBUG
   if (p.dbg & 8) {
     hipStreamSynchronize(st);
@@ -1099,7 +1228,7 @@ int launch_cfg_impl(ConvParams p, hipStream_t st) {
     for (int i = 0; i < 1024 * 8; ++i) h[i & 7] += hh[i];
     const double w = h[7] ? (double)h[7] : 1.0;
     fprintf(stderr, "[conv133 MODE %d P %d Q %d] per-wave cycles(100MHz ticks): pro %.0f commit %.0f bar1 %.0f prefetch %.0f walk %.0f bar2 %.0f epi %.0f (waves %.0f)\n",
-            MODE, p.P, p.Q, h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w, w);
+            t.mode, p.P, p.Q, h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w, w);
     static unsigned long long zz[1024 * 8];
     hipMemcpyToSymbol(HIP_SYMBOL(g_conv_stamps), zz, sizeof(zz));
   }
@@ -1107,96 +1236,20 @@ int launch_cfg_impl(ConvParams p, hipStream_t st) {
   return e2e::check_launch("conv133_kernel");
 }
 
-// sub-pixel data gradient (stride (2,2) convs); dx planes of 8x8 and smaller keep the zero-dilated MODE 1 path
-int launch_sub(const ConvParams& p, int kind, hipStream_t st);
-
-
-inline int opw8_knob() {
-  return 0;
-}
-
-// stride-1 tiles; STG = 1 (aligned float4 staging) needs rows that are multiples of 4 floats
-template <int MODE, int DH, int DW>
-int launch_s1(const ConvParams& p, int kind, hipStream_t st) {
-  const bool vec = (DH == 1 && DW == 1) && (p.Wi % 4 == 0);
-  switch (kind) {
-    case 0:
-      // 16x32 tile, 97 VGPRs -> two 512-thread workgroups per CU (measured best; see DESIGN.md §5 for the variants
-      // that were measured against it)
-      if (vec && opw8_knob() == 1 && p.P > 8) return launch_cfg<MODE, 1, 1, 1, 1, 16, 32, 8, 8, 8, 4, 8, 1, 3, 0>(p, st);   // 4 fat waves
-      if (vec && opw8_knob() == 2 && p.P > 8) return launch_cfg<MODE, 1, 1, 1, 1, 16, 32, 8, 8, 4, 4, 8, 1, 4, 0>(p, st);   // 4 waves, 16 output planes: 4 workgroups per CU
-      return vec ? launch_cfg<MODE, 1, 1, 1, 1, 16, 32, 8, 8, 4, 8, 8, 1, 4, 0>(p, st)
-                 : launch_cfg<MODE, 1, 1, DH, DW, 16, 32, 8, 8, 4, 8, 8, 0, 4, 0>(p, st);
-    case 1:
-      return vec ? launch_cfg<MODE, 1, 1, 1, 1, 16, 16, 8, 8, 4, 8, 16, 1>(p, st)
-                 : launch_cfg<MODE, 1, 1, DH, DW, 16, 16, 8, 8, 4, 8, 16, 0>(p, st);
-    default:
-      return vec ? launch_cfg<MODE, 1, 1, 1, 1, 8, 8, 8, 8, 4, 8, 16, 1>(p, st)
-                 : launch_cfg<MODE, 1, 1, DH, DW, 8, 8, 8, 8, 4, 8, 16, 0>(p, st);
-  }
-}
-
-// tile selection shared by the launcher and e2e_conv133_num_partials
-enum TileKind { T32 = 0, T16 = 1, T8 = 2, T16x32S = 3, T8S = 4 };
-inline TileKind pick_tile(int Ho, int Wo, int sh, int sw) {
-  const bool strided = (sh != 1 || sw != 1);
-  const int m = Ho < Wo ? Ho : Wo;
-  if (strided) return m > 8 ? T16x32S : T8S;
-  if (m > 16) return T32;
-  if (m > 8) return T16;
-  return T8;
-}
-inline void tile_dims(TileKind k, int& th, int& tw) {
-  switch (k) {
-    case T32: th = 16; tw = 32; break;
-    case T16: th = 16; tw = 16; break;
-    case T8: th = 8; tw = 8; break;
-    case T16x32S: th = 16; tw = 32; break;
-    default: th = 8; tw = 8; break;
-  }
-}
-
-
-
-int launch_sub(const ConvParams& p, int kind, hipStream_t st) {
-  const bool vec = (p.Ws % 4) == 0;
-  if (kind == 0)
-    return vec ? launch_cfg<2, 1, 1, 1, 1, 16, 32, 8, 8, 4, 8, 8, 1, 4, 0>(p, st)
-               : launch_cfg<2, 1, 1, 1, 1, 16, 32, 8, 8, 4, 8, 8, 0, 4, 0>(p, st);
-  return vec ? launch_cfg<2, 1, 1, 1, 1, 16, 16, 8, 8, 4, 8, 16, 1>(p, st)
-             : launch_cfg<2, 1, 1, 1, 1, 16, 16, 8, 8, 4, 8, 16, 0>(p, st);
-}
-
 }  // namespace
 
+// the three size queries are fields of the plan that the launch follows
 extern "C" int e2e_conv133_num_partials(int Do, int Ho, int Wo, int sh, int sw) {
-  int th, tw;
-  tile_dims(pick_tile(Ho, Wo, sh, sw), th, tw);
-  return Do * e2e::cdiv(Ho, th) * e2e::cdiv(Wo, tw);
-}
-
-// split-K plan of the forward (deep levels only: planes no larger than a 16 x 16 tile): number of parts, 1 = off
-static int plan_fwd_ksplit(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  static const int knob = getenv("E2E_CONV_KSPLIT") ? atoi(getenv("E2E_CONV_KSPLIT")) : -1;   // 0/1 = off, n = force n (A/B)
-  const int Do = (Di - 1) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
-  const TileKind k = pick_tile(Ho, Wo, sh, sw);
-  if (k == T32 || k == T16x32S) return 1;
-  int th, tw;
-  tile_dims(k, th, tw);
-  const int chunks = e2e::cdiv(Cin, 16);                   // (these configurations stage 16 planes per chunk)
-  const long long base = (long long)B * Do * e2e::cdiv(Ho, th) * e2e::cdiv(Wo, tw) * e2e::cdiv(Cout, 32);
-  if (knob == 0 || knob == 1) return 1;
-  long long ks = knob > 1 ? knob : 1024 / (base > 0 ? base : 1);
-  if (ks > 8) ks = 8;
-  if (ks > chunks / 2) ks = chunks / 2;
-  return ks < 2 ? 1 : (int)ks;
+  // (the tile grid depends on the output plane alone: the smallest input with these output dims stands for all of them)
+  return plan_k1_fwd({1, 1, 1, Do, (Ho - 1) * sh + 1, (Wo - 1) * sw + 1, 1, sh, sw}, false).num_partials;
 }
 
 extern "C" long long e2e_conv133_fwd_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  const int ks = plan_fwd_ksplit(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-  if (ks <= 1) return 0;
-  const long long Do = (Di - 1) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
-  return (long long)ks * B * Cout * Do * Ho * Wo * 4;
+  return plan_k1_fwd({B, Cin, Cout, Di, Hi, Wi, sd, sh, sw}, true).ws_bytes;
+}
+
+extern "C" long long e2e_conv133_dgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
+  return plan_k1_dgrad({B, Cin, Cout, Di, Hi, Wi, sd, sh, sw}, true).ws_bytes;
 }
 
 static int conv133_fwd_impl(const e2e_in_chan_t* chans, int Cin, const float* w, const float* bias, const unsigned* live, float* y,
@@ -1205,36 +1258,15 @@ static int conv133_fwd_impl(const e2e_in_chan_t* chans, int Cin, const float* w,
   E2E_REQUIRE(chans && w && y, "conv133_fwd: null pointer");
   E2E_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && Di > 0 && Hi > 0 && Wi > 0, "conv133_fwd: bad dims");
   E2E_REQUIRE((sd == 1 || sd == 2) && (sh == 1 || sh == 2) && (sw == 1 || sw == 2), "conv133_fwd: stride must be 1 or 2");
+  const K1Plan pl = plan_k1_fwd({B, Cin, Cout, Di, Hi, Wi, sd, sh, sw}, ws != nullptr);
+  E2E_REQUIRE(ws_bytes >= pl.ws_bytes, "conv133_fwd: workspace too small (%lld < %lld bytes)", ws_bytes, pl.ws_bytes);
   ConvParams p{};
   p.chans = chans; p.xin = nullptr; p.w = w; p.bias = bias; p.live = live; p.y = y; p.part = part; p.outs = nullptr;
   p.P = Cin; p.Q = Cout; p.wq_stride = Cin * 9; p.wp_stride = 9; p.live_words = e2e::cdiv(Cin, 32);
   p.B = B; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd;
   p.Do = (Di - 1) / sd + 1; p.Ho = (Hi - 1) / sh + 1; p.Wo = (Wi - 1) / sw + 1;
   p.Ds = Di; p.Hs = Hi; p.Ws = Wi;
-  p.ksplit = 1; p.kpart = nullptr;
-  if (ws != nullptr) {
-    const long long need = e2e_conv133_fwd_ws_bytes(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-    if (need > 0) {
-      E2E_REQUIRE(ws_bytes >= need, "conv133_fwd: workspace too small (%lld < %lld bytes)", ws_bytes, need);
-      p.ksplit = plan_fwd_ksplit(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-      p.kpart = ws;
-    }
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const TileKind k = pick_tile(p.Ho, p.Wo, sh, sw);
-  if (sh == 1 && sw == 1) return launch_s1<0, 1, 1>(p, k == T32 ? 0 : (k == T16 ? 1 : 2), st);
-  // strided variants ("convolutional pooling", 5 layers): element staging with register prefetch
-  if (sh == 2 && sw == 2) {
-    if (k == T16x32S && (Wi % 4) == 0) return launch_cfg<0, 2, 2, 1, 1, 16, 32, 4, 16, 4, 8, 8, 1>(p, st);   // float4 staging
-    if (k == T16x32S) return launch_cfg<0, 2, 2, 1, 1, 16, 32, 4, 16, 4, 8, 8, 0>(p, st);
-    return launch_cfg<0, 2, 2, 1, 1, 8, 8, 8, 8, 4, 8, 16, 0>(p, st);
-  }
-  if (sh == 1 && sw == 2) {
-    if (k == T16x32S) return launch_cfg<0, 1, 2, 1, 1, 16, 32, 4, 16, 4, 8, 8, 0>(p, st);
-    return launch_cfg<0, 1, 2, 1, 1, 8, 8, 8, 8, 4, 8, 16, 0>(p, st);
-  }
-  if (k == T16x32S) return launch_cfg<0, 2, 1, 1, 1, 16, 32, 4, 16, 4, 8, 8, 0>(p, st);
-  return launch_cfg<0, 2, 1, 1, 1, 8, 8, 8, 8, 4, 8, 16, 0>(p, st);
+  return run_k1(pl, p, ws, (hipStream_t)stream);
 }
 
 extern "C" int e2e_conv133_fwd(const e2e_in_chan_t* chans, int Cin, const float* w, const float* bias,
@@ -1249,29 +1281,6 @@ extern "C" int e2e_conv133_fwd_splitk(const e2e_in_chan_t* chans, int Cin, const
   return conv133_fwd_impl(chans, Cin, w, bias, live, y, part, B, Cout, Di, Hi, Wi, sd, sh, sw, ws, ws_bytes, stream);
 }
 
-// split-K plan of the data gradient (deep levels; the tiled paths only)
-static int plan_dgrad_ksplit(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  static const int knob = getenv("E2E_CONV_KSPLIT") ? atoi(getenv("E2E_CONV_KSPLIT")) : -1;
-  if (knob == 0 || knob == 1) return 1;
-  const bool tiled = (sh == 1 && sw == 1) || (sh == 2 && sw == 2);
-  if (!tiled) return 1;
-  const TileKind k = pick_tile(Hi, Wi, 1, 1);
-  if (k == T32) return 1;
-  int th, tw;
-  tile_dims(k, th, tw);
-  const int chunks = e2e::cdiv(Cout, 16);
-  const long long base = (long long)B * Di * e2e::cdiv(Hi, th) * e2e::cdiv(Wi, tw) * e2e::cdiv(Cin, 32);
-  long long ks = knob > 1 ? knob : 1024 / (base > 0 ? base : 1);
-  if (ks > 8) ks = 8;
-  if (ks > chunks / 2) ks = chunks / 2;
-  return ks < 2 ? 1 : (int)ks;
-}
-
-extern "C" long long e2e_conv133_dgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  const int ks = plan_dgrad_ksplit(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-  return ks <= 1 ? 0 : (long long)ks * B * Cin * Di * Hi * Wi * 4;
-}
-
 static int conv133_dgrad_impl(const float* dy, const float* w, const unsigned* live_t, const e2e_out_chan_t* outs,
                               int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, float* ws,
                               long long ws_bytes, void* stream) {
@@ -1280,8 +1289,9 @@ static int conv133_dgrad_impl(const float* dy, const float* w, const unsigned* l
   E2E_REQUIRE((sd == 1 || sd == 2) && (sh == 1 || sh == 2) && (sw == 1 || sw == 2), "conv133_dgrad: stride must be 1 or 2");
   hipStream_t st = (hipStream_t)stream;
   const int Do = (Di - 1) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
-  const bool tiled = (sh == 1 && sw == 1) || (sh == 2 && sw == 2);
-  if (!tiled) {     // in-plane anisotropic strides: rare, plain gather kernel
+  const K1Plan pl = plan_k1_dgrad({B, Cin, Cout, Di, Hi, Wi, sd, sh, sw}, ws != nullptr);
+  E2E_REQUIRE(ws_bytes >= pl.ws_bytes, "conv133_dgrad: workspace too small (%lld < %lld bytes)", ws_bytes, pl.ws_bytes);
+  if (pl.path == K1_GATHER) {
     const long long per = (long long)Di * Hi * Wi;
     dim3 grid((unsigned)e2e::cdivll(per, 256), Cin, B);
     e2e::note_kernel("conv133_dgrad_strided_gather");
@@ -1289,32 +1299,12 @@ static int conv133_dgrad_impl(const float* dy, const float* w, const unsigned* l
                        Ho, Wo, sd, sh, sw);
     return e2e::check_launch("conv133_dgrad_strided_kernel");
   }
-  // The forward kernel with transposed, tap-reversed weights.  Its "input planes" are dy's channels (a plain tensor,
-  // no shift; for a strided conv dy is read zero-dilated: only positions that are multiples of the stride carry a
-  // value, and only every sd-th depth slice is non-zero), its output planes are the virtual-concat input channels
-  // (un-shift on store).
   ConvParams p{};
   p.chans = nullptr; p.xin = dy; p.w = w; p.bias = nullptr; p.live = live_t; p.y = nullptr; p.part = nullptr; p.outs = outs;
   p.P = Cout; p.Q = Cin; p.wq_stride = 9; p.wp_stride = Cin * 9; p.live_words = e2e::cdiv(Cout, 32);
   p.B = B; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd; p.Do = Di; p.Ho = Hi; p.Wo = Wi;
   p.Ds = Do; p.Hs = Ho; p.Ws = Wo;
-  p.ksplit = 1; p.kpart = nullptr;
-  if (ws != nullptr) {
-    const long long need = e2e_conv133_dgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-    if (need > 0) {
-      E2E_REQUIRE(ws_bytes >= need, "conv133_dgrad: workspace too small (%lld < %lld bytes)", ws_bytes, need);
-      p.ksplit = plan_dgrad_ksplit(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
-      p.kpart = ws;
-    }
-  }
-  const TileKind k = pick_tile(Hi, Wi, 1, 1);
-  const int kind = k == T32 ? 0 : (k == T16 ? 1 : 2);
-  if (sh == 1) return launch_s1<1, 1, 1>(p, kind, st);
-  if (kind <= 1 && (Hi % 2) == 0 && (Wi % 2) == 0) {     // sub-pixel form: weights are read un-reversed
-    p.wq_stride = 9; p.wp_stride = Cin * 9;
-    return launch_sub(p, kind, st);
-  }
-  return launch_s1<1, 2, 2>(p, kind, st);
+  return run_k1(pl, p, ws, st);
 }
 
 extern "C" int e2e_conv133_dgrad(const float* dy, const float* w, const unsigned* live_t, const e2e_out_chan_t* outs,
@@ -1328,3 +1318,4 @@ extern "C" int e2e_conv133_dgrad_splitk(const float* dy, const float* w, const u
                                         long long ws_bytes, void* stream) {
   return conv133_dgrad_impl(dy, w, live_t, outs, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, ws, ws_bytes, stream);
 }
+

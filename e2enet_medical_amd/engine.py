@@ -396,38 +396,46 @@ class ConvOp:
             return False
         return self.live is None or self.density >= DENSE_MIN_DENSITY
 
+    def path(self, direction):
+        """The kernel family that serves the forward ('f') or the data gradient ('b'), in dispatch order: 'mm' (conv133_mm.hip),
+        'dense' (conv133_dense.hip), 'sparse' (the load-balanced plan of DSFF-masked full-resolution layers, conv133_sparse.hip),
+        'splitk' (K1 at the deep levels, chunks split over several workgroups, where the engine has a workspace) or 'plain' (K1).
+        Evaluated per call: tests and tools move the knobs and the kernel maps at run time."""
+        if self.use_mm(direction):
+            return "mm"
+        if self.use_dense():
+            return "dense"
+        if (self.sp_fwd if direction == "f" else self.sp_bwd) is not None:
+            return "sparse"
+        if getattr(self.eng, "fwd_ws", None) is not None and (self.fwd_ws_bytes if direction == "f" else self.dgrad_ws_bytes) > 0:
+            return "splitk"
+        return "plain"
+
     def forward(self):
         e = self.eng
         p = e.params
         b = self.out.shape[0]
-        di, hi, wi = self.in_dims
-        sd, sh, sw = self.stride
         L = lib()
-        ws = getattr(e, "fwd_ws", None)
-        if self.use_mm("f"):
+        ws = getattr(e, "fwd_ws", None)             # (the backward borrows it: it is idle then)
+        path = self.path("f")
+        bias, y, part = p[self.prefix + ".conv.bias"].data_ptr(), self.out.data.data_ptr(), self.part.data_ptr()
+        shape = (b, self.cout, *self.in_dims)
+        k1 = (self.chans.data_ptr(), self.cin, p[self.w_name].data_ptr(), bias, _ptr(self.live), y, part)
+        if path == "mm":
             if not hasattr(e, "_refresh_weight_caches"):
                 self.pack_mm_standalone("f")
-            L.conv133_fwd_mm(self.chans.data_ptr(), self.cin, self.wpk_fwd.data_ptr(), self.w_absmax.data_ptr(),
-                             p[self.prefix + ".conv.bias"].data_ptr(), self.x_absmax_ptr(), self.out.data.data_ptr(), self.part.data_ptr(),
-                             b, self.cout, di, hi, wi, _stream())
-        elif self.use_dense():
-            L.conv133_fwd_dense(self.chans.data_ptr(), self.cin, p[self.w_name].data_ptr(), p[self.prefix + ".conv.bias"].data_ptr(),
-                                _ptr(self.live), self.out.data.data_ptr(), self.part.data_ptr(), b, self.cout, di, hi, wi, ws.data_ptr(),
-                                ws.numel() * 4, _stream())
-        elif self.sp_fwd is not None:                       # DSFF-masked full-resolution layers: load-balanced plan
+            L.conv133_fwd_mm(self.chans.data_ptr(), self.cin, self.wpk_fwd.data_ptr(), self.w_absmax.data_ptr(), bias, self.x_absmax_ptr(),
+                             y, part, *shape, _stream())
+        elif path == "dense":
+            L.conv133_fwd_dense(*k1, *shape, ws.data_ptr(), ws.numel() * 4, _stream())
+        elif path == "sparse":
             sp = self.sp_fwd
-            L.conv133_fwd_sparse(sp.table.data_ptr(), self.cin, sp.wpk.data_ptr(), p[self.prefix + ".conv.bias"].data_ptr(),
-                                 sp.quads.data_ptr(), sp.woff.data_ptr(), sp.kmax, sp.qslot.data_ptr(), sp.flush_every, self.out.data.data_ptr(),
-                                 self.part.data_ptr(), b, self.cout, di, hi, wi, _stream())
-        elif ws is not None and self.fwd_ws_bytes > 0:      # deep levels: input-plane chunks split over several workgroups
-            L.conv133_fwd_splitk(self.chans.data_ptr(), self.cin, p[self.w_name].data_ptr(),
-                                 p[self.prefix + ".conv.bias"].data_ptr(), _ptr(self.live), self.out.data.data_ptr(),
-                                 self.part.data_ptr(), b, self.cout, di, hi, wi, sd, sh, sw, ws.data_ptr(), ws.numel() * 4,
-                                 _stream())
+            L.conv133_fwd_sparse(sp.table.data_ptr(), self.cin, sp.wpk.data_ptr(), bias, sp.quads.data_ptr(), sp.woff.data_ptr(), sp.kmax,
+                                 sp.qslot.data_ptr(), sp.flush_every, y, part, *shape, _stream())
+        elif path == "splitk":
+            L.conv133_fwd_splitk(*k1, *shape, *self.stride, ws.data_ptr(), ws.numel() * 4, _stream())
         else:
-            L.conv133_fwd(self.chans.data_ptr(), self.cin, p[self.w_name].data_ptr(), p[self.prefix + ".conv.bias"].data_ptr(),
-                          _ptr(self.live), self.out.data.data_ptr(), self.part.data_ptr(), b, self.cout, di, hi, wi,
-                          sd, sh, sw, _stream())
+            L.conv133_fwd(*k1, *shape, *self.stride, _stream())
         L.in_stats_finalize(self.part.data_ptr(), self.np, p[self.prefix + ".instnorm.weight"].data_ptr(),
                             p[self.prefix + ".instnorm.bias"].data_ptr(), IN_EPS, self.out.scale.data_ptr(),
                             self.out.shift.data_ptr(), self.out.mean.data_ptr(), self.out.rstd.data_ptr(), b,
@@ -438,8 +446,7 @@ class ConvOp:
         p, g = e.params, e.grads
         o = self.out
         b = o.shape[0]
-        di, hi, wi = self.in_dims
-        sd, sh, sw = self.stride
+        shape = (b, self.cin, self.cout, *self.in_dims)     # as every gradient entry point of the conv takes it
         L = lib()
         # dz (w.r.t. the post-activation output) -> dy (w.r.t. the pre-norm conv output), in place; the first pass (two sums per
         # instance) has already been done by the last writer of dz where that writer could (conv133_sparse.hip)
@@ -453,40 +460,39 @@ class ConvOp:
                        self.dy_absmax.data_ptr(), _stream())
         late = WGRAD_LATE and getattr(e, "_wg_active", None) is not None and o.data.numel() > WGRAD_STREAM_MAX_ELEMS
         if not late:
-            self._wgrad(e, L, g, o, b, di, hi, wi, sd, sh, sw, o.data.numel())
+            self._wgrad(shape, o.data.numel())
         if self.do_dgrad:
-            ws = getattr(e, "fwd_ws", None)
-            if self.use_mm("b"):
+            ws = getattr(e, "fwd_ws", None)             # (idle during backward)
+            path = self.path("b")
+            k1 = (o.grad.data_ptr(), p[self.w_name].data_ptr(), _ptr(self.live_t), self.outs.data_ptr())
+            if path == "mm":
                 if not hasattr(e, "_refresh_weight_caches"):
                     self.pack_mm_standalone("b")
                 L.conv133_dgrad_mm(o.grad.data_ptr(), self.dy_absmax.data_ptr(), self.wpk_bwd.data_ptr(), self.w_absmax.data_ptr(),
-                                   self.outs.data_ptr(), b, self.cin, self.cout, di, hi, wi, _stream())
-            elif self.use_dense():
-                L.conv133_dgrad_dense(o.grad.data_ptr(), p[self.w_name].data_ptr(), _ptr(self.live_t), self.outs.data_ptr(), b, self.cin, self.cout,
-                                      di, hi, wi, ws.data_ptr(), ws.numel() * 4, _stream())
-            elif self.sp_bwd is not None:
+                                   self.outs.data_ptr(), *shape, _stream())
+            elif path == "dense":
+                L.conv133_dgrad_dense(*k1, *shape, ws.data_ptr(), ws.numel() * 4, _stream())
+            elif path == "sparse":
                 sp = self.sp_bwd
                 table = self._bwd_table()
                 L.conv133_dgrad_sparse(o.grad.data_ptr(), sp.wpk.data_ptr(), sp.quads.data_ptr(), sp.woff.data_ptr(), sp.kmax, sp.pslot.data_ptr(),
-                                       table.data_ptr(), _ptr(sp.insum), sp.flush_every, b, self.cin, self.cout, di, hi, wi, _stream())
+                                       table.data_ptr(), _ptr(sp.insum), sp.flush_every, *shape, _stream())
                 for s in sp.fused_srcs:
                     s.sums_ready = True
-            elif ws is not None and self.dgrad_ws_bytes > 0:        # deep levels: split-K (the workspace is idle during backward)
-                L.conv133_dgrad_splitk(o.grad.data_ptr(), p[self.w_name].data_ptr(), _ptr(self.live_t), self.outs.data_ptr(),
-                                       b, self.cin, self.cout, di, hi, wi, sd, sh, sw, ws.data_ptr(), ws.numel() * 4, _stream())
+            elif path == "splitk":
+                L.conv133_dgrad_splitk(*k1, *shape, *self.stride, ws.data_ptr(), ws.numel() * 4, _stream())
             else:
-                L.conv133_dgrad(o.grad.data_ptr(), p[self.w_name].data_ptr(), _ptr(self.live_t), self.outs.data_ptr(),
-                                b, self.cin, self.cout, di, hi, wi, sd, sh, sw, _stream())
+                L.conv133_dgrad(*k1, *shape, *self.stride, _stream())
         if late:
             # full-resolution layers: the matrix-pipe weight gradient is issued BEHIND the layer's data gradient on the
             # weight-gradient stream, so that it runs beside the next layer's HBM-bound in_lrelu_bwd passes (no LDS, few
             # registers: they share CUs with it) instead of beside the LDS/VALU-bound data gradient
-            self._wgrad(e, L, g, o, b, di, hi, wi, sd, sh, sw, 0)
+            self._wgrad(shape, 0)
 
-    def _wgrad(self, e, L, g, o, b, di, hi, wi, sd, sh, sw, elems):
-        with _wgrad_stream(e, elems) as ws:
-            L.conv133_wgrad(self.chans.data_ptr(), o.grad.data_ptr(), g[self.w_name].data_ptr(), ws.data_ptr(),
-                            b, self.cin, self.cout, di, hi, wi, sd, sh, sw, self.dy_absmax.data_ptr(), self.x_absmax_ptr(), _stream())
+    def _wgrad(self, shape, elems):
+        with _wgrad_stream(self.eng, elems) as ws:
+            lib().conv133_wgrad(self.chans.data_ptr(), self.out.grad.data_ptr(), self.eng.grads[self.w_name].data_ptr(), ws.data_ptr(),
+                                *shape, *self.stride, self.dy_absmax.data_ptr(), self.x_absmax_ptr(), _stream())
 
     def wgrad_ws_bytes(self):
         di, hi, wi = self.in_dims
@@ -912,7 +918,7 @@ class Engine:
         # the job table is cached under the dispatch decisions it was built for (advisor, round 4: a table built while an op went to a
         # matrix-pipe kernel left that op's packed weights zero when tests / knobs sent it to the planned walk afterwards)
         def matrix_only(op):
-            return (op.use_mm("f") and op.use_mm("b")) or op.use_dense()
+            return all(op.path(d) in ("mm", "dense") for d in "fb")
         key = tuple(matrix_only(op) for op in self.conv_ops.values())
         if self._sparse_jobs is None or self._sparse_jobs[0] != key:
             jobs = [j for op in self.conv_ops.values() if not matrix_only(op) for j in op.sparse_jobs()]
@@ -962,7 +968,7 @@ class Engine:
                 L.conv133_input_ranges(self._range_table[0].data_ptr(), self._range_table[1], self._range_table[3].data_ptr(), _stream())
             self._range_key = (ptrs, state)
         # which layers run on K1m in which direction is part of what a packed set is valid for (tests and knobs move it)
-        dkey = (tuple((op.use_mm("f"), op.use_mm("b")) for op in self.conv_ops.values()), self.maps_generation, ptrs)
+        dkey = (tuple((op.path("f") == "mm", op.path("b") == "mm") for op in self.conv_ops.values()), self.maps_generation, ptrs)
         todo = "".join(d for d in directions if always or self._mm_packed.get(d) != (dkey, state))
         if not todo:
             return

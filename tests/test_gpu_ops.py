@@ -894,6 +894,183 @@ def test_conv133_data_gradient_split_k_matches_unsplit(B, src_desc, cout, dims, 
             assert torch.equal(g, a)
 
 
+def _k1_op(B, src_desc, cout, dims, stride, seeded):
+    """a ConvOp on a stub engine whose K1 entry points are driven directly (_k1_launch), planned for a first-writer data
+    gradient; unseeded: zero operands (the dispatch is a function of the shape alone)"""
+    from e2enet_medical_amd.engine import Act, ConvOp
+    cin = sum(c for c, _ in src_desc)
+    if seeded:
+        srcs = [_make_act((B, c) + dims, normed, 60 + i) for i, (c, normed) in enumerate(src_desc)]
+        w = seeded_input((cout, cin, 1, 3, 3), seed=3) * (1.0 / math.sqrt(cin * 9))
+        bias = seeded_input((cout,), seed=4) * 0.1
+    else:
+        srcs = [Act("t", (B, c) + dims, False, _dev()) for c, _ in src_desc]
+        for s in srcs:
+            s.data.zero_()
+        w, bias = torch.zeros(cout, cin, 1, 3, 3), torch.zeros(cout)
+    e = _eng_stub({"blk.conv.weight": w, "blk.conv.bias": bias, "blk.instnorm.weight": torch.ones(cout),
+                   "blk.instnorm.bias": torch.zeros(cout)})
+    e.batch = B
+    op = ConvOp(e, "blk", srcs, cout, stride)
+    op.out.alloc_grad()
+    op.out.grad.zero_()
+    op.plan_backward()
+    return e, op
+
+
+def _k1_launch(e, op, direction, ws_ptr=None, ws_bytes=0):
+    """one K1 launch through the C ABI, dense (the split-K entry point where a workspace is handed over); returns the dispatch note"""
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    B, w = op.out.shape[0], e.params["blk.conv.weight"].data_ptr()
+    if direction == "fwd":
+        entry = L.conv133_fwd if ws_ptr is None else L.conv133_fwd_splitk
+        args = (op.chans.data_ptr(), op.cin, w, e.params["blk.conv.bias"].data_ptr(), None, op.out.data.data_ptr(), op.part.data_ptr(),
+                B, op.cout, *op.in_dims, *op.stride)
+    else:
+        entry = L.conv133_dgrad if ws_ptr is None else L.conv133_dgrad_splitk
+        args = (op.out.grad.data_ptr(), w, None, op.outs.data_ptr(), B, op.cin, op.cout, *op.in_dims, *op.stride)
+    entry(*args, 0) if ws_ptr is None else entry(*args, ws_ptr, ws_bytes, 0)
+    torch.cuda.synchronize()
+    return (L.last_kernel() or b"").decode()
+
+
+_K1 = "conv133_kernel<mode=%d,s=%s,dil=%s,tile=%s,opw=4,nw=8,ck=%d,stg=%d,persist=%d> wgs=%d ksplit=%d"
+_S1, _S2, _S122, _S112, _S121 = (1, 1, 1), (2, 2, 2), (1, 2, 2), (1, 1, 2), (1, 2, 1)
+
+K1_DISPATCH_CASES = [
+    # (direction, B, Cin, Cout, (D,H,W), stride, workspace, dispatch note): one row per configuration of the K1 plan
+    # (csrc/conv133.hip, K1_CONFIGS), per persistent form and per split-K tile; the notes, grid and split counts included,
+    # are those of the library before the plan existed
+    # ---- forward, stride 1: 16x32 / 16x16 / 8x8 tiles, float4 staging and (W % 4 != 0) element staging
+    ("fwd", 1, 33, 34, (3, 40, 64), _S1, False, _K1 % (0, "1x1", "1x1", "16x32", 8, 1, 0, 40, 1)),
+    ("fwd", 1, 9, 7, (2, 17, 18), _S1, False, _K1 % (0, "1x1", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("fwd", 2, 33, 34, (3, 9, 20), _S1, False, _K1 % (0, "1x1", "1x1", "16x16", 16, 1, 0, 24, 1)),
+    ("fwd", 2, 13, 9, (4, 9, 11), _S1, False, _K1 % (0, "1x1", "1x1", "16x16", 16, 0, 0, 8, 1)),
+    ("fwd", 1, 100, 64, (2, 8, 8), _S1, False, _K1 % (0, "1x1", "1x1", "8x8", 16, 1, 0, 8, 1)),       # splits only with a workspace
+    ("fwd", 1, 9, 7, (1, 6, 5), _S1, False, _K1 % (0, "1x1", "1x1", "8x8", 16, 0, 0, 8, 1)),
+    # ---- forward, the three strided families on wide and on 8x8 output planes
+    ("fwd", 1, 35, 40, (6, 32, 64), _S2, False, _K1 % (0, "2x2", "1x1", "16x32", 8, 1, 0, 8, 1)),
+    ("fwd", 1, 12, 20, (2, 18, 22), _S122, False, _K1 % (0, "2x2", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("fwd", 1, 40, 33, (4, 4, 4), _S2, False, _K1 % (0, "2x2", "1x1", "8x8", 16, 0, 0, 8, 1)),
+    ("fwd", 1, 12, 20, (2, 20, 36), _S112, False, _K1 % (0, "1x2", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("fwd", 1, 12, 20, (2, 8, 12), _S112, False, _K1 % (0, "1x2", "1x1", "8x8", 16, 0, 0, 8, 1)),
+    ("fwd", 1, 12, 20, (2, 36, 20), _S121, False, _K1 % (0, "2x1", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("fwd", 1, 12, 20, (2, 12, 8), _S121, False, _K1 % (0, "2x1", "1x1", "8x8", 16, 0, 0, 8, 1)),
+    # ---- forward, persistent: a single input chunk and more than 1024 work items
+    ("fwd", 1, 4, 8, (33, 96, 192), _S1, False, _K1 % (0, "1x1", "1x1", "16x32", 8, 1, 1, 600, 1)),
+    ("fwd", 1, 4, 8, (1100, 16, 16), _S1, False, _K1 % (0, "1x1", "1x1", "16x16", 16, 1, 1, 552, 1)),
+    ("fwd", 1, 4, 8, (1100, 8, 8), _S1, False, _K1 % (0, "1x1", "1x1", "8x8", 16, 1, 1, 552, 1)),
+    ("fwd", 2, 4, 8, (17, 192, 384), _S122, False, _K1 % (0, "2x2", "1x1", "16x32", 8, 1, 1, 616, 1)),
+    # ---- forward, split-K: 16x16, 8x8, strided 8x8
+    ("fwd", 1, 160, 40, (3, 12, 40), _S1, True, _K1 % (0, "1x1", "1x1", "16x16", 16, 1, 0, 96, 5)),
+    ("fwd", 1, 128, 70, (5, 7, 5), _S1, True, _K1 % (0, "1x1", "1x1", "8x8", 16, 0, 0, 64, 4)),
+    ("fwd", 1, 64, 33, (4, 4, 4), _S2, True, _K1 % (0, "2x2", "1x1", "8x8", 16, 0, 0, 8, 2)),
+    # ---- data gradient, stride 1 (MODE 1) on the three tiles, both stagings
+    ("dgrad", 1, 33, 34, (3, 40, 64), _S1, False, _K1 % (1, "1x1", "1x1", "16x32", 8, 1, 0, 40, 1)),
+    ("dgrad", 1, 9, 7, (2, 17, 18), _S1, False, _K1 % (1, "1x1", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("dgrad", 2, 33, 34, (3, 9, 20), _S1, False, _K1 % (1, "1x1", "1x1", "16x16", 16, 1, 0, 24, 1)),
+    ("dgrad", 2, 13, 9, (4, 9, 11), _S1, False, _K1 % (1, "1x1", "1x1", "16x16", 16, 0, 0, 8, 1)),
+    ("dgrad", 1, 100, 64, (2, 8, 8), _S1, False, _K1 % (1, "1x1", "1x1", "8x8", 16, 1, 0, 8, 1)),
+    ("dgrad", 1, 9, 7, (1, 6, 5), _S1, False, _K1 % (1, "1x1", "1x1", "8x8", 16, 0, 0, 8, 1)),
+    # ---- data gradient of stride-(2,2) convs: sub-pixel (MODE 2) on even planes wider than 8, staging by the width of dy
+    ("dgrad", 1, 35, 40, (6, 32, 64), _S2, False, _K1 % (2, "1x1", "1x1", "16x32", 8, 1, 0, 48, 1)),
+    ("dgrad", 1, 12, 20, (2, 18, 22), _S122, False, _K1 % (2, "1x1", "1x1", "16x32", 8, 0, 0, 8, 1)),
+    ("dgrad", 1, 12, 20, (8, 16, 16), _S2, False, _K1 % (2, "1x1", "1x1", "16x16", 16, 1, 0, 8, 1)),
+    ("dgrad", 2, 10, 12, (5, 18, 10), _S122, False, _K1 % (2, "1x1", "1x1", "16x16", 16, 0, 0, 24, 1)),
+    # ---- ... zero-dilated MODE 1 where H or W is odd, and on planes of 8x8 and smaller
+    ("dgrad", 1, 12, 20, (2, 17, 22), _S122, False, _K1 % (1, "1x1", "2x2", "16x32", 8, 0, 0, 8, 1)),
+    ("dgrad", 1, 12, 20, (2, 9, 14), _S122, False, _K1 % (1, "1x1", "2x2", "16x16", 16, 0, 0, 8, 1)),
+    ("dgrad", 1, 40, 33, (4, 4, 4), _S2, False, _K1 % (1, "1x1", "2x2", "8x8", 16, 0, 0, 8, 1)),
+    # ---- ... the plain gather where the in-plane strides differ
+    ("dgrad", 1, 12, 20, (2, 8, 12), _S112, False, "conv133_dgrad_strided_gather"),
+    ("dgrad", 1, 12, 20, (2, 12, 8), _S121, False, "conv133_dgrad_strided_gather"),
+    # ---- data gradient, persistent (dy of at most one chunk of channels)
+    ("dgrad", 1, 4, 8, (33, 96, 192), _S1, False, _K1 % (1, "1x1", "1x1", "16x32", 8, 1, 1, 600, 1)),
+    ("dgrad", 1, 4, 8, (1100, 16, 16), _S1, False, _K1 % (1, "1x1", "1x1", "16x16", 16, 1, 1, 552, 1)),
+    ("dgrad", 1, 4, 8, (1100, 8, 8), _S1, False, _K1 % (1, "1x1", "1x1", "8x8", 16, 1, 1, 552, 1)),
+    ("dgrad", 1, 4, 8, (33, 96, 192), _S122, False, _K1 % (2, "1x1", "1x1", "16x32", 8, 1, 1, 600, 1)),
+    ("dgrad", 1, 4, 8, (1100, 16, 16), _S122, False, _K1 % (2, "1x1", "1x1", "16x16", 16, 1, 1, 552, 1)),
+    # ---- data gradient, split-K: 16x16, 8x8, strided 8x8 (dilated), sub-pixel 16x16; and the same shape without a workspace
+    ("dgrad", 1, 160, 128, (3, 12, 40), _S1, True, _K1 % (1, "1x1", "1x1", "16x16", 16, 1, 0, 184, 4)),
+    ("dgrad", 1, 128, 70, (5, 7, 5), _S1, True, _K1 % (1, "1x1", "1x1", "8x8", 16, 0, 0, 40, 2)),
+    ("dgrad", 1, 33, 64, (4, 4, 4), _S2, True, _K1 % (1, "1x1", "2x2", "8x8", 16, 0, 0, 16, 2)),
+    ("dgrad", 1, 20, 64, (2, 16, 16), _S2, True, _K1 % (2, "1x1", "1x1", "16x16", 16, 1, 0, 8, 2)),
+    ("dgrad", 1, 160, 128, (3, 12, 40), _S1, False, _K1 % (1, "1x1", "1x1", "16x16", 16, 1, 0, 48, 1)),
+]
+
+
+@pytest.mark.parametrize("case", K1_DISPATCH_CASES)
+def test_k1_dispatch_follows_the_plan(case):
+    """Every configuration the K1 host plan can choose (csrc/conv133.hip: plan_k1_fwd, plan_k1_dgrad) is reached by the smallest
+    shape that selects it, and the launch reports it with the grid and the split count that the separate tile / persistence /
+    split-K functions of the library before the plan produced for that shape."""
+    from e2enet_medical_amd._lib import lib
+    direction, B, cin, cout, dims, stride, with_ws, want = case
+    e, op = _k1_op(B, [(cin, False)], cout, dims, stride, seeded=False)
+    if with_ws:
+        query = lib().conv133_fwd_ws_bytes if direction == "fwd" else lib().conv133_dgrad_ws_bytes
+        nbytes = int(query(B, cin, cout, *dims, *stride))
+        assert nbytes > 0, "this shape is expected to split"
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=_dev())
+        note = _k1_launch(e, op, direction, ws.data_ptr(), nbytes)
+    else:
+        note = _k1_launch(e, op, direction)
+    print("k1 dispatch %s: %s" % (case[:7], note))
+    assert note == want
+
+
+K1_SPLITK_WS_CASES = [
+    # (direction, B, sources, Cout, (D,H,W)): the small shapes of the two split-K tests above
+    ("fwd", 1, [(100, True), (28, False)], 70, (5, 7, 5)),
+    ("fwd", 1, [(320, True)], 320, (2, 4, 4)),
+    ("fwd", 1, [(100, True), (60, False)], 40, (3, 12, 40)),
+    ("dgrad", 1, [(100, True), (28, False)], 70, (5, 7, 5)),
+    ("dgrad", 1, [(320, True)], 320, (2, 4, 4)),
+    ("dgrad", 1, [(100, True), (60, False)], 128, (3, 12, 40)),
+]
+
+
+@pytest.mark.parametrize("case", K1_SPLITK_WS_CASES)
+def test_k1_split_k_stays_inside_the_workspace_it_asked_for(case):
+    """The split-K entry points check the caller's byte count against the plan, and the launch writes what the same plan says: with
+    a workspace of exactly the queried bytes, followed in the same allocation by 1 MiB of guard words (ordinary memory: nothing
+    faults even if a plan were wrong), the guard comes back untouched, and the result -- forward: output and InstanceNorm
+    partials; data gradient: every source, in overwrite and in accumulate mode -- equals that of a roomy workspace bit for bit,
+    under the same dispatch note."""
+    from e2enet_medical_amd._lib import lib
+    direction, B, src_desc, cout, dims = case
+    e, op = _k1_op(B, src_desc, cout, dims, _S1, seeded=True)
+    query = lib().conv133_fwd_ws_bytes if direction == "fwd" else lib().conv133_dgrad_ws_bytes
+    nbytes = int(query(B, op.cin, cout, *dims, *_S1))
+    assert nbytes > 0 and nbytes % 4 == 0
+    sentinel, guard_words = 0x5A5A5A5A, (1 << 20) // 4
+    roomy = torch.empty(2 * (nbytes // 4) + guard_words, dtype=torch.float32, device=_dev())
+    op.out.grad.copy_(seeded_input(tuple(op.out.shape), seed=8))
+
+    def run(ws_ptr, ws_bytes, accumulate):
+        if direction == "fwd":
+            op.out.data.fill_(float("nan"))
+            op.part.fill_(float("nan"))
+        else:
+            for s in op.sources:
+                s._grad_written = accumulate
+            op.plan_backward()
+            for s in op.sources:
+                s.grad.copy_(s.data * 0.25) if accumulate else s.grad.fill_(float("nan"))
+        note = _k1_launch(e, op, direction, ws_ptr, ws_bytes)
+        return ([op.out.data.clone(), op.part.clone()] if direction == "fwd" else [s.grad.clone() for s in op.sources]), note
+    for accumulate in ((False,) if direction == "fwd" else (False, True)):
+        buf = torch.full((nbytes // 4 + guard_words,), sentinel, dtype=torch.int32, device=_dev())   # workspace, then the guard
+        tight, note = run(buf.data_ptr(), nbytes, accumulate)
+        wide, note_wide = run(roomy.data_ptr(), roomy.numel() * 4, accumulate)
+        print("k1 split-K workspace %s accumulate=%s: %d bytes, %s" % (case, accumulate, nbytes, note))
+        assert note == note_wide and int(note.rsplit("ksplit=", 1)[1]) > 1, (note, note_wide)
+        assert bool((buf[nbytes // 4:] == sentinel).all()), "the split-K launch wrote past the workspace it asked for"
+        for t, r in zip(tight, wide):
+            assert torch.isfinite(t).all() and torch.equal(t, r)
+
+
 @pytest.mark.parametrize("path,density", [("mm", 0.2), ("dense", 0.6), ("sparse", 0.2)])
 def test_conv133_masks_are_structural_on_every_path(path, density, monkeypatch):
     """A DSFF map is enforced by the kernels, not by pruned weights happening to be zero: with garbage left in the dead

@@ -802,3 +802,29 @@ def test_live_traffic_summary_and_bench_selection(tmp_path, monkeypatch):
     monkeypatch.setattr(subprocess, "run", lambda *a, **k: R())
     bench.collect_live_traffic()
     assert bench.LIVE_TRAFFIC is None and bench.traffic_source().startswith("profiles/")
+
+
+def test_k1_queries_equal_the_parent():
+    """The three host queries of the K1 conv (csrc/conv133.hip) are fields of the plan its launches follow.  Over a fixed sweep
+    of 4480 shapes -- every stride, planes of each tile class, thin and deep channel counts -- they answer what the separate
+    tile / split-K functions they replaced answered (tests/golden/conv133_k1_queries.json, recorded by
+    tools/make_golden_k1_queries.py at the commit named in the file, with E2E_CONV_* unset as here).  At least 200 rows split
+    in each direction, so the table cannot degenerate into the unsplit case."""
+    import importlib.util
+    import json
+    from e2enet_medical_amd._lib import lib
+    spec = importlib.util.spec_from_file_location("make_golden_k1_queries", os.path.join(ROOT, "tools", "make_golden_k1_queries.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    assert not {"E2E_CONV_PERSIST", "E2E_CONV_WGS", "E2E_CONV_KSPLIT"} & set(os.environ), "the table holds for the default knobs"
+    with open(os.path.join(ROOT, "tests", "golden", "conv133_k1_queries.json")) as fh:
+        g = json.load(fh)
+    assert {k: g[k] for k in mk.SWEEP} == mk.SWEEP, "the committed table was recorded over another sweep"
+    rows = list(mk.rows())
+    assert len(rows) == 4480 == len(g["fwd_ws_bytes"]) == len(g["dgrad_ws_bytes"]) == len(g["num_partials"])
+    assert sum(v > 0 for v in g["fwd_ws_bytes"]) >= 200 and sum(v > 0 for v in g["dgrad_ws_bytes"]) >= 200
+    L = lib()
+    bad = [(row, got, want) for row, got, want in
+           ((row, mk.query(L, row), (f, d, n)) for row, f, d, n in zip(rows, g["fwd_ws_bytes"], g["dgrad_ws_bytes"], g["num_partials"]))
+           if got != want]
+    assert not bad, "%d rows differ, first (row, (fwd, dgrad, partials) now, at the parent): %s" % (len(bad), bad[:3])
