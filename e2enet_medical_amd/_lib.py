@@ -242,6 +242,10 @@ SIGNATURES = {
     "e2e_nifti_decode_u8": (I, [P, LL, I, I, I, C.c_double, C.c_double, P, P, P]),
     "e2e_nifti_scan_grid_voxels": (LL, [I]),
     "e2e_nifti_scan": (I, [P, LL, I, I, I, C.c_double, C.c_double, P, P]),
+    "e2e_deflate_chunk_bytes": (I, []),
+    "e2e_deflate_slot_bytes": (I, []),
+    "e2e_deflate_encode": (I, [P, LL, I, P, P, P, P, P]),
+    "e2e_deflate_gather": (I, [P, P, P, LL, P, LL, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
@@ -250,7 +254,7 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_pp_minmax_ws_bytes", "e2e_pp_norm_ws_bytes", "e2e_pp_select_chunk", "e2e_pp_select_max_classes", "e2e_pp_select_ws_bytes",
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
               "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
-              "e2e_loader_crop_max_batch", "e2e_nifti_scan_grid_voxels"}
+              "e2e_loader_crop_max_batch", "e2e_nifti_scan_grid_voxels", "e2e_deflate_chunk_bytes", "e2e_deflate_slot_bytes"}
 
 
 class E2EError(RuntimeError):
@@ -288,7 +292,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 27          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 28          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -103,10 +103,19 @@ def softmax_to_f16(softmax: torch.Tensor, dims: Sequence[int], strides: Sequence
 
 
 def save_softmax_npz(softmax_f16: torch.Tensor, resampled_npz_fname: str, properties_dict: dict,
-                     region_class_order: Optional[Sequence[int]] = None):
+                     region_class_order: Optional[Sequence[int]] = None, device_deflate: bool = False):
     """``<case>.npz`` (key ``softmax``, fp16) and ``<case>.pkl`` as segmentation_export.py:117-122 leaves them for the ensembling
-    step (inference/ensemble_predictions.py); the pickle names ``regions_class_order`` when there is one."""
-    np.savez_compressed(resampled_npz_fname, softmax=softmax_f16.cpu().numpy())
+    step (inference/ensemble_predictions.py); the pickle names ``regions_class_order`` when there is one.  ``device_deflate``: the
+    device tensor is deflated where it lies (``deflate.savez``) and only compressed bytes are downloaded; ``np.load`` reads the same
+    array, the archive's bytes differ from the default route's.  A CPU or non-contiguous tensor is then a ValueError."""
+    if device_deflate:
+        from .. import deflate
+        if not (softmax_f16.is_cuda and softmax_f16.is_contiguous()):
+            raise ValueError("save_softmax_npz(device_deflate=True): the probabilities must be a contiguous device tensor (got %s)"
+                             % ("a non-contiguous tensor" if softmax_f16.is_cuda else "a CPU tensor",))
+        deflate.savez(resampled_npz_fname, softmax=softmax_f16)
+    else:
+        np.savez_compressed(resampled_npz_fname, softmax=softmax_f16.cpu().numpy())
     if region_class_order is not None:
         properties_dict = dict(properties_dict, regions_class_order=region_class_order)
     with open(resampled_npz_fname[:-4] + ".pkl", 'wb') as f:
@@ -116,7 +125,8 @@ def save_softmax_npz(softmax_f16: torch.Tensor, resampled_npz_fname: str, proper
 def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_backward: Optional[Sequence[int]] = None,
                         region_class_order: Optional[Sequence[int]] = None, force_separate_z: Optional[bool] = None,
                         order: int = 1, interpolation_order_z: int = 0, postprocessing=None,
-                        resampled_npz_fname: Optional[str] = None) -> np.ndarray:
+                        resampled_npz_fname: Optional[str] = None, device_deflate: bool = False,
+                        keep_on_device: bool = False) -> Union[np.ndarray, torch.Tensor]:
     """uint8 label volume in the ORIGINAL (uncropped) geometry from a device softmax [K, X, Y, Z]
     (reference predict.py:298-301 + segmentation_export.py:73-136).
 
@@ -125,7 +135,9 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
     label volume, before its one download; ``volume_per_voxel`` is the product of ``properties_dict['itk_spacing']``.
 
     ``resampled_npz_fname`` (the reference's argument of that name): the probabilities the labels are taken from -- on the case's own
-    grid, in its own axis order -- are also stored there as fp16, with the properties beside them (``save_softmax_npz``)."""
+    grid, in its own axis order -- are also stored there as fp16, with the properties beside them (``save_softmax_npz``;
+    ``device_deflate`` is handed on to it).  ``keep_on_device``: the label volume is returned as the device tensor it is, for a writer
+    that compresses it there."""
     assert softmax.is_cuda and softmax.dtype == torch.float32 and softmax.dim() == 4 and softmax.is_contiguous()
     k = softmax.shape[0]
     tb = [0, 1, 2] if transpose_backward is None else [int(i) for i in transpose_backward]
@@ -142,7 +154,8 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
         dims = [int(v) for v in after_crop]
         strides = [int(softmax.stride(1 + i)) for i in range(3)]
     if resampled_npz_fname is not None:
-        save_softmax_npz(softmax_to_f16(softmax, dims, strides), resampled_npz_fname, properties_dict, region_class_order)
+        save_softmax_npz(softmax_to_f16(softmax, dims, strides), resampled_npz_fname, properties_dict, region_class_order,
+                         device_deflate=device_deflate)
     bbox = properties_dict.get('crop_bbox')
     if bbox is not None:
         out_shape = tuple(int(v) for v in properties_dict.get('original_size_of_raw_data'))
@@ -162,26 +175,35 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
         for_which_classes, min_valid_object_sizes = postprocessing
         volume_per_voxel = float(np.prod(properties_dict['itk_spacing'], dtype=np.float64))
         seg = apply_postprocessing(seg, for_which_classes, min_valid_object_sizes, volume_per_voxel)
-    return seg.cpu().numpy()
+    return seg if keep_on_device else seg.cpu().numpy()
 
 
 def predict_cases(trainer, params: Sequence[dict], preprocessed: Iterable[Tuple[str, Tuple[np.ndarray, dict]]],
                   writer: Callable[[np.ndarray, str, dict], None], do_tta: bool = True, step_size: float = 0.5,
-                  all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None, save_npz: bool = False):
+                  all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None, save_npz: bool = False,
+                  device_deflate: bool = False):
     """The per-case loop of reference predict_cases (predict.py:273-331) on preprocessed cases
     ``(output_filename, (data [C,X,Y,Z], properties_dict))``; ``writer(seg_uint8, output_filename, properties_dict)``
     stores the label volume (the reference's SimpleITK NIfTI writer, segmentation_export.py:144-148, is host tooling).
     ``postprocessing``: see ``export_segmentation``.  ``save_npz``: ``<case>.npz`` and ``<case>.pkl`` beside every label file
-    (predict.py:303-304), what ``inference/ensemble_predictions.py`` merges."""
+    (predict.py:303-304), what ``inference/ensemble_predictions.py`` merges.  ``device_deflate``: the ``.npz`` is deflated on the
+    device, and a writer that carries ``accepts_device = True`` (``nifti.writer``) is called as ``writer(device_seg, output_filename,
+    properties_dict, device_deflate=True)``: it receives the label volume as a device tensor and compresses it there.  Any other
+    writer gets the host array as before."""
     done = []
+    to_writer = device_deflate and getattr(writer, "accepts_device", False)
     for output_filename, (d, dct) in preprocessed:
         if isinstance(d, str):
             d = np.load(d)
         softmax = predict_case_ensemble(trainer, params, d, do_tta, step_size, all_in_gpu, mixed_precision)
         tb = trainer.plans.get('transpose_backward') if trainer.plans.get('transpose_forward') is not None else None
         seg = export_segmentation(softmax, dct, tb, getattr(trainer, 'regions_class_order', None), postprocessing=postprocessing,
-                                  resampled_npz_fname=output_filename[:-7] + ".npz" if save_npz else None)
-        writer(seg, output_filename, dct)
+                                  resampled_npz_fname=output_filename[:-7] + ".npz" if save_npz else None,
+                                  device_deflate=device_deflate, keep_on_device=to_writer)
+        if to_writer:
+            writer(seg.contiguous(), output_filename, dct, device_deflate=True)
+        else:
+            writer(seg, output_filename, dct)
         done.append(output_filename)
     return done
 
@@ -234,7 +256,7 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
                         mixed_precision: bool = True, overwrite_existing: bool = True, mode: str = 'normal',
                         overwrite_all_in_gpu: bool = None, step_size: float = 0.5,
                         checkpoint_name: str = "model_final_checkpoint", segmentation_export_kwargs: dict = None,
-                        disable_postprocessing: bool = False, writer=None, reader=None):
+                        disable_postprocessing: bool = False, writer=None, reader=None, device_deflate: bool = False):
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.
     The per-case work is ``predict_cases`` above (softmax resident in HBM).  ``num_threads_*`` are accepted and unused: there are
@@ -243,7 +265,8 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     ``output_folder`` and applied to every case on the device (reference :337-356); when the file is missing the reference's warning
     is printed and the raw label maps are written.  A folder of raw cases (``<case>_XXXX.nii.gz``) is read through
     ``reader(list_of_files) -> (data [C, X, Y, Z], properties)`` -- default: the reference's SimpleITK loader -- and preprocessed on
-    the device by ``trainer.preprocess_patient``; without a reader such a folder is refused before anything is loaded."""
+    the device by ``trainer.preprocess_patient``; without a reader such a folder is refused before anything is loaded.
+    ``device_deflate`` (``simple_predict --device_deflate``): see ``predict_cases``."""
     import shutil
     from ..training.model_restore import load_model_and_checkpoint_files
     if mode != "normal":
@@ -298,4 +321,4 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
             yield out, (d, props)
     return predict_cases(trainer, params, cases(), writer if writer is not None else nifti_writer(), do_tta=tta,
                          step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision, postprocessing=postprocessing,
-                         save_npz=save_npz)
+                         save_npz=save_npz, device_deflate=device_deflate)

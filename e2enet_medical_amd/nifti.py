@@ -359,26 +359,63 @@ def build_header(shape, itk_spacing, itk_origin, itk_direction):
     return bytes(hdr)
 
 
-def write(seg, path, properties=None):
+def _geometry_of(properties):
+    properties = properties or {}
+    if all(k in properties for k in ("itk_spacing", "itk_origin", "itk_direction")):
+        return properties["itk_spacing"], properties["itk_origin"], properties["itk_direction"]
+    return _axes_identity()
+
+
+def _check_shape(shape):
+    if len(shape) != 3:
+        raise ValueError("write: the volume has shape %s, not three axes" % (tuple(shape),))
+    if any(int(v) < 1 or int(v) > 32767 for v in shape):
+        raise ValueError("write: an axis of %s does not fit dim (1 .. 32767)" % (tuple(shape),))
+
+
+def _write_device(seg, path, properties):
+    """``write`` of a device label volume: the 352 bytes in front of the voxels go through host zlib, the voxels are deflated on the
+    device (deflate.gzip_member) and only compressed bytes are downloaded"""
+    import torch
+    from . import deflate
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda):
+        raise ValueError("write(device_deflate=True): the volume must be a device tensor (got %s); without the flag the host "
+                         "compresses" % ("a CPU tensor" if isinstance(seg, torch.Tensor) else type(seg).__name__))
+    if not seg.is_contiguous():
+        raise ValueError("write(device_deflate=True): the volume is not contiguous (shape %s, strides %s)"
+                         % (tuple(seg.shape), tuple(seg.stride())))
+    _check_shape(seg.shape)
+    if not str(path).lower().endswith(".gz"):
+        raise ValueError("write(device_deflate=True): %s is no .gz path, there is nothing to compress" % (path,))
+    if seg.dtype != torch.uint8:
+        as_u8 = seg.to(torch.uint8)
+        if not bool((as_u8.to(seg.dtype) == seg).all().item()):
+            raise ValueError("write: the volume holds values that are no labels in [0, 255]")
+        seg = as_u8
+    body = build_header(tuple(seg.shape), *_geometry_of(properties)) + b"\0\0\0\0"
+    member = deflate.gzip_member(body, seg)
+    with open(path, "wb") as fh:
+        fh.write(member)
+
+
+def write(seg, path, properties=None, device_deflate=False):
     """A uint8 label volume ``[Z, Y, X]`` as a NIfTI-1 ``.nii.gz`` (``.nii`` for a path without ``.gz``) with the geometry of
     ``properties`` (``itk_origin``, ``itk_spacing``, ``itk_direction``; without them identity LPS and spacing 1).  Deterministic:
-    the same volume and geometry give the same bytes."""
+    the same volume and geometry give the same bytes.  ``device_deflate``: the volume is a contiguous device tensor (anything else
+    is a ValueError) and is compressed where it lies (csrc/deflate.hip); the file inflates to the same bytes as the default
+    route's, its compressed bytes differ."""
+    if device_deflate:
+        return _write_device(seg, path, properties)
     if hasattr(seg, "cpu"):
         seg = seg.cpu().numpy()
     seg = np.asarray(seg)
-    if seg.ndim != 3:
-        raise ValueError("write: the volume has shape %s, not three axes" % (seg.shape,))
-    if any(int(v) < 1 or int(v) > 32767 for v in seg.shape):
-        raise ValueError("write: an axis of %s does not fit dim (1 .. 32767)" % (seg.shape,))
+    _check_shape(seg.shape)
     if seg.dtype != np.uint8:
         as_u8 = seg.astype(np.uint8)
         if not np.array_equal(as_u8, seg):
             raise ValueError("write: the volume holds values that are no labels in [0, 255]")
         seg = as_u8
-    properties = properties or {}
-    spacing, origin, direction = _axes_identity()
-    if all(k in properties for k in ("itk_spacing", "itk_origin", "itk_direction")):
-        spacing, origin, direction = properties["itk_spacing"], properties["itk_origin"], properties["itk_direction"]
+    spacing, origin, direction = _geometry_of(properties)
     body = build_header(seg.shape, spacing, origin, direction) + b"\0\0\0\0"
     with open(path, "wb") as fh:
         if str(path).lower().endswith(".gz"):
@@ -390,9 +427,13 @@ def write(seg, path, properties=None):
             fh.write(memoryview(np.ascontiguousarray(seg)).cast("B"))
 
 
-def writer(seg, path, properties):
-    """``writer(seg_uint8, path, properties)`` of ``predict_cases``, ``validate`` and ``ensemble_predictions``"""
-    write(seg, path, properties)
+def writer(seg, path, properties, device_deflate=False):
+    """``writer(seg_uint8, path, properties)`` of ``predict_cases``, ``validate`` and ``ensemble_predictions``.  ``accepts_device``:
+    ``predict_cases(device_deflate=True)`` hands it the device label volume and the flag"""
+    write(seg, path, properties, device_deflate=device_deflate)
+
+
+writer.accepts_device = True
 
 
 def gt_reader(path):

@@ -65,8 +65,9 @@ def build_parser():
                         help='keep up to GIB GiB of preprocessed cases on the device and cut every training batch there with one '
                              'kernel launch (negative: no limit; 0: stage every case, still crop and pad on the device); '
                              'default: the host loader')
-    from . import nifti
+    from . import deflate, nifti
     nifti.add_argument(parser)
+    deflate.add_argument(parser)
     add_sparse_args(parser)
     return parser
 
@@ -161,7 +162,8 @@ def main(argv=None):
         writer, gt_reader = select_validation_callbacks(args)
         trainer.validate(save_softmax=args.npz, validation_folder_name=args.val_folder,
                          run_postprocessing_on_folds=not args.disable_postprocessing_on_folds, overwrite=args.val_disable_overwrite,
-                         determine_postprocessing=args.determine_postprocessing, writer=writer, gt_reader=gt_reader)
+                         determine_postprocessing=args.determine_postprocessing, writer=writer, gt_reader=gt_reader,
+                         device_deflate=args.device_deflate)
     print(f'finish training {args.Tconv} !!!')
     if network == '3d_lowres' and not args.disable_next_stage_pred:
         raise NotImplementedError("predict_next_stage (3d_lowres cascade) is outside the shiftConvPP hot path")

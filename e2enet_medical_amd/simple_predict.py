@@ -6,7 +6,7 @@ over a process group instead).  The input folder holds preprocessed cases (``<ca
 import argparse
 import os
 
-from . import nifti, paths
+from . import deflate, nifti, paths
 from .inference.predict import predict_from_folder
 from .utilities.task_name_id_conversion import convert_id_to_task_name
 
@@ -41,6 +41,7 @@ def build_parser():
     parser.add_argument('--disable_mixed_precision', default=False, action='store_true', required=False)
     parser.add_argument('--Tconv', type=str, required=False, default='shiftConvPP', help='ori;shiftConvPP')
     nifti.add_argument(parser)
+    deflate.add_argument(parser)
     return parser
 
 
@@ -82,7 +83,8 @@ def main(argv=None, reader=None, writer=None):
                                args.num_threads_preprocessing, args.num_threads_nifti_save, lowres_segmentations, args.part_id,
                                args.num_parts, not args.disable_tta, overwrite_existing=args.overwrite_existing, mode=args.mode,
                                overwrite_all_in_gpu=all_in_gpu, mixed_precision=not args.disable_mixed_precision,
-                               step_size=args.step_size, checkpoint_name=args.chk, writer=writer, reader=reader)
+                               step_size=args.step_size, checkpoint_name=args.chk, writer=writer, reader=reader,
+                               device_deflate=args.device_deflate)
 
 
 if __name__ == "__main__":

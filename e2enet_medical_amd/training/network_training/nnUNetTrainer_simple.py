@@ -875,7 +875,8 @@ class nnUNetTrainer_simple(object):
                  save_softmax: bool = True, use_gaussian: bool = True, overwrite: bool = True,
                  validation_folder_name: str = 'validation_raw', debug: bool = False, all_in_gpu: bool = False,
                  segmentation_export_kwargs: dict = None, run_postprocessing_on_folds: bool = True, writer=None, gt_reader=None,
-                 advanced_metrics: bool = False, nsd_tolerance=None, determine_postprocessing: bool = False):
+                 advanced_metrics: bool = False, nsd_tolerance=None, determine_postprocessing: bool = False,
+                 device_deflate: bool = False):
         """reference :1309-1479: every case of the validation split through the sliding-window prediction, exported to the case's
         original geometry, scored against the ground truth, ``summary.json`` written in the reference's structure.
 
@@ -897,7 +898,11 @@ class nnUNetTrainer_simple(object):
         to every label's dict and ``nsd_tolerance`` (mm) the normalized surface Dice, both computed on the device
         (evaluation/surface_distance.py).  A case scored on its original grid uses ``properties['itk_spacing'][::-1]`` (reference
         evaluator.py:299-301), one scored on the preprocessed grid its ``properties['spacing_after_resampling']`` (the plans' stage
-        ``current_spacing`` when the properties lack it), both in network-axis order; the case's entry in summary.json records it."""
+        ``current_spacing`` when the properties lack it), both in network-axis order; the case's entry in summary.json records it.
+
+        ``device_deflate`` (``simple_main --device_deflate``): the probabilities of ``save_softmax`` are rounded to fp16 and permuted
+        on the device (``softmax_to_f16``) and deflated there (``deflate.savez``); only compressed bytes are downloaded.  ``np.load``
+        reads the array the default route stores, the archive's bytes differ."""
         import json
         import shutil
         from ...inference.predict import export_segmentation
@@ -994,8 +999,16 @@ class nnUNetTrainer_simple(object):
                     if save_softmax:
                         # (float16 like segmentation_export.py:109; the reference stores the volume on the case's own grid, here the
                         #  network's grid is stored: it is what an ensembling step on this engine reads back)
-                        np.savez_compressed(join(output_folder, fname + ".npz"),
-                                            softmax=softmax.permute(0, *[i + 1 for i in tb]).cpu().numpy().astype(np.float16))
+                        if device_deflate:
+                            from ... import deflate
+                            from ...inference.predict import softmax_to_f16
+                            dev = softmax.contiguous()
+                            deflate.savez(join(output_folder, fname + ".npz"),
+                                          softmax=softmax_to_f16(dev, [int(dev.shape[1 + i]) for i in tb],
+                                                                 [int(dev.stride(1 + i)) for i in tb]))
+                        else:
+                            np.savez_compressed(join(output_folder, fname + ".npz"),
+                                                softmax=softmax.permute(0, *[i + 1 for i in tb]).cpu().numpy().astype(np.float16))
                     writer(seg, out_nii, properties)
                     case_properties.append(properties)
                     gt_path = join(self.gt_niftis_folder, fname + ".nii.gz") if self.gt_niftis_folder else None

@@ -816,6 +816,30 @@ long long e2e_nifti_scan_grid_voxels(int datatype);
 int e2e_nifti_scan(const void* raw, long long nvox, int datatype, int swap, int scale, double slope, double inter,
                    unsigned long long* out, void* stream);
 
+/* ---- N5: raw DEFLATE (RFC 1951) of a device buffer (csrc/deflate.hip) ----------------------------------------------------
+ * Replaces: the download of an uncompressed volume and the host's zlib pass over it (np.savez_compressed of the -z
+ * probabilities, gzip of a label volume).  The stream is the simplest one every inflater takes: the input is cut into chunks of
+ * e2e_deflate_chunk_bytes() bytes, one workgroup per chunk, no workgroup waits for another.  A chunk is one non-final
+ * fixed-Huffman block whose only matches have distance `elem` ("the same element again": byte i equals byte i - elem; a match may
+ * reach back in front of the chunk, the window is the input), lengths 3..258, a maximal run inside the chunk cut into 258s and one
+ * match for the rest (literals when fewer than 3 bytes are left); everything else is a literal.  An empty stored block behind the
+ * end-of-block symbol byte-aligns the chunk.  A chunk whose fixed-Huffman form is longer than 5 + its bytes is one stored block.
+ * The caller closes the stream with the bytes 03 00 (an empty final fixed block).
+ *   encode: slots [nchunks][e2e_deflate_slot_bytes()] receives every chunk's bytes, counts[nchunks] their number; nchunks =
+ *     ceil(nbytes / chunk).  *crc (device) receives zlib's CRC-32 of the input: one CRC per chunk (chunk_crcs[nchunks], workspace),
+ *     combined by one small kernel with the shift operator of a whole chunk, applied once per chunk.  elem: 1, 2, 4 or 8, a
+ *     divisor of nbytes.  nbytes == 0 only sets *crc = 0.  The bytes depend on the input and elem only.
+ *   gather: out[offsets[c] .. offsets[c] + counts[c]) = slot c, offsets the exclusive prefix sum of counts (64-bit, device); a chunk
+ *     that would end behind out_bytes is not copied.
+ * Refused with E2E_ERR_ARG before anything is launched: elem not 1, 2, 4, 8 or no divisor of nbytes, nbytes < 0 or > 2^37, a null
+ * pointer, slots not aligned to 16 bytes.                                                                                      */
+int e2e_deflate_chunk_bytes(void);
+int e2e_deflate_slot_bytes(void);
+int e2e_deflate_encode(const void* src, long long nbytes, int elem, unsigned char* slots, unsigned* counts, unsigned* chunk_crcs,
+                       unsigned* crc, void* stream);
+int e2e_deflate_gather(const unsigned char* slots, const unsigned* counts, const long long* offsets, long long nchunks,
+                       unsigned char* out, long long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
