@@ -533,7 +533,8 @@ def test_conv133_wgrad_alternative_paths_forced(env):
     import subprocess
     import sys
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k",
-                        "test_conv133_fwd_bwd or test_wgrad_stays_inside_the_workspace_it_asked_for or test_convT_fwd_bwd",
+                        "test_conv133_fwd_bwd or test_wgrad_stays_inside_the_workspace_it_asked_for or test_convT_fwd_bwd"
+                        " or test_convT_dgrad_first_and_later_writer",
                         "-p", "no:cacheprovider"],
                        env=dict(os.environ, **env), capture_output=True, text=True, timeout=900,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -1343,3 +1344,395 @@ def test_convT_h2_and_bf3_vs_fp64(cin, cout, dims, kernel, mag):
     for i, name in enumerate(("forward", "data gradient", "weight gradient")):
         assert res["h2"][i] <= 2e-6 and res["bf3"][i] <= 2e-6, (name, res)
         assert res["h2"][i] <= 1.5 * res["bf3"][i] + 1e-7, (name, res)
+
+
+# ---- who writes an activation's gradient buffer, and when ---------------------------------------------------------------------
+# The first consumer in backward order overwrites the buffer (it holds garbage: NaN here), every later one adds to it
+# (accumulate = 1, Act.claim_grad_write), and the last writer may leave the two per-instance sums of the producer's InstanceNorm +
+# LeakyReLU backward as records.  The 1x3x3 convs and the heads are held to this elsewhere; below: transposed conv and max pool.
+
+def _prefill(shape, seed):
+    """what an earlier consumer left in a gradient buffer: order 1, both signs, a tenth of the cells exactly 0"""
+    g = torch.Generator().manual_seed(seed)
+    p = torch.randn(shape, generator=g)
+    p[torch.rand(shape, generator=g) < 0.1] = 0.0
+    return p
+
+
+def _ct_dgrad_note(default):
+    """dispatch note of the transposed-conv data gradient under this process's knobs (E2E_CT_BF3=0: the split-operand forms fall
+    back to the fp32 matrix instructions; E2E_CT_H2=0: fp16 two-piece becomes bf16 three-piece)"""
+    if default.startswith(("convT_dgrad_h2<", "convT_dgrad_bf3<")):
+        kdh = default[default.index("<"):]
+        if os.environ.get("E2E_CT_BF3", "1") == "0":
+            return "convT_dgrad_v3" + kdh
+        if os.environ.get("E2E_CT_H2", "1") != "0":
+            return default
+        return "convT_dgrad_bf3" + kdh
+    return default
+
+
+CT_WRITER_CASES = [
+    # (B, Cin, Cout, (D,H,W), kernel, density, range words handed over, dispatch note by default)
+    (1, 5, 3, (2, 3, 5), (1, 1, 1), 1.0, False, "convT_dgrad_gather<1>"),          # smallest gather form
+    (2, 9, 5, (2, 3, 6), (1, 1, 2), 1.0, False, "convT_dgrad_gather<2>"),          # the three KT = 2 instantiations
+    (2, 9, 5, (2, 3, 6), (1, 2, 1), 1.0, False, "convT_dgrad_gather<2>"),
+    (2, 9, 5, (2, 3, 6), (2, 1, 1), 1.0, False, "convT_dgrad_gather<2>"),
+    (1, 9, 5, (3, 6, 8), (2, 2, 1), 1.0, False, "convT_dgrad_gather<4>"),          # kw == 1
+    (1, 9, 5, (2, 9, 7), (1, 2, 2), 1.0, False, "convT_dgrad_gather<4>"),          # odd W
+    (2, 40, 33, (3, 5, 7), (2, 2, 2), 0.3, False, "convT_dgrad_gather<8>"),        # masked: two liveness words, the second with one bit
+    (1, 40, 24, (4, 32, 32), (2, 2, 2), 1.0, True, "convT_dgrad_gather<8>"),       # GEMM shape with 128 tiles: the low side of min_tiles = 256
+    (2, 40, 24, (4, 32, 32), (2, 2, 2), 1.0, True, "convT_dgrad_h2<4>"),           # 256 tiles: the high side
+    (2, 40, 24, (4, 32, 32), (2, 2, 2), 1.0, False, "convT_dgrad_bf3<4>"),         # no range words: bf16 three-piece form
+    (2, 72, 40, (4, 32, 32), (2, 2, 2), 0.3, True, "convT_dgrad_h2<4>"),           # two Cin groups (the second: 8 live rows), two Cout chunks (the second ragged), masked
+    (2, 20, 70, (4, 32, 32), (1, 2, 2), 1.0, False, "convT_dgrad_bf3<2>"),         # three Cout chunks
+    (2, 20, 40, (4, 32, 32), (2, 1, 2), 1.0, True, "convT_dgrad_h2<2>"),           # KDH = 2 with kd = 2: DyTile's ii = rr / kh
+    (2, 72, 40, (6, 20, 34), (2, 2, 2), 0.3, False, "convT_dgrad_v3<4>"),          # W % 32 != 0; 4080 voxels: ragged last tile (16 voxels) per sample, ragged group and chunk
+    (2, 20, 70, (6, 20, 34), (1, 2, 2), 0.5, False, "convT_dgrad_v3<2>"),          # three chunks, masked
+    (2, 20, 40, (6, 20, 34), (2, 1, 2), 1.0, False, "convT_dgrad_v3<2>"),          # kd = 2, kh = 1 on the fp32 matrix form
+]
+
+
+@pytest.mark.parametrize("case", CT_WRITER_CASES)
+def test_convT_dgrad_first_and_later_writer(case):
+    """e2e_convT_dgrad as the first writer of dx (overwrite into NaN), as a later writer onto zeros (the same bits: every form
+    computes 0 + x in the same chunk order) and onto a seeded prefill P (P + dx, twice: bit-identical, no atomics on this path),
+    against fp64 conv_transpose3d autograd: max-abs < 2e-4 of the scale (test_convT_fwd_bwd's bar), on the split-operand forms also
+    relative L2 <= 2e-6 (test_convT_h2_and_bf3_vs_fp64's bar).  One case per accumulating form and per untested kernel shape: the
+    gather kernel's `*dst += acc`, v3's per-chunk `accumulate || o0 > 0`, and the old-dx prefetch of convT_dgrad_bf3_kernel (indexed
+    by tile, 16-voxel block and channel row); a kernel that drops, doubles or misplaces the old value is off by order 1.  The
+    kernels (2,1,2) and (2,2,1) had no reference comparison at all: their forward and weight gradient are checked here too."""
+    from e2enet_medical_amd.engine import UpOp
+    from e2enet_medical_amd._lib import lib
+    B, cin, cout, dims, kernel, density, words, note_default = case
+    kd, kh, kw = kernel
+    spatial = dims[0] * dims[1] * dims[2]
+    tiles = -(-spatial // 32) * B
+    gemm = kw == 2 and kd * kh in (2, 4) and dims[2] % 2 == 0 and spatial % 4 == 0 and tiles >= 256       # plan_convT_dgrad
+    assert gemm == (not note_default.startswith("convT_dgrad_gather")), "the case does not sit where its note says"
+    note = _ct_dgrad_note(note_default)
+    split = note.startswith(("convT_dgrad_h2<", "convT_dgrad_bf3<"))
+    L = lib()
+    src = _make_act((B, cin) + dims, True, 601)
+    w = seeded_input((cin, cout) + kernel, seed=602) * (1.0 / math.sqrt(cin))
+    km = _kmask(cin, cout, density, 603)
+    if km is not None:
+        w = w * km.view(cin, cout, 1, 1, 1)
+    e = _eng_stub({"up.weight": w})
+    op = UpOp(e, "up.weight", src, cout, kernel)
+    if km is not None:
+        rows = torch.empty(cin * ((cout + 31) // 32), dtype=torch.int32, device=e.device)
+        cols = torch.empty(cout * ((cin + 31) // 32), dtype=torch.int32, device=e.device)
+        L.dsff_expand(km.to(e.device).data_ptr(), None, rows.data_ptr(), cols.data_ptr(), cin, cout, 1, 0)
+        op.live, op.live_t = cols, rows
+    x64 = _act_value(src).double().requires_grad_(True)
+    w64 = w.double().requires_grad_(True)
+    y64 = F.conv_transpose3d(x64, w64, stride=kernel)
+    dy = seeded_input(tuple(y64.shape), seed=604)
+    y64.backward(dy.double())
+    dx64 = x64.grad
+    dyd = dy.to(e.device)
+    word = _absmax_word(dyd)
+    if words:
+        op.set_ranges(float(x64.detach().abs().max()), float(w.abs().max()), 1.0)
+    dya = word.data_ptr() if words else None
+    dyb = op._w(2) if words else None
+    live_t = op.live_t.data_ptr() if op.live_t is not None else None
+
+    def launch(prefill, accumulate):
+        dx = prefill.to(e.device)
+        L.convT_dgrad(dyd.data_ptr(), e.params["up.weight"].data_ptr(), live_t, dx.data_ptr(), accumulate, B, cin, cout, *dims, *kernel,
+                      op._w(1), dya, dyb, 0)
+        torch.cuda.synchronize()
+        got_note = (L.last_kernel() or b"").decode()
+        assert got_note.startswith(note), (got_note, note)
+        return dx.cpu()
+
+    def check(got, ref, what):
+        assert torch.isfinite(got).all(), what + ": cells left unwritten"
+        err = float((got.double() - ref).abs().max())
+        rel = float((got.double() - ref).norm() / ref.norm())
+        print("convT dgrad %s %s %s: max-abs %.3e (scale %.3g), rel-L2 %.3e" % (case[:7], note, what, err, float(ref.abs().max()), rel))
+        assert err < 2e-4 * max(1.0, float(ref.abs().max())), what
+        if split:
+            assert rel <= 2e-6, what
+
+    shape = (B, cin) + dims
+    P = _prefill(shape, 605)
+    first = launch(torch.full(shape, float("nan")), 0)
+    check(first, dx64, "first writer")
+    onto_zeros = launch(torch.zeros(shape), 1)
+    assert torch.equal(onto_zeros, first), "accumulating onto zeros differs from overwriting"
+    later = launch(P, 1)
+    check(later, P.double() + dx64, "later writer")
+    again = launch(P, 1)
+    assert torch.equal(again.view(torch.int32), later.view(torch.int32)), "two accumulating launches differ"
+
+    if kernel in ((2, 1, 2), (2, 2, 1)):
+        op.forward()
+        torch.cuda.synchronize()
+        note_f = (L.last_kernel() or b"").decode()
+        err_f = float((op.out.data.cpu().double() - y64.detach()).abs().max())
+        dw = torch.full(tuple(w.shape), float("nan"), device=e.device)
+        L.convT_wgrad(src.data.data_ptr(), src.scale.data_ptr(), src.shift.data_ptr(), 0.01, dyd.data_ptr(), dw.data_ptr(),
+                      e.wgrad_ws.data_ptr(), B, cin, cout, *dims, *kernel, op._w(0), dya, dyb, 0)
+        torch.cuda.synchronize()
+        note_w = (L.last_kernel() or b"").decode()
+        scale_w = max(1.0, float(w64.grad.abs().max()))
+        err_w = float((dw.cpu().double() - w64.grad).abs().max())
+        print("convT %s: forward %s max-abs %.3e; weight gradient %s max-abs %.3e (scale %.3g)" % (case[:7], note_f, err_f, note_w, err_w, scale_w))
+        assert err_f < 2e-5, "forward"
+        assert torch.isfinite(dw).all() and err_w < 2e-4 * scale_w, "weight gradient"
+
+
+def _pool_grid_data(shape, seed):
+    """multiples of 0.25 in [-0.5, 0.5], the middle levels the most frequent: more than a quarter of the windows hold their maximum
+    twice even where a window is two cells.  Equal inputs stay equal behind the on-load affine and LeakyReLU, unequal ones stay at
+    least 0.25 * 0.5 * 0.01 apart, so fma-versus-multiply-add rounding cannot reorder them."""
+    return (seeded_input(shape, seed=seed) * 0.6).round().clamp(-2, 2) * 0.25
+
+
+def _tied_share(v, kernel):
+    """share of the pooling windows of v whose maximum is attained more than once"""
+    kd, kh, kw = kernel
+    win = v.unfold(2, kd, kd).unfold(3, kh, kh).unfold(4, kw, kw)
+    win = win.reshape(win.shape[:5] + (-1,))
+    return float(((win == win.max(-1, keepdim=True).values).sum(-1) > 1).float().mean())
+
+
+POOL_WRITER_CASES = [
+    # (B, C, (D,H,W), kernel, float4 kernel (maxpool_bwd_w2_kernel) or the generic one, NaNs planted)
+    (2, 5, (4, 6, 8), (2, 2, 2), True, False),
+    (1, 3, (5, 7, 8), (2, 2, 2), True, False),       # D and H remainders
+    (1, 3, (3, 10, 8), (1, 2, 2), True, False),
+    (1, 3, (3, 5, 8), (1, 1, 2), True, False),
+    (1, 3, (3, 10, 6), (1, 2, 2), False, False),
+    (1, 4, (5, 7, 9), (2, 2, 2), False, False),
+    (1, 3, (4, 6, 5), (2, 2, 1), False, False),
+    (2, 5, (4, 6, 8), (2, 2, 2), True, True),
+    (1, 4, (5, 7, 9), (2, 2, 2), False, True),
+]
+
+
+@pytest.mark.parametrize("B,c,dims,kernel,w2,nans", POOL_WRITER_CASES)
+def test_maxpool_bwd_first_and_later_writer(B, c, dims, kernel, w2, nans):
+    """e2e_maxpool_bwd as first writer (overwrite into NaN), as later writer onto zeros and onto a seeded prefill P, bit-exact
+    against torch-CPU fp32 autograd of max_pool3d (P + x.grad is one fp32 add per cell on both sides), on data with ties in most
+    windows (the first maximum of a window takes the gradient), on volumes with cells outside every window (they receive 0 / keep
+    P), for a normalised source (a third of the channels negative-gamma) and a raw one, and with NaNs planted -- two of them in
+    one window: the forward gives NaN, the backward routes to the window's last NaN, as the kernels' `v > m || v != v` does."""
+    from e2enet_medical_amd.engine import PoolOp
+    kd, kh, kw = kernel
+    D, H, W = dims
+    assert w2 == (kw == 2 and W % 4 == 0 and kd <= 2 and kh <= 2)           # e2e_maxpool_bwd's dispatch
+    shape = (B, c) + dims
+    stub = _eng_stub({})
+    for normed in (True, False):
+        src = _make_act(shape, normed, 611)
+        data = _pool_grid_data(shape, 612)
+        if nans:
+            data[0, 0, 0, 0, 0] = float("nan")
+            data[0, 0, 1, 1, 1] = float("nan")                               # same window, later in scan order: takes the gradient
+            data[B - 1, 2, 2, 3, 5] = float("nan")
+        src.data.copy_(data)
+        op = PoolOp(stub, "down", src, kernel)
+        xl = _act_value(src).requires_grad_(True)
+        tied = _tied_share(xl.detach(), kernel)
+        assert tied > 0.25, "the reference data has too few tied windows (%.2f)" % tied
+        y = F.max_pool3d(xl, kernel)
+        dy = seeded_input(tuple(y.shape), seed=613)
+        y.backward(dy)
+        op.forward()
+        got_y = op.out.data.cpu()
+        assert torch.equal(got_y.isnan(), y.detach().isnan()) and int(y.detach().isnan().sum()) == (2 if nans else 0)
+        assert (torch.nan_to_num(got_y) - torch.nan_to_num(y.detach())).abs().max() < 1e-6     # fma vs mul+add in the on-load affine
+        op.out.alloc_grad()
+        op.plan_backward()
+        op.out.grad.copy_(dy)
+        P = _prefill(shape, 614)
+        inside = torch.zeros(shape, dtype=torch.bool)
+        inside[:, :, :D // kd * kd, :H // kh * kh, :W // kw * kw] = True
+
+        def run(prefill, accumulate):
+            src.grad.copy_(prefill)
+            op.acc = accumulate
+            op.backward()
+            torch.cuda.synchronize()
+            return src.grad.cpu()
+        first = run(torch.full(shape, float("nan")), 0)
+        assert torch.equal(first, xl.grad), "overwrite: routing differs from ATen's (first maximum, last NaN)"
+        assert bool((first[~inside] == 0).all())
+        assert torch.equal(run(torch.zeros(shape), 1), first), "accumulating onto zeros differs from overwriting"
+        later = run(P, 1)
+        assert torch.equal(later, P + xl.grad), "accumulate"
+        assert torch.equal(later[~inside], P[~inside])
+        if nans:
+            g = xl.grad
+            assert g[0, 0, 0, 0, 0] == 0 and g[0, 0, 1, 1, 1] == dy[0, 0, 0, 0, 0] and g[B - 1, 2, 2, 3, 5] == dy[B - 1, 2, 1, 1, 2]
+        print("maxpool %s %s %s: %.0f %% of the windows tied, %d cells outside every window" %
+              ((B, c) + dims, kernel, "normalised" if normed else "raw", 100 * tied, int((~inside).sum())))
+
+
+@pytest.mark.parametrize("B,c,dims,kernel", [(2, 3, (8, 16, 40), (2, 2, 2)),       # 320 pairs per instance: two records, the second from a partly idle block
+                                             (2, 3, (4, 16, 40), (1, 2, 2)),       # the same count
+                                             (1, 2, (4, 8, 8), (2, 2, 2))])        # one record
+def test_maxpool_bwd_fused_records_vs_fp64(B, c, dims, kernel):
+    """The records that the pooling backward leaves as last writer of dz: for every instance (n, c) the np records at
+    [(nc * np + i) * 2 + {0, 1}] -- the layout in_bwd_tile_sums_kernel reads -- add up to
+        S1 = sum dz lrelu'(u),   S2 = sum dz lrelu'(u) xhat       (dz: the final dx; u = a y + b; xhat = (y - mean) rstd)
+    evaluated in fp64 from the same fp32 a, b, mean, rstd, y, within 2^-19 of sum |dz lrelu'| and sum |dz lrelu' xhat|: a thread
+    adds at most 16 terms in fp32 (under 2^-20 of the absolute sum) and forms xhat with two fp32 roundings, everything above a
+    thread is fp64.  No kink exclusion: the kernel branches on fmaf(a, y, b) > 0, whose sign is that of the exact a y + b.  Both
+    writer modes; dx is bit-identical to the launch without records, every record is written, nothing behind them is."""
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    D, H, W = dims
+    kd, kh, kw = kernel
+    npr = int(L.maxpool_bwd_num_records(D, H, W, kd, kh, kw))
+    assert npr == -(-((D // kd) * (H // kh) * (W // 4)) // 256)
+    for d0, k0 in (((4, 6, 6), (2, 2, 2)), ((5, 6, 8), (2, 2, 2)), ((4, 6, 8), (2, 2, 1))):
+        assert int(L.maxpool_bwd_num_records(*d0, *k0)) == 0
+    shape = (B, c) + dims
+    n = B * c
+    src = _make_act(shape, True, 621)
+    src.mean.copy_(seeded_input((n,), seed=622) * 0.2)
+    src.rstd.copy_(0.5 + torch.rand(n, generator=torch.Generator().manual_seed(623)))
+    dy = seeded_input((B, c, D // kd, H // kh, W // kw), seed=624).to(_dev())
+    P = _prefill(shape, 625)
+    sentinel, guard_words = 0x5A5A5A5A, 4096
+    rec_words = n * npr * 2 * 2                                              # doubles as int32 words
+
+    def run(prefill, accumulate, buf):
+        dx = prefill.to(_dev())
+        L.maxpool_bwd(src.data.data_ptr(), src.scale.data_ptr(), src.shift.data_ptr(), 0.01, dy.data_ptr(), dx.data_ptr(), accumulate,
+                      B, c, D, H, W, kd, kh, kw, src.mean.data_ptr() if buf is not None else None,
+                      src.rstd.data_ptr() if buf is not None else None, buf.data_ptr() if buf is not None else None, 0)
+        torch.cuda.synchronize()
+        return dx.cpu()
+
+    def bc(t):
+        return t.cpu().double().view(B, c, 1, 1, 1)
+    yv = src.data.cpu().double()
+    u = bc(src.scale) * yv + bc(src.shift)
+    slope = torch.where(u > 0, torch.ones_like(u), torch.full_like(u, 0.01))
+    xhat = (yv - bc(src.mean)) * bc(src.rstd)
+    for what, prefill, accumulate in (("later writer", P, 1), ("first writer", torch.full(shape, float("nan")), 0)):
+        buf = torch.full((rec_words + guard_words,), sentinel, dtype=torch.int32, device=_dev())     # records, then the guard
+        rec = buf[:rec_words].view(torch.float64)
+        rec.fill_(float("nan"))
+        dx = run(prefill, accumulate, buf)
+        plain = run(prefill, accumulate, None)
+        assert torch.equal(dx.view(torch.int32), plain.view(torch.int32)), what + ": dx differs with records"
+        assert bool((buf[rec_words:] == sentinel).all()), what + ": wrote past the records"
+        recs = rec.cpu().view(n, npr, 2)
+        assert torch.isfinite(recs).all(), what + ": a record was left unwritten"
+        got = recs.sum(1)
+        t1 = dx.double() * slope
+        t2 = t1 * xhat
+        worst = [0.0, 0.0]
+        for j, t in enumerate((t1, t2)):
+            ref = t.sum((2, 3, 4)).view(n)
+            mag = t.abs().sum((2, 3, 4)).view(n)
+            rel = (got[:, j] - ref).abs() / mag
+            worst[j] = float(rel.max())
+            assert bool((rel <= 2.0 ** -19).all()), (what, "S%d" % (j + 1), rel)
+        print("maxpool fused records %s %s %s: %d per instance, worst |S1 - ref| / sum|.| %.2e, S2 %.2e (bar %.2e)" %
+              (shape, kernel, what, npr, worst[0], worst[1], 2.0 ** -19))
+
+
+def test_pool_as_last_writer_feeds_instancenorm_backward():
+    """The consumer of those records, at operator level with the engine's own plumbing: a ConvOp whose output gradient was first
+    written by an earlier consumer (a seeded P), then a PoolOp planned as its last writer (acc = 1); pool.backward() followed by
+    op.backward(), once with the records (sums_ready: e2e_in_lrelu_bwd adds them up and runs its apply pass only) and once without
+    (two passes).  Reference: fp64 autograd of <P, z> + <dy_pool, max_pool3d(z)>, z = lrelu(instance_norm(conv(x))), at
+    test_conv133_fwd_bwd's bars for both routes; between the routes everything but conv.bias (analytically zero: rounding noise on
+    both sides) within 5e-5 of its scale (the network-level bar); and the max |dy| word that scales the fp16 weight gradient must be
+    the maximum of the dy the call left behind, on both routes.  As in test_conv133_fwd_bwd no gradient enters elements on the
+    LeakyReLU kink (|u| < 2e-5: P zeroed there, dy_pool of any window holding one zeroed)."""
+    from e2enet_medical_amd.engine import ConvOp, PoolOp
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    B, cout, dims, kernel = 2, 5, (8, 16, 40), (2, 2, 2)
+    src_desc = [(4, True), (2, False)]
+    cin = sum(ch for ch, _ in src_desc)
+    srcs = [_make_act((B, ch) + dims, normed, 630 + i) for i, (ch, normed) in enumerate(src_desc)]
+    params = {"blk.conv.weight": seeded_input((cout, cin, 1, 3, 3), seed=633) * (1.0 / math.sqrt(cin * 9)),
+              "blk.conv.bias": seeded_input((cout,), seed=634) * 0.1,
+              "blk.instnorm.weight": 1 + 0.2 * seeded_input((cout,), seed=636),
+              "blk.instnorm.bias": 0.2 * seeded_input((cout,), seed=637)}
+    e = _eng_stub(params)
+    e.batch = B
+    op = ConvOp(e, "blk", srcs, cout, (1, 1, 1))
+    if op.dense_ws_bytes > 0:
+        e.fwd_ws = torch.empty(op.dense_ws_bytes // 4, dtype=torch.float32, device=e.device)
+    op.set_input_range(max(float(_act_value(a).abs().max()) for a in srcs))
+    op.forward()
+    pool = PoolOp(e, "down", op.out, kernel)
+    # ---- reference
+    leaves = [_act_value(a).double().requires_grad_(True) for a in srcs]
+    ref_p = {k: v.double().requires_grad_(True) for k, v in params.items()}
+    y = F.conv3d(oracle.depth_shift(torch.cat(leaves, 1)), ref_p["blk.conv.weight"], ref_p["blk.conv.bias"], padding=(0, 1, 1))
+    u = F.instance_norm(y, weight=ref_p["blk.instnorm.weight"], bias=ref_p["blk.instnorm.bias"], eps=1e-5)
+    z = F.leaky_relu(u, 0.01)
+    z.retain_grad()
+    kink = u.detach().abs() < 2e-5
+    assert float(kink.float().mean()) < 1e-3
+    P = _prefill(tuple(z.shape), 638)
+    P[kink] = 0.0
+    pooled = F.max_pool3d(z, kernel)
+    dyp = seeded_input(tuple(pooled.shape), seed=639)
+    dyp[F.max_pool3d(kink.float(), kernel) > 0] = 0.0
+    ((P.double() * z).sum() + (dyp.double() * pooled).sum()).backward()
+    torch.cuda.synchronize()
+    assert (op.out.data.cpu().double() - y.detach()).abs().max() < 2e-5, "conv output"
+    # ---- the plan: an earlier consumer has written op.out.grad, the pooling backward is its last writer
+    op.out.alloc_grad()
+    op.out._grad_written = True
+    pool.out.alloc_grad()
+    pool.plan_backward()
+    assert pool.acc == 1 and op.out.last_writer is pool
+    own_np = int(L.maxpool_bwd_num_records(*op.out_dims, *pool.kernel))      # (as Engine.prepare_backward lays the records out)
+    assert own_np == 2
+    own_sums = torch.zeros(B * cout * own_np * 2, dtype=torch.float64, device=e.device)
+    for s in srcs:
+        s._grad_written = False
+    op.plan_backward()
+
+    def route(with_records):
+        op.own_sums, op.own_np = (own_sums, own_np) if with_records else (None, 0)
+        own_sums.fill_(float("nan"))
+        op.out.grad.copy_(P)
+        pool.out.grad.copy_(dyp)
+        for s in srcs:
+            s.grad.fill_(float("nan"))                      # first writer must overwrite
+        for g in e.grads.values():
+            g.fill_(float("nan"))
+        pool.backward()
+        assert op.out.sums_ready == with_records
+        op.backward()
+        torch.cuda.synchronize()
+        assert not op.out.sums_ready
+        assert float(op.dy_absmax.view(torch.float32)) == float(op.out.grad.abs().max()), "the max |dy| word"
+        got = {k: v.cpu().double() for k, v in e.grads.items()}
+        for i, s in enumerate(srcs):
+            got["source %d" % i] = s.grad.cpu().double()
+        return got
+    ref = {k: v.grad for k, v in ref_p.items()}
+    for i, leaf in enumerate(leaves):
+        ref["source %d" % i] = leaf.grad
+    bars = {k: 2e-4 * max(1.0, float(v.abs().max())) for k, v in ref.items()}
+    bars["blk.conv.bias"] = 1e-3 * max(1.0, float(z.grad.abs().sum()) * 1e-3)
+    res = {}
+    for name, with_records in (("records", True), ("two passes", False)):
+        res[name] = got = route(with_records)
+        for k, v in ref.items():
+            assert torch.isfinite(got[k]).all(), (name, k)
+            err = float((got[k] - v).abs().max())
+            print("pool as last writer, %s: %s max-abs %.3e (bar %.3e)" % (name, k, err, bars[k]))
+            assert err < bars[k], (name, k)
+    for k, v in res["two passes"].items():
+        if k.endswith(".conv.bias"):
+            continue
+        err = float((res["records"][k] - v).abs().max()) / max(float(v.abs().max()), 1e-6)
+        print("pool as last writer, records vs two passes: %s %.3e of its scale" % (k, err))
+        assert err <= 5e-5, k
