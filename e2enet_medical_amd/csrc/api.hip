@@ -1,5 +1,6 @@
 // Error reporting and ABI version of libe2e_hip.so.
 #include "e2e_common.h"
+#include "e2e_concat.h"
 #include <cstring>
 
 namespace e2e {
@@ -21,7 +22,13 @@ void note_kernel(const char* fmt, ...) {
 
 extern "C" const char* e2e_last_error(void) { return e2e::g_err; }
 extern "C" const char* e2e_last_kernel(void) { return e2e::g_kernel; }
-extern "C" int e2e_abi_version(void) { return 28; }
+extern "C" int e2e_abi_version(void) { return 29; }
+
+extern "C" int e2e_diag_concat_slice(int d, int dshift, int D, int accumulate, int* dd) {
+  const e2e::ConcatSlice sl = e2e::concat_store_slice(d, dshift, D, accumulate);
+  if (dd != nullptr) *dd = sl.dd;
+  return sl.action;
+}
 
 extern "C" int e2e_diag_kernel_clock(int family, double* mhz, double* busy_ms, int reset) {
   E2E_REQUIRE(mhz != nullptr && (family == 0 || family == 1), "diag_kernel_clock: family 0 (conv133_mm) or 1 (conv133_wgrad v5)");

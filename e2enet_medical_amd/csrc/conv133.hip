@@ -20,6 +20,7 @@
 //     epilogue (dgrad): un-shift on store into the per-channel destination (scatter back through the concat).
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 #include <cstdio>
 #include <type_traits>
@@ -64,13 +65,6 @@ struct ConvParams {
   int ksplit;                          // fwd: the input-plane chunks of a tile are split over ksplit workgroups (deep levels)
   float* kpart;                        // ... which store raw partial sums here: [ksplit][B][Q][Do][Ho][Wo]
   int dbg;                             // diagnostics (E2E_CONV_DBG): 1 = no staging, 2 = no FMA phase, 4 = no barriers
-};
-
-// wave-uniform description of one staged input plane, kept in LDS (double buffered per chunk)
-struct PlaneDesc {
-  gfloat_p base;      // plane origin for this (n, depth); always dereferenceable
-  float a, b, slope;  // normalise-on-load coefficients
-  int valid;
 };
 
 template <int MODE, int SH, int SW, int DH, int DW, int TH, int TW, int LY, int LX, int OPW, int NW, int CK, int STG>
@@ -224,15 +218,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
     if (MODE == 0) {
       ds.base = (gfloat_p)p.chans[0].ptr;
       const e2e_in_chan_t ch = p.chans[pl];
-      const int din = d * p.sd - ch.dshift;
-      if ((unsigned)din < (unsigned)p.Di) {
+      const ConcatDepth sl = concat_depth(d, p.sd, ch.dshift, p.Di);
+      if (sl.valid) {
+        const ConcatChan cc = concat_chan(ch, n);
         ds.valid = 1;
-        ds.base = (gfloat_p)(ch.ptr + (long long)n * ch.nstride + (long long)din * in_plane);
-        if (ch.scale != nullptr) {
-          ds.a = ch.scale[(long long)n * ch.ab_nstride];
-          ds.b = ch.shift[(long long)n * ch.ab_nstride];
-          ds.slope = ch.slope;
-        }
+        ds.base = (gfloat_p)(cc.base + (long long)sl.din * in_plane);
+        ds.a = cc.a; ds.b = cc.b; ds.slope = cc.slope;
       }
     } else {
       ds.valid = 1;
@@ -700,12 +691,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
     float psum[OPW];                                      // fwd: per-lane sums of the stored values
 #pragma unroll
     for (int a = 0; a < OPW; ++a) psum[a] = 0.f;
-    float4* vdst[MODE != 0 ? OPW : 1][C::PH];             // dgrad, float4 rows: destination (null = nothing to store) and mode
+    float4* vdst[MODE != 0 ? OPW : 1][C::PH];             // dgrad, float4 rows: destination (null = nothing to store) and ConcatAction
     int vmode[MODE != 0 ? OPW : 1];
     if (MODE != 0) {
 #pragma unroll
       for (int a = 0; a < OPW; ++a) {
-        vmode[a] = 0;
+        vmode[a] = CONCAT_STORE;
 #pragma unroll
         for (int i = 0; i < C::PH; ++i) vdst[a][i] = nullptr;
       }
@@ -742,22 +733,13 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
         }
         psum[a] = s;
       } else {
-        // dgrad: gradient of virtual-concat channel q at (shifted) depth d goes to depth d - s(q) of its source
+        // dgrad: scatter back through the concat (concat_store_slice)
         const e2e_out_chan_t oc = ocs[a];
         if (oc.ptr == nullptr) continue;
-        int dd = d - oc.dshift;
-        bool zero_fill = false;
-        if (dd < 0) {              // s > 0: slices [max(D-s,0), D) receive nothing -> this workgroup zero-fills one
-          const int lo = p.Do - oc.dshift > 0 ? p.Do - oc.dshift : 0;
-          dd = lo + d;
-          zero_fill = true;
-        } else if (dd >= p.Do) {   // s < 0: slices [0, min(-s, D)) receive nothing
-          const int lo = p.Do + oc.dshift > 0 ? p.Do + oc.dshift : 0;
-          dd = d - lo;
-          zero_fill = true;
-        }
-        if (zero_fill && oc.accumulate) continue;
-        float* xp = oc.ptr + (long long)n * oc.nstride + (long long)dd * out_plane;
+        const ConcatSlice sl = concat_store_slice(d, oc.dshift, p.Do, oc.accumulate);
+        if (sl.action == CONCAT_SKIP) continue;
+        const bool zero_fill = sl.action == CONCAT_ZERO_FILL;
+        float* xp = oc.ptr + (long long)n * oc.nstride + (long long)sl.dd * out_plane;
         const bool vec_store = (C::PW == 4) && (p.Wo % 4 == 0);
         const bool vec2_store = (C::PW == 2) && (p.Wo % 2 == 0);
 #pragma unroll
@@ -776,7 +758,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
           if (vec_store) {      // handled below: all old values are requested first, then added and stored
             if (oh < p.Ho && ow0 < p.Wo) {
               vdst[a][i] = reinterpret_cast<float4*>(xp + (long long)oh * p.Wo + ow0);
-              vmode[a] = zero_fill ? 2 : (oc.accumulate ? 1 : 0);
+              vmode[a] = sl.action;
             }
             continue;
           }
@@ -800,7 +782,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
 #pragma unroll
         for (int i = 0; i < C::PH; ++i) {
           oldv[a][i] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (vdst[a][i] != nullptr && vmode[a] == 1) oldv[a][i] = *vdst[a][i];
+          if (vdst[a][i] != nullptr && vmode[a] == CONCAT_ADD) oldv[a][i] = *vdst[a][i];
         }
 #pragma unroll
       for (int a = 0; a < OPW; ++a)
@@ -808,7 +790,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv133_kernel(ConvParams p) {
         for (int i = 0; i < C::PH; ++i) {
           if (vdst[a][i] == nullptr) continue;
           float4 val = make_float4(acc[a][i][0], acc[a][i][1 % C::PW], acc[a][i][2 % C::PW], acc[a][i][3 % C::PW]);
-          if (vmode[a] == 2) val = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (vmode[a] == CONCAT_ZERO_FILL) val = make_float4(0.f, 0.f, 0.f, 0.f);
           val.x += oldv[a][i].x; val.y += oldv[a][i].y; val.z += oldv[a][i].z; val.w += oldv[a][i].w;
           *vdst[a][i] = val;
         }
@@ -937,8 +919,8 @@ __global__ __launch_bounds__(64) void conv133_ksum_kernel(const float* __restric
   }
 }
 
-// ---- split-K tail of the data gradient: sum of the parts (fixed order), then the scatter epilogue of conv133_kernel
-// (un-shift on store, zero-fill of the slices that receive nothing, accumulate flag).  One wave per (n, q, tile).
+// ---- split-K tail of the data gradient: sum of the parts (fixed order), then the scatter back through the concat
+// (concat_store_slice).  One wave per (n, q, tile).
 __global__ __launch_bounds__(64) void conv133_dsum_kernel(const float* __restrict__ kpart, const e2e_out_chan_t* __restrict__ outs,
                                                           int ksplit, int B, int Q, int Do, int Ho, int Wo, int TH, int TW,
                                                           int tiles_x, int tiles_y) {
@@ -953,24 +935,15 @@ __global__ __launch_bounds__(64) void conv133_dsum_kernel(const float* __restric
   const int ty = u % tiles_y, d = u / tiles_y;
   const e2e_out_chan_t oc = outs[q];
   if (oc.ptr == nullptr) return;
-  int dd = d - oc.dshift;
-  bool zero_fill = false;
-  if (dd < 0) {
-    const int lo = Do - oc.dshift > 0 ? Do - oc.dshift : 0;
-    dd = lo + d;
-    zero_fill = true;
-  } else if (dd >= Do) {
-    const int lo = Do + oc.dshift > 0 ? Do + oc.dshift : 0;
-    dd = d - lo;
-    zero_fill = true;
-  }
-  if (zero_fill && oc.accumulate) return;
+  const ConcatSlice sl = concat_store_slice(d, oc.dshift, Do, oc.accumulate);
+  if (sl.action == CONCAT_SKIP) return;
+  const bool zero_fill = sl.action == CONCAT_ZERO_FILL;
   const int h0 = ty * TH, w0 = tx * TW;
   const int vr = Ho - h0 < TH ? Ho - h0 : TH, vc = Wo - w0 < TW ? Wo - w0 : TW;
   const long long plane = (long long)Ho * Wo;
   const long long src = (((long long)n * Q + q) * Do + d) * plane;
   const long long kstride = (long long)B * Q * Do * plane;
-  float* xp = oc.ptr + (long long)n * oc.nstride + (long long)dd * plane;
+  float* xp = oc.ptr + (long long)n * oc.nstride + (long long)sl.dd * plane;
   const int npx = vr * vc;
   for (int i = threadIdx.x; i < npx; i += 64) {
     const int r = i / vc, c = i - r * vc;

@@ -20,7 +20,7 @@
 // Wave w owns rows 2w, 2w+1 of the half (2 x 16 accumulator registers, 108 matrix instructions per chunk).  Two workgroups per
 // CU (2 x 77 KB LDS): one stages while the other multiplies.  Epilogue through LDS (transposed to pixel-fastest rows):
 // forward: bias, coalesced stores, (count, mean, M2) per wave and half, combined in fp64 to the tile's partial record;
-// data gradient: the scatter epilogue of conv133_kernel (un-shift on store, zero-fill, accumulate).
+// data gradient: the scatter back through the concat (e2e_concat.h).
 //
 // Staging loads are aligned float4s over columns w0 - 4 .. w0 + 35 (one lane = one (row, 4-column group) x 8 channels); the plane
 // pointers and normalise-on-load coefficients come from a per-workgroup LDS table built once (round 3: read through the
@@ -31,6 +31,7 @@
 // dispatched for); everything else stays on conv133_kernel.
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 
 #ifndef DENSE_DIAG
@@ -230,19 +231,13 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
   prefetch_w(0);
   if (MODE == 0) {
     for (int ch = tid; ch < p.nchunks * 16; ch += 256) {
-      const e2e_in_chan_t cd = p.chans[ch < p.P ? ch : 0];
-      const int din = d - cd.dshift;
-      const bool valid = ch < p.P && (unsigned)din < (unsigned)p.D;
-      float a = 1.f, b = 0.f, sl = 1.f;
-      if (cd.scale != nullptr) {
-        a = cd.scale[(long long)n * cd.ab_nstride];
-        b = cd.shift[(long long)n * cd.ab_nstride];
-        sl = cd.slope;
-      }
+      const ConcatChan cc = concat_chan(p.chans[ch < p.P ? ch : 0], n);
+      const ConcatDepth sl = concat_depth(d, 1, cc.dshift, p.D);
+      const bool valid = ch < p.P && sl.valid;
       unsigned char* e = ctab + ch * CTAB_ENT;
-      *reinterpret_cast<unsigned long long*>(e) = (unsigned long long)(cd.ptr + (long long)n * cd.nstride + (long long)(valid ? din : 0) * plane);
-      *reinterpret_cast<float2*>(e + 8) = float2{a, b};
-      *reinterpret_cast<float*>(e + 16) = sl;
+      *reinterpret_cast<unsigned long long*>(e) = (unsigned long long)(cc.base + (long long)(valid ? sl.din : 0) * plane);
+      *reinterpret_cast<float2*>(e + 8) = float2{cc.a, cc.b};
+      *reinterpret_cast<float*>(e + 16) = cc.slope;
       *reinterpret_cast<unsigned*>(e + 20) = valid ? 1u : 0u;
     }
     __syncthreads();
@@ -348,25 +343,14 @@ __global__ __launch_bounds__(256, 2) void conv133_dense_kernel(DenseParams p) {
       if (MODE == 0) {
         *reinterpret_cast<f32x4_t*>(p.y + (((long long)n * p.Q + q) * p.D + d) * plane + po) = v;
       } else {
-        // data gradient: the gradient of virtual-concat channel q at (shifted) depth d goes to depth d - s(q) of its source;
-        // slices that receive nothing are zero-filled by the workgroups of the out-of-range depths (conv133_kernel's rule)
+        // data gradient: scatter back through the concat (concat_store_slice)
         const e2e_out_chan_t oc = p.outs[q];
         if (oc.ptr == nullptr) continue;
-        int dd = d - oc.dshift;
-        bool zero_fill = false;
-        if (dd < 0) {
-          const int lo = p.D - oc.dshift > 0 ? p.D - oc.dshift : 0;
-          dd = lo + d;
-          zero_fill = true;
-        } else if (dd >= p.D) {
-          const int lo = p.D + oc.dshift > 0 ? p.D + oc.dshift : 0;
-          dd = d - lo;
-          zero_fill = true;
-        }
-        if (zero_fill && oc.accumulate) continue;
-        f32x4_t* dst = reinterpret_cast<f32x4_t*>(oc.ptr + (long long)n * oc.nstride + (long long)dd * plane + po);
-        f32x4_t o = zero_fill ? f32x4_t{0.f, 0.f, 0.f, 0.f} : v;
-        if (!zero_fill && oc.accumulate) { const f32x4_t old = *dst; o += old; }
+        const ConcatSlice sl = concat_store_slice(d, oc.dshift, p.D, oc.accumulate);
+        if (sl.action == CONCAT_SKIP) continue;
+        f32x4_t* dst = reinterpret_cast<f32x4_t*>(oc.ptr + (long long)n * oc.nstride + (long long)sl.dd * plane + po);
+        f32x4_t o = sl.action == CONCAT_ZERO_FILL ? f32x4_t{0.f, 0.f, 0.f, 0.f} : v;
+        if (sl.action == CONCAT_ADD) { const f32x4_t old = *dst; o += old; }
         *dst = o;
       }
     }

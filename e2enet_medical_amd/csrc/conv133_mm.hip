@@ -38,6 +38,7 @@
 // Shapes: stride (1,1,1), W % 32 == 0, H % 16 == 0, more than 16 channels on the reduction side, at most CT_MAX.
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -261,16 +262,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int np16 = p.nchunks * 16, nrec = p.B * np16;
     for (int i = tid; i < nrec; i += 512) {
       const int ch = i % np16, nb = i / np16;
-      const e2e_in_chan_t cd = p.chans[ch < p.P ? ch : 0];
+      const bool have = ch < p.P;                              // (absent: channel 0's planes, read and multiplied by 0)
+      const ConcatChan cc = concat_chan(p.chans[have ? ch : 0], nb);
       ChanRec r;
-      r.ptr = (unsigned long long)(cd.ptr + (long long)nb * cd.nstride);
-      r.a = ch < p.P ? 1.f : 0.f; r.b = 0.f; r.slope = 1.f;
-      r.dshift = ch < p.P ? cd.dshift : 0;
-      if (ch < p.P && cd.scale != nullptr) {
-        r.a = cd.scale[(long long)nb * cd.ab_nstride];
-        r.b = cd.shift[(long long)nb * cd.ab_nstride];
-        r.slope = cd.slope;
-      }
+      r.ptr = (unsigned long long)cc.base;
+      r.a = have ? cc.a : 0.f; r.b = have ? cc.b : 0.f; r.slope = have ? cc.slope : 1.f;
+      r.dshift = have ? cc.dshift : 0;
       lrec[i] = r;
     }
     for (int i = tid; i < p.qblocks * 32; i += 512) lbias[i] = (p.bias != nullptr && i < p.Q) ? p.bias[i] : 0.f;
@@ -289,12 +286,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       float sv = 1.f;
       if (MODE == 0) {
         const ChanRec r = lrec[it.n * np16 + ch];
-        const int din = it.d - r.dshift;
-        const bool valid = (unsigned)din < (unsigned)p.D;
-        e.a = valid ? r.a * xsc : 0.f;                         // (LeakyReLU commutes with the positive pre-scale)
-        e.b = valid ? r.b * xsc : 0.f;
+        const ConcatDepth sl = concat_depth(it.d, 1, r.dshift, p.D);
+        e.a = sl.valid ? r.a * xsc : 0.f;                      // (LeakyReLU commutes with the positive pre-scale)
+        e.b = sl.valid ? r.b * xsc : 0.f;
         sv = r.slope;
-        e.ptr = r.ptr + (unsigned long long)(valid ? din : 0) * (unsigned long long)plane * 4ull;
+        e.ptr = r.ptr + (unsigned long long)(sl.valid ? sl.din : 0) * (unsigned long long)plane * 4ull;
       } else {
         const bool valid = ch < p.P;
         e.a = valid ? xsc : 0.f;
@@ -306,9 +302,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   };
 
-  // data gradient: where the 32 out channels of an item go -- the gradient of virtual-concat channel q at (shifted) depth d goes to
-  // depth d - s(q) of its source; slices that receive nothing are zero-filled by the workgroups of the out-of-range depths
-  // (conv133_kernel's rule).  Resolved once per item into LDS by the staging waves (LDS-to-LDS, like the channel table).
+  // data gradient: where the 32 out channels of an item go (concat_store_slice), resolved once per item into LDS by the staging
+  // waves (LDS-to-LDS, like the channel table)
   auto build_odesc = [&](const Item& it, int slot, int t) __attribute__((always_inline)) {
     if (MODE != 1 || t < 0 || t >= 32) return;
     const int q = it.qb * 32 + t;
@@ -317,21 +312,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (q < p.Q) {
       const e2e_out_chan_t oc = lout[q];
       if (oc.ptr != nullptr) {
-        int dd = it.d - oc.dshift;
-        bool zero_fill = false;
-        if (dd < 0) {
-          const int lo = p.D - oc.dshift > 0 ? p.D - oc.dshift : 0;
-          dd = lo + it.d;
-          zero_fill = true;
-        } else if (dd >= p.D) {
-          const int lo = p.D + oc.dshift > 0 ? p.D + oc.dshift : 0;
-          dd = it.d - lo;
-          zero_fill = true;
-        }
-        if (!(zero_fill && oc.accumulate)) {
-          od.dst = oc.ptr + (long long)it.n * oc.nstride + (long long)dd * plane + (long long)it.h0 * p.W + it.w0;
-          od.usc = zero_fill ? 0.f : unsc;
-          od.flags = 1 | ((!zero_fill && oc.accumulate) ? 2 : 0);
+        const ConcatSlice sl = concat_store_slice(it.d, oc.dshift, p.D, oc.accumulate);
+        if (sl.action != CONCAT_SKIP) {
+          od.dst = oc.ptr + (long long)it.n * oc.nstride + (long long)sl.dd * plane + (long long)it.h0 * p.W + it.w0;
+          od.usc = sl.action == CONCAT_ZERO_FILL ? 0.f : unsc;
+          od.flags = 1 | (sl.action == CONCAT_ADD ? 2 : 0);
         }
       }
     }

@@ -33,6 +33,7 @@
 // with normalise-on-load, quad-nibble walk unrolled over the eight plane slots, fp64 statistics records) is conv133_kernel's.
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -80,12 +81,6 @@ struct SparseParams {
   int nchunks, ppad, groups, flush_every, kmax, uw;      // uw: 16-byte units of a chunk's weight block per wave
   int dbg;                                               // diagnostic build: 1 no walk, 2 no plane loads, 4 no stores
   int tiles_x, tiles_y, tiles_per_n, total, padded_total;
-};
-
-struct PlaneDesc {
-  gfloat_p base;
-  float a, b, slope;
-  int valid;
 };
 
 typedef const volatile f32x2_t __attribute__((address_space(3)))* lds_v2_p;      // (volatile: not merged into ds_read2_b64)
@@ -212,11 +207,11 @@ __global__ __launch_bounds__(NW * 64, 4) void conv133_sparse_kernel(SparseParams
     bool ok = false;
     if (MODE == 0) {
       const e2e_in_chan_t ch = load_uniform(p.chans + (long long)g * p.ppad + wave);
-      const int din = d - ch.dshift;
-      if (ch.ptr != nullptr && (unsigned)din < (unsigned)p.D) {
+      const ConcatDepth sl = concat_depth(d, 1, ch.dshift, p.D);
+      if (ch.ptr != nullptr && sl.valid) {
         ok = true;
-        base = (gfloat_p)(ch.ptr + (long long)n * ch.nstride + (long long)din * plane);
-        if (ch.scale != nullptr) {
+        base = (gfloat_p)(ch.ptr + (long long)n * ch.nstride + (long long)sl.din * plane);
+        if (ch.scale != nullptr) {                            // (concat_chan, with the coefficients on the scalar path)
           pd_a = load_uniform(ch.scale + (long long)n * ch.ab_nstride);
           pd_b = load_uniform(ch.shift + (long long)n * ch.ab_nstride);
           pd_slope = ch.slope;
@@ -246,15 +241,12 @@ __global__ __launch_bounds__(NW * 64, 4) void conv133_sparse_kernel(SparseParams
     ds.base = (gfloat_p)p.wpk;                                    // always dereferenceable
     if (MODE == 0) {
       const e2e_in_chan_t ch = p.chans[(long long)g * p.ppad + pl];
-      const int din = d - ch.dshift;
-      if (ch.ptr != nullptr && (unsigned)din < (unsigned)p.D) {
+      const ConcatDepth sl = concat_depth(d, 1, ch.dshift, p.D);
+      if (ch.ptr != nullptr && sl.valid) {
+        const ConcatChan cc = concat_chan(ch, n);
         ds.valid = 1;
-        ds.base = (gfloat_p)(ch.ptr + (long long)n * ch.nstride + (long long)din * plane);
-        if (ch.scale != nullptr) {
-          ds.a = ch.scale[(long long)n * ch.ab_nstride];
-          ds.b = ch.shift[(long long)n * ch.ab_nstride];
-          ds.slope = ch.slope;
-        }
+        ds.base = (gfloat_p)(cc.base + (long long)sl.din * plane);
+        ds.a = cc.a; ds.b = cc.b; ds.slope = cc.slope;
       }
     } else {
       const int c = p.pslot[(long long)g * p.ppad + pl];
@@ -296,30 +288,19 @@ __global__ __launch_bounds__(NW * 64, 4) void conv133_sparse_kernel(SparseParams
     for (int i = 0; i < PH; ++i)
 #pragma unroll
       for (int j = 0; j < PW / 2; ++j) { accp[a][i][j] = f32x2_t{0.f, 0.f}; acc2p[a][i][j] = f32x2_t{0.f, 0.f}; }
-  // data gradient: gradient of virtual-concat channel q at (shifted) depth d goes to depth d - s(q) of its source; the slices that
-  // receive nothing are zero-filled by the workgroups of the slices that fall outside (conv133_kernel's rule).  Wave-uniform.
-  // mode: 0 store, 1 accumulate (the old values are the initial outer accumulators), 2 zero fill, 3 nothing to do, 4 nothing to
-  // store but the slice holds final values of earlier writers (an accumulating launch whose depth falls outside: dd = that slice)
+  // data gradient: scatter back through the concat (concat_store_slice).  Wave-uniform.
+  // mode: 0 store, 1 accumulate (the old values are the initial outer accumulators), 2 zero fill, 3 no destination, 4 nothing to
+  // store but slice dd holds final values of earlier writers (CONCAT_SKIP)
   int dd_out = 0;
   auto destination = [&](const e2e_out_chan_t& oc, int& mode) -> float* {
     mode = 3;
     dd_out = 0;
     if (oc.ptr == nullptr) return nullptr;
-    int dd = d - oc.dshift;
-    bool zero_fill = false;
-    if (dd < 0) {
-      const int lo = p.D - oc.dshift > 0 ? p.D - oc.dshift : 0;
-      dd = lo + d;
-      zero_fill = true;
-    } else if (dd >= p.D) {
-      const int lo = p.D + oc.dshift > 0 ? p.D + oc.dshift : 0;
-      dd = d - lo;
-      zero_fill = true;
-    }
-    dd_out = dd;
-    if (zero_fill && oc.accumulate) { mode = 4; return nullptr; }
-    mode = zero_fill ? 2 : (oc.accumulate ? 1 : 0);
-    return oc.ptr + (long long)n * oc.nstride + (long long)dd * plane;
+    const ConcatSlice sl = concat_store_slice(d, oc.dshift, p.D, oc.accumulate);
+    dd_out = sl.dd;
+    if (sl.action == CONCAT_SKIP) { mode = 4; return nullptr; }
+    mode = sl.action;
+    return oc.ptr + (long long)n * oc.nstride + (long long)sl.dd * plane;
   };
   if (MODE != 0) {
 #pragma unroll

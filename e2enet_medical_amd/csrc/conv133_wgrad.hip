@@ -15,6 +15,7 @@
 // distinct banks.  Per-chunk partial sums go to a slab, reduced in fixed order by a second kernel (deterministic).
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 
 namespace {
@@ -84,26 +85,19 @@ __global__ __launch_bounds__(256) void conv133_wgrad_kernel(WgParams p) {
     for (int cl = wave; cl < 32; cl += 4) {          // one wave per channel -> channel descriptor is wave-uniform
       const int c = cb * 32 + cl;
       const bool cv = c < p.Cin;
-      e2e_in_chan_t chd = p.chans[cv ? c : 0];
-      float a = 1.f, b = 0.f, sl = 1.f;
-      if (cv && chd.scale != nullptr) {
-        a = chd.scale[(long long)n * chd.ab_nstride];
-        b = chd.shift[(long long)n * chd.ab_nstride];
-        sl = chd.slope;
-      }
-      gfloat_p base = (gfloat_p)(chd.ptr + (long long)n * chd.nstride);
+      const ConcatChan chd = concat_chan(p.chans[cv ? c : 0], n);   // (!cv: channel 0, every element masked below)
+      gfloat_p base = (gfloat_p)chd.base;
       for (int e = lane; e < ND * C::IH * C::IW; e += 64) {
         const int nd = e / (C::IH * C::IW);
         const int rem = e - nd * (C::IH * C::IW);
         const int r = rem / C::IW, cc = rem - r * C::IW;
         const int hi = hbase + r, wi = wbase + cc;
         const int dq = d0 + nd;
-        const int din = dq * p.sd - chd.dshift;
-        const bool ok = cv && dq < p.Do && (unsigned)din < (unsigned)p.Di && (unsigned)hi < (unsigned)p.Hi &&
-                        (unsigned)wi < (unsigned)p.Wi;
-        const long long off = ok ? (long long)din * in_plane + (long long)hi * p.Wi + wi : 0;
+        const ConcatDepth sl = concat_depth(dq, p.sd, chd.dshift, p.Di);
+        const bool ok = cv && dq < p.Do && sl.valid && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi;
+        const long long off = ok ? (long long)sl.din * in_plane + (long long)hi * p.Wi + wi : 0;
         float v = base[off];
-        v = e2e::in_act(v, a, b, sl);
+        v = e2e::in_act(v, chd.a, chd.b, chd.slope);
         xs[cl * C::CS + nd * (C::IH * C::PITCH) + r * C::PITCH + cc] = ok ? v : 0.f;
       }
     }
@@ -236,15 +230,10 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
     for (int k = 0; k < C::XCW; ++k) {
       const int c = cbase + wave * C::XCW + k;
       xval[k] = c < p.Cin;
-      const e2e_in_chan_t chd = p.chans[xval[k] ? c : 0];
+      const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
       xdsh[k] = chd.dshift;
-      xbase[k] = (gfloat_p)(chd.ptr + (long long)n * chd.nstride);
-      xa[k] = 1.f; xb[k] = 0.f; xsl[k] = 1.f;
-      if (xval[k] && chd.scale != nullptr) {
-        xa[k] = chd.scale[(long long)n * chd.ab_nstride];
-        xb[k] = chd.shift[(long long)n * chd.ab_nstride];
-        xsl[k] = chd.slope;
-      }
+      xbase[k] = (gfloat_p)chd.base;
+      xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
     }
   };
 
@@ -275,9 +264,9 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
       const long long lane_off = (long long)hi * p.Wi + gc;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const int din = dq * p.sd - xdsh[k];
-        const bool ok = lane_ok && xval[k] && (unsigned)din < (unsigned)p.Di && !(p.dbg & 4);
-        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)din * in_plane + lane_off : 0));
+        const ConcatDepth sl = concat_depth(dq, p.sd, xdsh[k], p.Di);
+        const bool ok = lane_ok && xval[k] && sl.valid && !(p.dbg & 4);
+        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
       }
     }
     const int dq = d0 + y_nd, ho = h0 + y_r, wo = w0 + y_col;
@@ -299,8 +288,8 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
       const bool lane_ok = dq < p.Do && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const int din = dq * p.sd - xdsh[k];
-        const bool ok = lane_ok && xval[k] && (unsigned)din < (unsigned)p.Di;
+        const ConcatDepth sl = concat_depth(dq, p.sd, xdsh[k], p.Di);
+        const bool ok = lane_ok && xval[k] && sl.valid;
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -497,15 +486,10 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
   for (int k = 0; k < C::XCW; ++k) {
     const int c = cbase + wave * C::XCW + k;
     xval[k] = c < p.Cin;
-    const e2e_in_chan_t chd = p.chans[xval[k] ? c : 0];
+    const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
     xdsh[k] = chd.dshift;
-    xbase[k] = (gfloat_p)(chd.ptr + (long long)n * chd.nstride);
-    xa[k] = 1.f; xb[k] = 0.f; xsl[k] = 1.f;
-    if (xval[k] && chd.scale != nullptr) {
-      xa[k] = chd.scale[(long long)n * chd.ab_nstride];
-      xb[k] = chd.shift[(long long)n * chd.ab_nstride];
-      xsl[k] = chd.slope;
-    }
+    xbase[k] = (gfloat_p)chd.base;
+    xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
   }
 
   // ---- per-lane geometry ----
@@ -527,9 +511,9 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
       const int hi = h0 - 1 + g_r, gc = w0 - 4 + 4 * g_q;
       const bool lane_ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
       const long long lane_off = (long long)hi * p.Wi + gc;
-      const int din = d0 * p.sd - xdsh[k];
-      const bool ok = lane_ok && xval[k] && (unsigned)din < (unsigned)p.Di;
-      vx[k] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)din * in_plane + lane_off : 0));
+      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
+      const bool ok = lane_ok && xval[k] && sl.valid;
+      vx[k] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
     } else {
       const int it = s - C::XCW;
       const int ho = h0 + y_r, wo = w0 + y_col;
@@ -551,8 +535,8 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
       //  that the in-loop staging below stays straight-line code and its loads get exact vmcnt distances)
       const int k = s;
       const int hi = h0 - 1 + g_r, gc = w0 - 4 + 4 * g_q;
-      const int din = d0 * p.sd - xdsh[k];
-      const bool ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && xval[k] && (unsigned)din < (unsigned)p.Di;
+      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
+      const bool ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && xval[k] && sl.valid;
       float v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -696,14 +680,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
 
   // wave w stages input channel w (if it exists): descriptor in scalar registers
   const bool xval = wave < p.Cin;
-  const e2e_in_chan_t chd = p.chans[xval ? wave : 0];
-  const gfloat_p xbase = (gfloat_p)(chd.ptr + (long long)n * chd.nstride);
-  float xa = 1.f, xb = 0.f, xsl = 1.f;
-  if (xval && chd.scale != nullptr) {
-    xa = chd.scale[(long long)n * chd.ab_nstride];
-    xb = chd.shift[(long long)n * chd.ab_nstride];
-    xsl = chd.slope;
-  }
+  const ConcatChan chd = concat_chan(p.chans[xval ? wave : 0], n);   // (!xval: channel 0, masked where it is used)
+  const gfloat_p xbase = (gfloat_p)chd.base;
+  const float xa = chd.a, xb = chd.b, xsl = chd.slope;
   const int xdsh = chd.dshift;
 
   // dy: 32 channels x 64 float4 groups = 8 per thread: thread -> (channel tid / 64 + 4 it, group lane)
@@ -717,9 +696,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
       if (g >= C::GPC) g = C::GPC - 1;
       const int r = g / C::NQ, q = g - r * C::NQ;
       const int hi = h0 - 1 + r, gc = w0 - 4 + 4 * q;
-      const int din = d0 * p.sd - xdsh;
-      const bool ok = xval && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && (unsigned)din < (unsigned)p.Di;
-      vx[it] = *reinterpret_cast<gf4_p>(xbase + (ok ? (long long)din * in_plane + (long long)hi * p.Wi + gc : 0));
+      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh, p.Di);
+      const bool ok = xval && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && sl.valid;
+      vx[it] = *reinterpret_cast<gf4_p>(xbase + (ok ? (long long)sl.din * in_plane + (long long)hi * p.Wi + gc : 0));
     }
     const int ho = h0 + y_r, wo = w0 + y_col;
     const bool yok = ho < p.Ho && wo + 3 < p.Wo;
@@ -738,8 +717,8 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
       if (g >= C::GPC) continue;
       const int r = g / C::NQ, q = g - r * C::NQ;
       const int hi = h0 - 1 + r, gc = w0 - 4 + 4 * q;
-      const int din = d0 * p.sd - xdsh;
-      const bool ok = xval && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && (unsigned)din < (unsigned)p.Di;
+      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh, p.Di);
+      const bool ok = xval && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && sl.valid;
       float v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -886,15 +865,10 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
     for (int k = 0; k < C::XCW; ++k) {
       const int c = cbase + wave * C::XCW + k;
       xval[k] = c < p.Cin;
-      const e2e_in_chan_t chd = p.chans[xval[k] ? c : 0];
+      const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
       xdsh[k] = chd.dshift;
-      xbase[k] = (gfloat_p)(chd.ptr + (long long)n * chd.nstride);
-      xa[k] = 1.f; xb[k] = 0.f; xsl[k] = 1.f;
-      if (xval[k] && chd.scale != nullptr) {
-        xa[k] = chd.scale[(long long)n * chd.ab_nstride];
-        xb[k] = chd.shift[(long long)n * chd.ab_nstride];
-        xsl[k] = chd.slope;
-      }
+      xbase[k] = (gfloat_p)chd.base;
+      xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
     }
   };
 
@@ -920,9 +894,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
       const long long lane_off = (long long)hi * p.Wi + gc;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const int din = d0 * p.sd - xdsh[k];
-        const bool ok = lane_ok && xval[k] && (unsigned)din < (unsigned)p.Di;
-        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)din * in_plane + lane_off : 0));
+        const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
+        const bool ok = lane_ok && xval[k] && sl.valid;
+        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
       }
     }
     const int ho = h0 + y_r, wo = w0 + y_col;
@@ -942,8 +916,8 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
       const bool lane_ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const int din = d0 * p.sd - xdsh[k];
-        const bool ok = lane_ok && xval[k] && (unsigned)din < (unsigned)p.Di;
+        const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
+        const bool ok = lane_ok && xval[k] && sl.valid;
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

@@ -28,6 +28,7 @@
 // 0.83 ms on 64 -> 32 @128^3 x 2) and removed in round 5; what is left is v5 in two operand formats (NPC below).
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_concat.h"
 #include <cstdlib>
 
 // raw buffer loads (the clang builtin __builtin_amdgcn_raw_buffer_load_b128 of this toolchain lowers to a splatted dword load)
@@ -158,19 +159,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int x_r = rem >> XQS, x_q = rem & ((1 << XQS) - 1);
       const int c = cbase + sw * 8 + chl;
       const bool val = c < p.Cin;
-      const e2e_in_chan_t* chd = p.chans + (val ? c : 0);
-      xdsh[j] = val ? chd->dshift : (1 << 30);
-      xbase[j] = (gfloat_p)(chd->ptr + (long long)n * chd->nstride);
-      xa[j] = 1.f; xb[j] = 0.f; xsl[j] = 1.f;
-      if (val && chd->scale != nullptr) {
-        xa[j] = chd->scale[(long long)n * chd->ab_nstride];
-        xb[j] = chd->shift[(long long)n * chd->ab_nstride];
-        xsl[j] = chd->slope;
-      }
+      const ConcatChan chd = concat_chan(p.chans[val ? c : 0], n);
+      xdsh[j] = val ? chd.dshift : (1 << 30);                  // (absent channel: no depth is in range)
+      xbase[j] = (gfloat_p)chd.base;
+      xa[j] = chd.a; xb[j] = chd.b; xsl[j] = chd.slope;
       if constexpr (NPC == 2) { xa[j] *= xsc; xb[j] *= xsc; }   // LeakyReLU commutes with a positive scale
       xro[j] = x_r - 1;
       xgc[j] = 4 * x_q;
-      xoff[j] = (x_r - 1) * p.Wi + 4 * x_q - (val ? chd->dshift : 0) * in_plane;
+      xoff[j] = (x_r - 1) * p.Wi + 4 * x_q - (val ? chd.dshift : 0) * in_plane;
       xdst[j] = (sw * 8 + chl) * CSTR2 + x_r * GXROWB + x_q * 8;
     }
     const int y_grp = lane & 31, y_r = y_grp >> XQS, y_q = y_grp & ((1 << XQS) - 1);
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int S = dd * in_plane + h0 * p.Wi + w0;
 #pragma unroll
       for (int j = 0; j < NX; ++j) {
-        const bool ok = (unsigned)(h0 + xro[j]) < (unsigned)p.Hi && xgc[j] < p.Wi - w0 && (unsigned)(dd - xdsh[j]) < (unsigned)p.Di;
+        const bool ok = (unsigned)(h0 + xro[j]) < (unsigned)p.Hi && xgc[j] < p.Wi - w0 && concat_depth(q.d, p.sd, xdsh[j], p.Di).valid;
         const unsigned off = ok ? (unsigned)(S + xoff[j]) : 0u;
         vx[rs][j] = *reinterpret_cast<gf4_p>(xbase[j] + off);
         ta[rs][j] = ok ? xa[j] : 0.f;

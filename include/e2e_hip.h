@@ -248,6 +248,12 @@ int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, float* dw, vo
  * fma-mix split (K1m, the fp16 transposed convs).  K % 16 == 0.  No reference counterpart (torch computes in fp32). */
 int e2e_diag_split_gemm(const float* A, const float* Bt, float* D, int K, int mode, const unsigned* absmax_b, void* stream);
 
+/* Diagnostic, host only (no GPU call): the store rule of e2e_out_chan_t as every data-gradient kernel applies it
+ * (csrc/e2e_concat.h: concat_store_slice).  The workgroups of (shifted) depth d of a D-slice volume, destination shift `dshift`:
+ * *dd = the source slice they own; returns what they do with it: 0 store, 1 add (accumulate != 0), 2 zero-fill (the slice
+ * receives nothing and this launch is the buffer's first writer), 3 skip (it receives nothing and holds earlier writers' values). */
+int e2e_diag_concat_slice(int d, int dshift, int D, int accumulate, int* dd);
+
 /* Diagnostic: the shader clock the hot kernels ran at.  Workgroup 0 of every launch of family 0 (K1m, conv133_mm) / 1 (the
  * matrix-pipe K1w, conv133_wgrad v5) adds its s_memtime span (shader-clock cycles) and its s_memrealtime span (100 MHz) to a
  * device-side pair; this call synchronises the device and returns *mhz = cycles / time over all launches since the last reset

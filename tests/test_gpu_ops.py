@@ -91,6 +91,11 @@ CONV_CASES = [
     (2, [(40, True), (30, False)], 70, (3, 32, 64), (1, 1, 1), 0.2),         # 70 -> 70: ragged chunks and out-channel blocks both ways, depth shifts, d = 0.2
     (1, [(100, True), (100, False), (100, False), (20, False)], 33, (2, 32, 32), (1, 1, 1), 0.1),   # 320 -> 33: twenty chunks, one tile per slice
     (1, [(24, True)], 24, (9, 48, 32), (1, 1, 1), 1.0),                      # more items than a workgroup's first round on a small grid (E2E_MM_GRID)
+    # volumes shallower than the largest shift (|s| <= 2), on the paths other than plain K1: the slices of vanished groups are
+    # zero-filled by a first writer and left alone by a later one (csrc/e2e_concat.h)
+    (1, [(40, True)], 34, (1, 32, 32), (1, 1, 1), 1.0),                      # conv133_mm (conv133_dense under E2E_CONV_MM=0): one tile row pair, every shifted group vanishes
+    (2, [(20, True), (13, False)], 34, (1, 20, 36), (1, 1, 1), 0.25),        # conv133_sparse: one slice, ragged tiles, two sources
+    (1, [(20, True), (13, False)], 34, (2, 20, 36), (1, 1, 1), 0.25),        # conv133_sparse, D = 2: groups +-1 partly survive, groups +-2 vanish
 ]
 
 
@@ -837,6 +842,9 @@ def test_conv133_forward_split_k_matches_unsplit(B, src_desc, cout, dims, stride
     (2, [(256, True)], 320, (4, 16, 16), (2, 2, 2), 1.0),                                # strided: sub-pixel data gradient
     (1, [(320, True)], 320, (2, 4, 4), (1, 1, 1), 1.0),
     (1, [(100, True), (60, False)], 128, (3, 12, 40), (1, 1, 1), 0.3),                    # three ragged 16 x 16 tiles per slice
+    # conv133_dsum_kernel on a one-slice volume: every shifted group's slice receives nothing (zero-filled, then left alone).
+    # 49 dy planes is the fewest for which e2e_conv133_dgrad_ws_bytes > 0 on such planes; ragged 3 x 5 plane, two sources
+    (1, [(30, True), (15, False)], 49, (1, 3, 5), (1, 1, 1), 1.0),
 ])
 def test_conv133_data_gradient_split_k_matches_unsplit(B, src_desc, cout, dims, stride, density):
     """Deep levels: data gradient with the dy-plane chunks split over several workgroups (+ the sum / scatter kernel:

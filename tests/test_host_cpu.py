@@ -828,3 +828,31 @@ def test_k1_queries_equal_the_parent():
            ((row, mk.query(L, row), (f, d, n)) for row, f, d, n in zip(rows, g["fwd_ws_bytes"], g["dgrad_ws_bytes"], g["num_partials"]))
            if got != want]
     assert not bad, "%d rows differ, first (row, (fwd, dgrad, partials) now, at the parent): %s" % (len(bad), bad[:3])
+
+
+def test_concat_store_slices_partition_the_volume():
+    """The store rule of the data gradients (csrc/e2e_concat.h: concat_store_slice, through the host-only entry
+    e2e_diag_concat_slice): for every depth D in 1..9, shift in -6..6 and both values of the accumulate flag, the D depths of
+    a launch name every source slice exactly once; a slice is stored (first writer) or added to (later writer) exactly where
+    the shifted tensor read it, dd = d - dshift, and every other slice is zero-filled by a first writer and left alone by a
+    later one."""
+    import ctypes
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    STORE, ADD, ZERO_FILL, SKIP = 0, 1, 2, 3
+    for D in range(1, 10):
+        for dshift in range(-6, 7):
+            for accumulate in (0, 1):
+                named = []
+                for d in range(D):
+                    dd = ctypes.c_int(-1)
+                    action = L.diag_concat_slice(d, dshift, D, accumulate, ctypes.byref(dd))
+                    dd = dd.value
+                    ctx = (D, dshift, accumulate, d, dd, action)
+                    assert 0 <= dd < D, ctx
+                    if 0 <= dd + dshift < D:
+                        assert action == (ADD if accumulate else STORE) and dd == d - dshift, ctx
+                    else:
+                        assert action == (SKIP if accumulate else ZERO_FILL), ctx
+                    named.append(dd)
+                assert sorted(named) == list(range(D)), (D, dshift, accumulate, named)
