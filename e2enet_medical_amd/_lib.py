@@ -139,6 +139,7 @@ SIGNATURES = {
     "e2e_conv133_wgrad": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P]),
     "e2e_diag_split_gemm": (I, [P, P, P, I, I, P, P]),
     "e2e_diag_concat_slice": (I, [I, I, I, I, P]),
+    "e2e_diag_wgrad_walk": (I, [I, I, I, I, I, I, I, I, I, I, I, P]),
     "e2e_diag_kernel_clock": (I, [I, P, P, I]),
     "e2e_in_stats_finalize": (I, [P, I, P, P, F, P, P, P, P, I, I, P]),
     "e2e_in_lrelu_bwd_ws_doubles": (LL, [I, I]),
@@ -256,7 +257,7 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
               "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
               "e2e_loader_crop_max_batch", "e2e_nifti_scan_grid_voxels", "e2e_deflate_chunk_bytes", "e2e_deflate_slot_bytes",
-              "e2e_diag_concat_slice"}
+              "e2e_diag_concat_slice", "e2e_diag_wgrad_walk"}
 
 
 class E2EError(RuntimeError):
@@ -294,7 +295,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 29          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 30          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

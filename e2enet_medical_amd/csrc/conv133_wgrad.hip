@@ -13,27 +13,16 @@
 // the 16 x 16 sub-block for all 9 taps (36 accumulator registers).  dy and the halo'd input tile are staged in LDS
 // with channel strides == 2 (mod 32) so that the A/B fragment reads (16 channels x 4 consecutive pixels) hit 32
 // distinct banks.  Per-chunk partial sums go to a slab, reduced in fixed order by a second kernel (deterministic).
-#include "e2e_common.h"
-#include "e2e_split.h"
-#include "e2e_concat.h"
+//
+// What the kernel bodies below share is defined once in e2e_wgrad.h: the parameter struct, chunk -> tile range (the device
+// half of split_tiles / split_tiles_per_item), tile -> origin, the wave-uniform channel descriptors, the slab a workgroup
+// writes and the 16 x 16 block store into it.  Here: the LDS images, staging pipelines and MFMA loops, and plan_wgrad.
+#include "e2e_wgrad.h"
 #include <cstdlib>
 
 namespace {
 
 using namespace e2e;
-
-struct WgParams {
-  const e2e_in_chan_t* chans;
-  const float* dy;
-  float* slab;
-  int B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, sd;
-  int tiles_x, tiles_y, tiles_d, tiles_per_n;
-  long long total_tiles;
-  int tiles_per_chunk;
-  int cblocks;
-  int cblocks_segs;   // v3: chunks per batch item
-  int dbg;     // diagnostic: bit0 = skip staging, bit1 = skip the MFMA phase (timing splits only; results are garbage)
-};
 
 constexpr int pad_mod32_2(int v) {
   while (v % 32 != 2) ++v;
@@ -69,23 +58,16 @@ __global__ __launch_bounds__(256) void conv133_wgrad_kernel(WgParams p) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  for (int ti = 0; ti < p.tiles_per_chunk; ++ti) {
-    const long long tile = (long long)chunk * p.tiles_per_chunk + ti;
-    if (tile >= p.total_tiles) break;
-    const int n = (int)((unsigned)tile / (unsigned)p.tiles_per_n);
-    int t = (int)tile - n * p.tiles_per_n;
-    const int tx = t % p.tiles_x;
-    t /= p.tiles_x;
-    const int ty = t % p.tiles_y;
-    const int td = t / p.tiles_y;
-    const int d0 = td * ND, h0 = ty * TH, w0 = tx * TW;
+  const WgTiles tiles = chunk_tiles(p, chunk);
+  for (long long tile = tiles.lo; tile < tiles.hi; ++tile) {
+    const WgOrigin to = tile_origin<ND, TH, TW>(p, tile);
+    const int n = to.n, d0 = to.d0, h0 = to.h0, w0 = to.w0;
     const int hbase = h0 * SH - 1, wbase = w0 * SW - 1;
 
     // ---- stage the input tile: 32 channels x ND slices x IH x IW (transform on load, zero padded) ----
     for (int cl = wave; cl < 32; cl += 4) {          // one wave per channel -> channel descriptor is wave-uniform
-      const int c = cb * 32 + cl;
-      const bool cv = c < p.Cin;
-      const ConcatChan chd = concat_chan(p.chans[cv ? c : 0], n);   // (!cv: channel 0, every element masked below)
+      bool cv;
+      const ConcatChan chd = concat_chan_or_first(p.chans, cb * 32 + cl, p.Cin, n, cv);
       gfloat_p base = (gfloat_p)chd.base;
       for (int e = lane; e < ND * C::IH * C::IW; e += 64) {
         const int nd = e / (C::IH * C::IW);
@@ -139,18 +121,7 @@ __global__ __launch_bounds__(256) void conv133_wgrad_kernel(WgParams p) {
     __syncthreads();
   }
 
-  // D[i = o][j = c]: col = lane & 15 -> c, row = (lane >> 4) * 4 + reg -> o
-  float* sp = p.slab + (long long)chunk * p.Cout * p.Cin * 9;
-  const int c = cb * 32 + ch * 16 + (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = ob * 32 + oh * 16 + (lane >> 4) * 4 + r;
-    if (o < p.Cout && c < p.Cin) {
-      float* dst = sp + ((long long)o * p.Cin + c) * 9;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) dst[t] = acc[t][r];
-    }
-  }
+  store_slab_block16(p, wg_slab_index(chunk, 0, 1), ob * 32 + oh * 16, cb * 32 + ch * 16, lane, acc);
 }
 
 // ---- v2: stride-1, rows that are multiples of 4 floats ---------------------------------------------------------
@@ -205,37 +176,8 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const long long tile_lo = (long long)chunk * p.tiles_per_chunk;
-  long long tile_hi = tile_lo + p.tiles_per_chunk;
-  if (tile_hi > p.total_tiles) tile_hi = p.total_tiles;
-
-  auto decode = [&](long long tile, int& n, int& d0, int& h0, int& w0) {
-    n = (int)((unsigned)tile / (unsigned)p.tiles_per_n);      // (fewer than 2^31 tiles: 32-bit division)
-    int t = (int)tile - n * p.tiles_per_n;
-    const int tx = t % p.tiles_x;
-    t /= p.tiles_x;
-    const int ty = t % p.tiles_y;
-    d0 = (t / p.tiles_y) * ND;
-    h0 = ty * TH;
-    w0 = tx * TW;
-  };
-
-  // ---- wave-uniform descriptors of this wave's 8 input channels (scalar registers) ----
-  gfloat_p xbase[C::XCW];
-  float xa[C::XCW], xb[C::XCW], xsl[C::XCW];
-  int xdsh[C::XCW];
-  bool xval[C::XCW];
-  auto load_desc = [&](int n) {
-#pragma unroll
-    for (int k = 0; k < C::XCW; ++k) {
-      const int c = cbase + wave * C::XCW + k;
-      xval[k] = c < p.Cin;
-      const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
-      xdsh[k] = chd.dshift;
-      xbase[k] = (gfloat_p)chd.base;
-      xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
-    }
-  };
+  const WgTiles tiles = chunk_tiles(p, chunk);
+  WaveChans<C::XCW> xc;         // this wave's 8 input channels
 
   // ---- per-lane geometry of the float4 groups (independent of the channel) ----
   int g_lrow[C::ITX], g_q[C::ITX], g_nd[C::ITX], g_r[C::ITX];
@@ -264,9 +206,9 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
       const long long lane_off = (long long)hi * p.Wi + gc;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const ConcatDepth sl = concat_depth(dq, p.sd, xdsh[k], p.Di);
-        const bool ok = lane_ok && xval[k] && sl.valid && !(p.dbg & 4);
-        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
+        const ConcatDepth sl = concat_depth(dq, p.sd, xc.dshift[k], p.Di);
+        const bool ok = lane_ok && xc.valid[k] && sl.valid;
+        vx[k][it] = *reinterpret_cast<gf4_p>(xc.base[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
       }
     }
     const int dq = d0 + y_nd, ho = h0 + y_r, wo = w0 + y_col;
@@ -274,7 +216,7 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
 #pragma unroll
     for (int k = 0; k < C::YCW; ++k) {
       const int o = ob * 32 + wave * C::YCW + k;
-      const bool ok = lane_ok && o < p.Cout && !(p.dbg & 4);
+      const bool ok = lane_ok && o < p.Cout;
       const long long off = ok ? (((long long)n * p.Cout + o) * p.Do + dq) * out_plane + (long long)ho * p.Wo + wo : 0;
       vy[k] = *reinterpret_cast<gf4_p>((gfloat_p)p.dy + off);
     }
@@ -288,12 +230,12 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
       const bool lane_ok = dq < p.Do && (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const ConcatDepth sl = concat_depth(dq, p.sd, xdsh[k], p.Di);
-        const bool ok = lane_ok && xval[k] && sl.valid;
+        const ConcatDepth sl = concat_depth(dq, p.sd, xc.dshift[k], p.Di);
+        const bool ok = lane_ok && xc.valid[k] && sl.valid;
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float t = e2e::in_act(vx[k][it][j], xa[k], xb[k], xsl[k]);
+          const float t = e2e::in_act(vx[k][it][j], xc.a[k], xc.b[k], xc.slope[k]);
           v[j] = ok ? t : 0.f;
         }
         float* row = xs + (wave * C::XCW + k) * C::CS + g_lrow[it] * C::PITCH;
@@ -322,21 +264,20 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
     }
   };
 
-  if (tile_lo < tile_hi) {
-    int n, d0, h0, w0;
-    decode(tile_lo, n, d0, h0, w0);
-    load_desc(n);
-    if (!(p.dbg & 1)) prefetch(n, d0, h0, w0);
-    for (long long tile = tile_lo; tile < tile_hi; ++tile) {
-      if (!(p.dbg & 1)) commit(d0, h0, w0);
-      int nn = n, nd0 = d0, nh0 = h0, nw0 = w0;
-      const bool more = tile + 1 < tile_hi;
+  if (tiles.lo < tiles.hi) {
+    WgOrigin cur = tile_origin<ND, TH, TW>(p, tiles.lo);
+    xc.load(p, cbase + wave * C::XCW, cur.n);
+    prefetch(cur.n, cur.d0, cur.h0, cur.w0);
+    for (long long tile = tiles.lo; tile < tiles.hi; ++tile) {
+      commit(cur.d0, cur.h0, cur.w0);
+      WgOrigin nxt = cur;
+      const bool more = tile + 1 < tiles.hi;
       if (more) {
-        decode(tile + 1, nn, nd0, nh0, nw0);
-        if (nn != n) load_desc(nn);                       // rare: the chunk crosses a batch item
+        nxt = tile_origin<ND, TH, TW>(p, tile + 1);
+        if (nxt.n != cur.n) xc.load(p, cbase + wave * C::XCW, nxt.n);   // rare: the chunk crosses a batch item
       }
       __syncthreads();
-      if (more && !(p.dbg & 1)) prefetch(nn, nd0, nh0, nw0);              // in flight during the MFMA phase below
+      if (more) prefetch(nxt.n, nxt.d0, nxt.h0, nxt.w0);  // in flight during the MFMA phase below
 
       // MFMA phase.  The A/B fragments of k-step s+1 are read from LDS before the 9 MFMAs of k-step s are issued
       // (explicit double registers + sched_barrier), so the matrix pipe never waits on an LDS round trip.
@@ -349,7 +290,8 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) b_cur[kh * 3 + kw] = bp[kh * C::PITCH + kw];
-      for (int row = 0; row < ((p.dbg & 2) ? 0 : ND * TH); ++row) {
+#pragma unroll 1                                        // (stays a loop: unrolled it is up to 32 rows x TW / 4 k-steps x 9 MFMAs)
+      for (int row = 0; row < ND * TH; ++row) {
         const int nd = row / TH, r = row - nd * TH;
         const float* apr = ap + row * TW;
         const float* bpr = bp + nd * (C::IH * C::PITCH) + r * C::PITCH;
@@ -374,35 +316,21 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
 #pragma unroll
               for (int kw = 0; kw < 3; ++kw) b_nxt[kh * 3 + kw] = bpn[kh * C::PITCH + kw];
           }
-#ifndef E2E_WG_NOSB
           __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
           for (int t = 0; t < 9; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur, b_cur[t], acc[t], 0, 0, 0);
-#ifndef E2E_WG_NOSB
           __builtin_amdgcn_sched_barrier(0);
-#endif
           a_cur = a_nxt;
 #pragma unroll
           for (int t = 0; t < 9; ++t) b_cur[t] = b_nxt[t];
         }
       }
       __syncthreads();
-      n = nn; d0 = nd0; h0 = nh0; w0 = nw0;
+      cur = nxt;
     }
   }
 
-  float* sp = p.slab + (long long)chunk * p.Cout * p.Cin * 9;
-  const int c = cbase + cbl * 32 + ch * 16 + (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = ob * 32 + oh * 16 + (lane >> 4) * 4 + r;
-    if (o < p.Cout && c < p.Cin) {
-      float* dst = sp + ((long long)o * p.Cin + c) * 9;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) dst[t] = acc[t][r];
-    }
-  }
+  store_slab_block16(p, wg_slab_index(chunk, 0, 1), ob * 32 + oh * 16, cbase + cbl * 32 + ch * 16, lane, acc);
 }
 
 // ---- v3: large stride-1 planes (rows >= 32, multiples of 4 floats): double-buffered LDS ------------------------------
@@ -417,6 +345,7 @@ __global__ __launch_bounds__(256 * NCB) void conv133_wgrad_v2_kernel(WgParams p)
 // over the k-steps 1.29.
 template <int NCB, int NOB, int NKB = 1>
 struct W3Cfg {
+  static_assert(NKB == 1 || NKB == WG_ROW_HALVES, "NKB = slabs per workgroup");
   static_assert(NCB * NOB * NKB == 2, "8 waves: 2 x 2 sub-blocks of 16 x 16 for two 32 x 32 blocks, or for the two row halves of one");
   static constexpr int TH = 4, TW = 32, TP = TH * TW;
   static constexpr int IH = TH + 2;
@@ -446,9 +375,8 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
   float* const xs0 = lds3;
   float* const ys0 = lds3 + 2 * C::XBUF;
 
-  // chunk = (batch item, run of tiles inside it)
-  const int segs = p.cblocks_segs;
-  const int n = blockIdx.x / segs, seg = blockIdx.x - n * segs;
+  const WgItemTiles tiles = chunk_tiles_per_item(p, blockIdx.x);
+  const int n = tiles.n, tile_lo = tiles.lo, tile_hi = tiles.hi;
   const int cgroups = p.cblocks;
   const int cg = blockIdx.y % cgroups, ob = blockIdx.y / cgroups;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -464,33 +392,8 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int tile_lo = seg * p.tiles_per_chunk;
-  int tile_hi = tile_lo + p.tiles_per_chunk;
-  if (tile_hi > p.tiles_per_n) tile_hi = p.tiles_per_n;
-
-  auto decode = [&](int tile, int& d0, int& h0, int& w0) {
-    const int tx = tile % p.tiles_x;
-    const int t = tile / p.tiles_x;
-    const int ty = t % p.tiles_y;
-    d0 = t / p.tiles_y;
-    h0 = ty * C::TH;
-    w0 = tx * C::TW;
-  };
-
-  // ---- wave-uniform descriptors of this wave's 8 input channels (scalar registers, fixed for the workgroup) ----
-  gfloat_p xbase[C::XCW];
-  float xa[C::XCW], xb[C::XCW], xsl[C::XCW];
-  int xdsh[C::XCW];
-  bool xval[C::XCW];
-#pragma unroll
-  for (int k = 0; k < C::XCW; ++k) {
-    const int c = cbase + wave * C::XCW + k;
-    xval[k] = c < p.Cin;
-    const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
-    xdsh[k] = chd.dshift;
-    xbase[k] = (gfloat_p)chd.base;
-    xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
-  }
+  WaveChans<C::XCW> xc;         // this wave's input channels, fixed for the workgroup
+  xc.load(p, cbase + wave * C::XCW, n);
 
   // ---- per-lane geometry ----
   const int g_r = (lane < C::GPC ? lane : C::GPC - 1) / C::NQ;
@@ -511,9 +414,9 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
       const int hi = h0 - 1 + g_r, gc = w0 - 4 + 4 * g_q;
       const bool lane_ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
       const long long lane_off = (long long)hi * p.Wi + gc;
-      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
-      const bool ok = lane_ok && xval[k] && sl.valid;
-      vx[k] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
+      const ConcatDepth sl = concat_depth(d0, p.sd, xc.dshift[k], p.Di);
+      const bool ok = lane_ok && xc.valid[k] && sl.valid;
+      vx[k] = *reinterpret_cast<gf4_p>(xc.base[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
     } else {
       const int it = s - C::XCW;
       const int ho = h0 + y_r, wo = w0 + y_col;
@@ -535,12 +438,12 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
       //  that the in-loop staging below stays straight-line code and its loads get exact vmcnt distances)
       const int k = s;
       const int hi = h0 - 1 + g_r, gc = w0 - 4 + 4 * g_q;
-      const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
-      const bool ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && xval[k] && sl.valid;
+      const ConcatDepth sl = concat_depth(d0, p.sd, xc.dshift[k], p.Di);
+      const bool ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi && xc.valid[k] && sl.valid;
       float v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float t = e2e::in_act(vx[k][j], xa[k], xb[k], xsl[k]);
+        const float t = e2e::in_act(vx[k][j], xc.a[k], xc.b[k], xc.slope[k]);
         v[j] = ok ? t : 0.f;
       }
       float2* dst = reinterpret_cast<float2*>(xs0 + buf * C::XBUF + (wave * C::XCW + k) * C::CS + g_r * C::PITCH + 4 * g_q);
@@ -558,23 +461,22 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
   };
 
   if (tile_lo < tile_hi) {
-    int d0, h0, w0;
-    decode(tile_lo, d0, h0, w0);
-    prefetch(d0, h0, w0);
+    const WgOrigin first = tile_origin_in_item<1, C::TH, C::TW>(p, n, tile_lo);
+    prefetch(first.d0, first.h0, first.w0);
 #pragma unroll
-    for (int s = 0; s < C::PIECES; ++s) commit_piece(s, 0, d0, h0, w0);
-    int nd0 = d0, nh0 = h0, nw0 = w0;
+    for (int s = 0; s < C::PIECES; ++s) commit_piece(s, 0, first.d0, first.h0, first.w0);
+    WgOrigin nxt = first;
     if (tile_lo + 1 < tile_hi) {
-      decode(tile_lo + 1, nd0, nh0, nw0);
-      prefetch(nd0, nh0, nw0);
+      nxt = tile_origin_in_item<1, C::TH, C::TW>(p, n, tile_lo + 1);
+      prefetch(nxt.d0, nxt.h0, nxt.w0);
     }
-    int fd0 = nd0, fh0 = nh0, fw0 = nw0;               // tile + 2: requested piece by piece inside the loop
+    WgOrigin far = nxt;                                // tile + 2: requested piece by piece inside the loop
     __syncthreads();
 
     const int li = lane & 15, lk = lane >> 4;
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
       const int buf = (tile - tile_lo) & 1;
-      decode(tile + 2 < tile_hi ? tile + 2 : tile_hi - 1, fd0, fh0, fw0);   // registers hold tile + 1 -> image buf ^ 1 during this phase
+      far = tile_origin_in_item<1, C::TH, C::TW>(p, n, tile + 2 < tile_hi ? tile + 2 : tile_hi - 1);   // registers hold tile + 1 -> image buf ^ 1 during this phase
       const float* ap = ys0 + buf * C::YBUF + (obl * 32 + oh * 16 + li) * C::OS + lk + kq * C::ROWS * C::TW;
       const float* bp = xs0 + buf * C::XBUF + (cbl * 32 + ch * 16 + li) * C::CS + lk + C::COL0 + kq * C::ROWS * C::PITCH;
       float a_cur = ap[0];
@@ -606,8 +508,8 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
             // staging in the shadow of the MFMAs, one piece per k-step, unconditionally (past the end of the chunk the
             // last tile is simply staged again into the image nobody reads): any branch here makes the compiler wait
             // for vmcnt(0) at every piece, i.e. for the load it issued one k-step earlier
-            if (t == 0 && s < C::PIECES) commit_piece(s < C::PIECES ? s : 0, buf ^ 1, nd0, nh0, nw0);
-            if (t == 4 && s >= 1 && s - 1 < C::PIECES) prefetch_piece(s >= 1 && s - 1 < C::PIECES ? s - 1 : 0, fd0, fh0, fw0);   // registers committed one k-step ago
+            if (t == 0 && s < C::PIECES) commit_piece(s < C::PIECES ? s : 0, buf ^ 1, nxt.d0, nxt.h0, nxt.w0);
+            if (t == 4 && s >= 1 && s - 1 < C::PIECES) prefetch_piece(s >= 1 && s - 1 < C::PIECES ? s - 1 : 0, far.d0, far.h0, far.w0);   // registers committed one k-step ago
           }
           __builtin_amdgcn_sched_barrier(0);
           a_cur = a_nxt;
@@ -615,22 +517,12 @@ __global__ __launch_bounds__(512) void conv133_wgrad_v3_kernel(WgParams p) {
           for (int t = 0; t < 9; ++t) b_cur[t] = b_nxt[t];
         }
       }
-      nd0 = fd0; nh0 = fh0; nw0 = fw0;
-      if (!(p.dbg & 32)) __syncthreads();
+      nxt = far;
+      __syncthreads();
     }
   }
 
-  float* sp = p.slab + ((long long)blockIdx.x * NKB + kq) * p.Cout * p.Cin * 9;
-  const int c = cbase + cbl * 32 + ch * 16 + (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = obase + obl * 32 + oh * 16 + (lane >> 4) * 4 + r;
-    if (o < p.Cout && c < p.Cin) {
-      float* dst = sp + ((long long)o * p.Cin + c) * 9;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) dst[t] = acc[t][r];
-    }
-  }
+  store_slab_block16(p, wg_slab_index(blockIdx.x, kq, NKB), obase + obl * 32 + oh * 16, cbase + cbl * 32 + ch * 16, lane, acc);
 }
 
 // ---- network input layer: Cin <= 4 (BraTS: 4 modalities, CT: 1), stride 1, large planes ------------------------------
@@ -653,12 +545,13 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
   float* xs = lds;
   float* ys = lds + 4 * C::CS;
 
-  const int segs = p.cblocks_segs;
-  const int n = blockIdx.x / segs, seg = blockIdx.x - n * segs;
+  const WgItemTiles tiles = chunk_tiles_per_item(p, blockIdx.x);
+  const int n = tiles.n, tile_lo = tiles.lo, tile_hi = tiles.hi;
   const int ob = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int oh = wave & 1, kq = wave >> 1;
+  static_assert(C::TH % WG_ROW_HALVES == 0, "the wave groups kq split the tile rows and write a slab each");
   const long long in_plane = (long long)p.Hi * p.Wi;
   const long long out_plane = (long long)p.Ho * p.Wo;
 
@@ -666,21 +559,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
 #pragma unroll
   for (int m = 0; m < 3; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int tile_lo = seg * p.tiles_per_chunk;
-  int tile_hi = tile_lo + p.tiles_per_chunk;
-  if (tile_hi > p.tiles_per_n) tile_hi = p.tiles_per_n;
-  auto decode = [&](int tile, int& d0, int& h0, int& w0) {
-    const int tx = tile % p.tiles_x;
-    const int t = tile / p.tiles_x;
-    const int ty = t % p.tiles_y;
-    d0 = t / p.tiles_y;
-    h0 = ty * C::TH;
-    w0 = tx * C::TW;
-  };
-
   // wave w stages input channel w (if it exists): descriptor in scalar registers
-  const bool xval = wave < p.Cin;
-  const ConcatChan chd = concat_chan(p.chans[xval ? wave : 0], n);   // (!xval: channel 0, masked where it is used)
+  bool xval;
+  const ConcatChan chd = concat_chan_or_first(p.chans, wave, p.Cin, n, xval);
   const gfloat_p xbase = (gfloat_p)chd.base;
   const float xa = chd.a, xb = chd.b, xsl = chd.slope;
   const int xdsh = chd.dshift;
@@ -752,23 +633,22 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
   }
 
   if (tile_lo < tile_hi) {
-    int d0, h0, w0;
-    decode(tile_lo, d0, h0, w0);
-    prefetch(d0, h0, w0);
+    WgOrigin to = tile_origin_in_item<1, C::TH, C::TW>(p, n, tile_lo);
+    prefetch(to.d0, to.h0, to.w0);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
-      commit(d0, h0, w0);
+      commit(to.d0, to.h0, to.w0);
       __syncthreads();
       if (tile + 1 < tile_hi) {
-        decode(tile + 1, d0, h0, w0);
-        prefetch(d0, h0, w0);
+        to = tile_origin_in_item<1, C::TH, C::TW>(p, n, tile + 1);
+        prefetch(to.d0, to.h0, to.w0);
       }
-      const float* ap = ys + (oh * 16 + li) * C::OS + lk + kq * (C::TH / 2) * C::TW;
-      const float* bp = xs + kq * (C::TH / 2) * C::PITCH;
+      const float* ap = ys + (oh * 16 + li) * C::OS + lk + kq * (C::TH / WG_ROW_HALVES) * C::TW;
+      const float* bp = xs + kq * (C::TH / WG_ROW_HALVES) * C::PITCH;
       float a_cur = ap[0], b_cur[3];
 #pragma unroll
       for (int m = 0; m < 3; ++m) b_cur[m] = bp[boff[m]];
 #pragma unroll
-      for (int row = 0; row < C::TH / 2; ++row) {
+      for (int row = 0; row < C::TH / WG_ROW_HALVES; ++row) {
 #pragma unroll
         for (int cq = 0; cq < C::TW / 4; ++cq) {
           const int nrow = cq + 1 < C::TW / 4 ? row : row + 1, ncq = cq + 1 < C::TW / 4 ? cq + 1 : 0;
@@ -790,7 +670,7 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
   }
 
   // D[i = o][j = column]: column = lane & 15 -> (c, tap), row = (lane >> 4) * 4 + reg -> o
-  float* sp = p.slab + ((long long)blockIdx.x * 2 + kq) * p.Cout * p.Cin * 9;
+  float* sp = wg_slab(p, wg_slab_index(blockIdx.x, kq, WG_ROW_HALVES));
   const int c = li & 3;
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
@@ -807,7 +687,6 @@ __global__ __launch_bounds__(256) void conv133_wgrad_smallc_kernel(WgParams p) {
 // Same pipeline as v2.  Output tile 4 x 16; the 9 x 33 input patch it needs is staged per channel as rows of
 // [20 even columns | 20 odd columns] so that the B fragments (4 consecutive output pixels = input columns 2 apart)
 // are unit-stride LDS reads: tap kw = 0 -> odd[wo + 1], kw = 1 -> even[wo + 2], kw = 2 -> odd[wo + 2].
-template <int DUMMY>
 struct WS2Cfg {
   static constexpr int TH = 4, TW = 16, TP = 64;
   static constexpr int IH = 2 * TH + 1;                       // 9 input rows
@@ -823,7 +702,7 @@ struct WS2Cfg {
 };
 
 __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
-  using C = WS2Cfg<0>;
+  using C = WS2Cfg;
   __shared__ __attribute__((aligned(16))) float lds[C::LDS_FLOATS];
   float* xs = lds;
   float* ys = lds + 32 * C::CS;
@@ -841,36 +720,8 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const long long tile_lo = (long long)chunk * p.tiles_per_chunk;
-  long long tile_hi = tile_lo + p.tiles_per_chunk;
-  if (tile_hi > p.total_tiles) tile_hi = p.total_tiles;
-
-  auto decode = [&](long long tile, int& n, int& d0, int& h0, int& w0) {
-    n = (int)((unsigned)tile / (unsigned)p.tiles_per_n);      // (fewer than 2^31 tiles: 32-bit division)
-    int t = (int)tile - n * p.tiles_per_n;
-    const int tx = t % p.tiles_x;
-    t /= p.tiles_x;
-    const int ty = t % p.tiles_y;
-    d0 = t / p.tiles_y;
-    h0 = ty * C::TH;
-    w0 = tx * C::TW;
-  };
-
-  gfloat_p xbase[C::XCW];
-  float xa[C::XCW], xb[C::XCW], xsl[C::XCW];
-  int xdsh[C::XCW];
-  bool xval[C::XCW];
-  auto load_desc = [&](int n) {
-#pragma unroll
-    for (int k = 0; k < C::XCW; ++k) {
-      const int c = cbase + wave * C::XCW + k;
-      xval[k] = c < p.Cin;
-      const ConcatChan chd = concat_chan(p.chans[xval[k] ? c : 0], n);   // (!xval: channel 0, masked where it is used)
-      xdsh[k] = chd.dshift;
-      xbase[k] = (gfloat_p)chd.base;
-      xa[k] = chd.a; xb[k] = chd.b; xsl[k] = chd.slope;
-    }
-  };
+  const WgTiles tiles = chunk_tiles(p, chunk);
+  WaveChans<C::XCW> xc;         // this wave's 8 input channels
 
   int g_r[C::ITX], g_q[C::ITX];
 #pragma unroll
@@ -894,9 +745,9 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
       const long long lane_off = (long long)hi * p.Wi + gc;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
-        const bool ok = lane_ok && xval[k] && sl.valid;
-        vx[k][it] = *reinterpret_cast<gf4_p>(xbase[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
+        const ConcatDepth sl = concat_depth(d0, p.sd, xc.dshift[k], p.Di);
+        const bool ok = lane_ok && xc.valid[k] && sl.valid;
+        vx[k][it] = *reinterpret_cast<gf4_p>(xc.base[k] + (ok ? (long long)sl.din * in_plane + lane_off : 0));
       }
     }
     const int ho = h0 + y_r, wo = w0 + y_col;
@@ -916,12 +767,12 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
       const bool lane_ok = (unsigned)hi < (unsigned)p.Hi && gc >= 0 && gc + 3 < p.Wi;
 #pragma unroll
       for (int k = 0; k < C::XCW; ++k) {
-        const ConcatDepth sl = concat_depth(d0, p.sd, xdsh[k], p.Di);
-        const bool ok = lane_ok && xval[k] && sl.valid;
+        const ConcatDepth sl = concat_depth(d0, p.sd, xc.dshift[k], p.Di);
+        const bool ok = lane_ok && xc.valid[k] && sl.valid;
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float t = e2e::in_act(vx[k][it][j], xa[k], xb[k], xsl[k]);
+          const float t = e2e::in_act(vx[k][it][j], xc.a[k], xc.b[k], xc.slope[k]);
           v[j] = ok ? t : 0.f;
         }
         float* row = xs + (wave * C::XCW + k) * C::CS + g_r[it] * C::PITCH;
@@ -940,21 +791,20 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
     }
   };
 
-  if (tile_lo < tile_hi) {
-    int n, d0, h0, w0;
-    decode(tile_lo, n, d0, h0, w0);
-    load_desc(n);
-    prefetch(n, d0, h0, w0);
-    for (long long tile = tile_lo; tile < tile_hi; ++tile) {
-      commit(d0, h0, w0);
-      int nn = n, nd0 = d0, nh0 = h0, nw0 = w0;
-      const bool more = tile + 1 < tile_hi;
+  if (tiles.lo < tiles.hi) {
+    WgOrigin cur = tile_origin<1, C::TH, C::TW>(p, tiles.lo);
+    xc.load(p, cbase + wave * C::XCW, cur.n);
+    prefetch(cur.n, cur.d0, cur.h0, cur.w0);
+    for (long long tile = tiles.lo; tile < tiles.hi; ++tile) {
+      commit(cur.d0, cur.h0, cur.w0);
+      WgOrigin nxt = cur;
+      const bool more = tile + 1 < tiles.hi;
       if (more) {
-        decode(tile + 1, nn, nd0, nh0, nw0);
-        if (nn != n) load_desc(nn);
+        nxt = tile_origin<1, C::TH, C::TW>(p, tile + 1);
+        if (nxt.n != cur.n) xc.load(p, cbase + wave * C::XCW, nxt.n);   // rare: the chunk crosses a batch item
       }
       __syncthreads();
-      if (more) prefetch(nn, nd0, nh0, nw0);
+      if (more) prefetch(nxt.n, nxt.d0, nxt.h0, nxt.w0);
 
       const int li = lane & 15, lk = lane >> 4;
       const float* ap = ys + (oh * 16 + li) * C::OS + lk;
@@ -974,21 +824,11 @@ __global__ __launch_bounds__(256) void conv133_wgrad_s2_kernel(WgParams p) {
         }
       }
       __syncthreads();
-      n = nn; d0 = nd0; h0 = nh0; w0 = nw0;
+      cur = nxt;
     }
   }
 
-  float* sp = p.slab + (long long)chunk * p.Cout * p.Cin * 9;
-  const int c = cbase + ch * 16 + (lane & 15);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = ob * 32 + oh * 16 + (lane >> 4) * 4 + r;
-    if (o < p.Cout && c < p.Cin) {
-      float* dst = sp + ((long long)o * p.Cin + c) * 9;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) dst[t] = acc[t][r];
-    }
-  }
+  store_slab_block16(p, wg_slab_index(chunk, 0, 1), ob * 32 + oh * 16, cbase + ch * 16, lane, acc);
 }
 
 __global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out,
@@ -1026,14 +866,6 @@ inline TileSel pick(int Ho, int Wo, bool strided) {
   if (m > 8) return {1, 8, 16};
   if (m > 4) return {2, 8, 8};
   return {8, 4, 4};
-}
-
-inline void set_tile_grid(WgParams& p, TileSel ts) {
-  p.tiles_x = e2e::cdiv(p.Wo, ts.tw);
-  p.tiles_y = e2e::cdiv(p.Ho, ts.th);
-  p.tiles_d = e2e::cdiv(p.Do, ts.nd);
-  p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
-  p.total_tiles = (long long)p.tiles_per_n * p.B;
 }
 
 // v2 applies to stride-1 (in plane) convs whose rows are multiples of 4 floats
@@ -1086,16 +918,27 @@ struct WgPlan {
   WgPath path;
   WgParams p;          // shape, tile grid, chunks, channel blocks; the pointers are added at launch
   int chunks, pairs;   // launch grid
+  int slabs_per_wg;    // WG_ROW_HALVES where the kernel's two wave groups keep a slab each, else 1
   int slabs;           // slabs the main kernel writes = slabs the reduction reads
-  TileSel ts;          // v1, v2: tile of the kernel template
+  TileSel ts;          // output pixels of a tile (v1, v2: the kernel template's)
   int ncb;             // v2: 32-channel input blocks per workgroup
   V3Form v3;
-  int geom;            // bf3: WgBf3Params::geom
 };
+
+inline void set_tile_grid(WgPlan& pl, TileSel ts) {
+  WgParams& p = pl.p;
+  pl.ts = ts;
+  p.tiles_x = e2e::cdiv(p.Wo, ts.tw);
+  p.tiles_y = e2e::cdiv(p.Ho, ts.th);
+  p.tiles_d = e2e::cdiv(p.Do, ts.nd);
+  p.tiles_per_n = p.tiles_d * p.tiles_y * p.tiles_x;
+  p.total_tiles = (long long)p.tiles_per_n * p.B;
+}
 
 inline WgPlan plan_wgrad(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
   WgPlan pl{};
-  WgParams& p = pl.p;
+  WgParams& p = pl.p;              // (p.segs stays 0 where the chunks come from split_tiles: the global walk)
+  pl.slabs_per_wg = 1;
   p.B = B; p.Cin = Cin; p.Cout = Cout; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.sd = sd;
   p.Do = (Di - 1) / sd + 1; p.Ho = (Hi - 1) / sh + 1; p.Wo = (Wi - 1) / sw + 1;
   const int cb32 = e2e::cdiv(Cin, 32), ob32 = e2e::cdiv(Cout, 32);
@@ -1103,52 +946,53 @@ inline WgPlan plan_wgrad(int B, int Cin, int Cout, int Di, int Hi, int Wi, int s
     pl.path = WG_S2;
     p.cblocks = cb32;
     pl.pairs = cb32 * ob32;
-    set_tile_grid(p, {1, 4, 16});
-    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 8, &p.tiles_per_chunk);
+    set_tile_grid(pl, {1, 4, 16});
+    pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 8, &p.tiles_per_chunk);
   } else if (use_smallc(Cin, Hi, Wi, sh, sw)) {
     pl.path = WG_SMALLC;
     pl.pairs = ob32;
-    set_tile_grid(p, {1, 8, 32});
-    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 1024, 4, &p.tiles_per_chunk, &p.cblocks_segs);   // 4 workgroups per CU
-    pl.slabs = 2 * pl.chunks;
+    set_tile_grid(pl, {1, 8, 32});
+    pl.slabs_per_wg = WG_ROW_HALVES;
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 1024, 4, &p.tiles_per_chunk, &p.segs);   // 4 workgroups per CU
   } else if (use_bf3(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
     pl.path = WG_BF3;
     p.cblocks = cb32;
     pl.pairs = cb32 * ob32;
-    set_tile_grid(p, {1, 4, 32});
+    set_tile_grid(pl, {1, 4, 32});
     // one workgroup per CU, equal work each; fewer chunks = fewer slabs to reduce
-    pl.slabs = pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.cblocks_segs);
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.segs);
   } else if (use_v3(Hi, Wi, sh, sw)) {
     pl.path = WG_V3;
     pl.v3 = v3_ksplit(Cin, Cout) ? V3_KSPLIT : (v3_wide_out(Cout) ? V3_WIDE_OUT : V3_WIDE_IN);
     p.cblocks = pl.v3 == V3_KSPLIT ? 1 : (pl.v3 == V3_WIDE_OUT ? cb32 : e2e::cdiv(Cin, 64));
     pl.pairs = p.cblocks * (pl.v3 == V3_WIDE_OUT ? e2e::cdiv(Cout, 64) : ob32);
-    set_tile_grid(p, {1, 4, 32});
-    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.cblocks_segs);   // as bf3
-    pl.slabs = pl.v3 == V3_KSPLIT ? 2 * pl.chunks : pl.chunks;   // two row-half slabs per workgroup
+    set_tile_grid(pl, {1, 4, 32});
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 8, &p.tiles_per_chunk, &p.segs);   // as bf3
+    if (pl.v3 == V3_KSPLIT) pl.slabs_per_wg = WG_ROW_HALVES;
   } else if (use_bf3_w16(Cin, Cout, Di, Hi, Wi, sd, sh, sw)) {
     pl.path = WG_BF3_W16;
-    pl.geom = 1;
+    p.geom = 1;
     p.cblocks = cb32;
     pl.pairs = cb32 * ob32;
-    set_tile_grid(p, {1, 8, 16});
-    pl.slabs = pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 4, &p.tiles_per_chunk, &p.cblocks_segs);   // one workgroup per CU
+    set_tile_grid(pl, {1, 8, 16});
+    pl.chunks = e2e::split_tiles_per_item(p.tiles_per_n, B, pl.pairs, 256, 4, &p.tiles_per_chunk, &p.segs);   // one workgroup per CU
   } else if (use_v2(Hi, Wi, sh, sw)) {
     pl.path = WG_V2;
-    pl.ts = pick(p.Ho, p.Wo, false);
+    const TileSel ts = pick(p.Ho, p.Wo, false);
     pl.ncb = v2_ncb(Cin, p.Ho, p.Wo);
     p.cblocks = e2e::cdiv(Cin, 32 * pl.ncb);
     pl.pairs = p.cblocks * ob32;
-    set_tile_grid(p, pl.ts);
-    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 4, &p.tiles_per_chunk);
+    set_tile_grid(pl, ts);
+    pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 512, 4, &p.tiles_per_chunk);
   } else {
     pl.path = WG_V1;
-    pl.ts = pick(p.Ho, p.Wo, sh != 1 || sw != 1);
+    const TileSel ts = pick(p.Ho, p.Wo, sh != 1 || sw != 1);
     p.cblocks = cb32;
     pl.pairs = cb32 * ob32;
-    set_tile_grid(p, pl.ts);
-    pl.slabs = pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 1024, 4, &p.tiles_per_chunk);
+    set_tile_grid(pl, ts);
+    pl.chunks = e2e::split_tiles(p.total_tiles, pl.pairs, 1024, 4, &p.tiles_per_chunk);
   }
+  pl.slabs = e2e::wg_slab_count(pl.chunks, pl.slabs_per_wg);
   return pl;
 }
 
@@ -1181,6 +1025,32 @@ extern "C" long long e2e_conv133_wgrad_ws_bytes(int B, int Cin, int Cout, int Di
   return (long long)plan_wgrad(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw).slabs * Cout * Cin * 9 * (long long)sizeof(float);
 }
 
+extern "C" int e2e_diag_wgrad_walk(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int chunk, int tile, long long out[20]) {
+  const WgPlan pl = plan_wgrad(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw);
+  const WgParams& p = pl.p;
+  if (out == nullptr || chunk < 0 || chunk >= pl.chunks || tile < 0) return -1;
+  const bool per_item = p.segs > 0;
+  long long lo, hi;                 // global tile indices
+  if (per_item) {
+    const WgItemTiles t = e2e::chunk_tiles_per_item(p, chunk);
+    lo = (long long)t.n * p.tiles_per_n + t.lo;
+    hi = (long long)t.n * p.tiles_per_n + t.hi;
+  } else {
+    const WgTiles t = e2e::chunk_tiles(p, chunk);
+    lo = t.lo; hi = t.hi;
+  }
+  if (lo + tile >= hi) return -1;
+  const WgOrigin first = e2e::tile_origin(p, lo, pl.ts.nd, pl.ts.th, pl.ts.tw), last = e2e::tile_origin(p, hi - 1, pl.ts.nd, pl.ts.th, pl.ts.tw);
+  // the kernels of the per-item walk decode the index inside their item; both forms must name the same tile
+  const WgOrigin to = per_item ? e2e::tile_origin_in_item(p, first.n, (int)(lo + tile - (long long)first.n * p.tiles_per_n), pl.ts.nd, pl.ts.th, pl.ts.tw)
+                               : e2e::tile_origin(p, lo + tile, pl.ts.nd, pl.ts.th, pl.ts.tw);
+  const long long v[20] = {pl.chunks, pl.pairs, pl.slabs, per_item, p.tiles_per_n, p.total_tiles, lo, hi, first.n, last.n,
+                           e2e::wg_slab_index(chunk, 0, pl.slabs_per_wg), e2e::wg_slab_index(chunk, pl.slabs_per_wg - 1, pl.slabs_per_wg),
+                           to.n, to.d0, to.h0, to.w0, pl.ts.nd, pl.ts.th, pl.ts.tw, pl.slabs_per_wg};
+  for (int i = 0; i < 20; ++i) out[i] = v[i];
+  return pl.path;
+}
+
 extern "C" int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, float* dw, void* ws, int B, int Cin,
                                  int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, const unsigned* dy_absmax,
                                  const unsigned* x_absmax, void* stream) {
@@ -1203,17 +1073,11 @@ extern "C" int e2e_conv133_wgrad(const e2e_in_chan_t* chans, const float* dy, fl
       hipLaunchKernelGGL(conv133_wgrad_smallc_kernel, grid, dim3(256), 0, st, p);
       break;
     case WG_BF3:
-    case WG_BF3_W16: {
-      e2e::WgBf3Params q{};
-      q.chans = chans; q.dy = dy; q.slab = p.slab;
-      q.B = B; q.Cin = Cin; q.Cout = Cout; q.Di = Di; q.Hi = Hi; q.Wi = Wi; q.Do = p.Do; q.sd = sd;
-      q.tiles_x = p.tiles_x; q.tiles_y = p.tiles_y; q.tiles_per_n = p.tiles_per_n; q.tiles_per_chunk = p.tiles_per_chunk;
-      q.segs = p.cblocks_segs; q.cblocks = p.cblocks; q.geom = pl.geom;
-      q.h2 = wg_h2_env() && dy_absmax != nullptr; q.dy_absmax = dy_absmax; q.x_absmax = x_absmax;
-      e2e::note_kernel("conv133_wgrad_%s%s chunks=%d pairs=%d", q.h2 ? "h2" : "bf3", pl.geom ? "w16" : "", pl.chunks, pl.pairs);
-      rc = e2e::launch_wgrad_bf3(q, pl.chunks, pl.pairs, st);
+    case WG_BF3_W16:
+      p.h2 = wg_h2_env() && dy_absmax != nullptr; p.dy_absmax = dy_absmax; p.x_absmax = x_absmax;
+      e2e::note_kernel("conv133_wgrad_%s%s chunks=%d pairs=%d", p.h2 ? "h2" : "bf3", p.geom ? "w16" : "", pl.chunks, pl.pairs);
+      rc = e2e::launch_wgrad_bf3(p, pl.chunks, pl.pairs, st);
       break;
-    }
     case WG_V3:
       e2e::note_kernel("conv133_wgrad_v3<%s> chunks=%d pairs=%d", pl.v3 == V3_KSPLIT ? "1,1,2" : (pl.v3 == V3_WIDE_OUT ? "1,2,1" : "2,1,1"), pl.chunks, pl.pairs);
       if (pl.v3 == V3_KSPLIT) hipLaunchKernelGGL((conv133_wgrad_v3_kernel<1, 1, 2>), grid, dim3(512), 0, st, p);

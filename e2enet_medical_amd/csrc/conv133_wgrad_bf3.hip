@@ -26,9 +26,7 @@
 // History: v1 (16x16x32 MFMA, eight waves), v2 (twelve waves that stage and multiply in lockstep) and v4 (four matrix waves + four
 // staging waves) were measured against this form in rounds 3 / 4 (profiles/r04_kbench.txt, r04_pmc_sq_bf3.txt: 0.905 / 0.865 /
 // 0.83 ms on 64 -> 32 @128^3 x 2) and removed in round 5; what is left is v5 in two operand formats (NPC below).
-#include "e2e_common.h"
-#include "e2e_split.h"
-#include "e2e_concat.h"
+#include "e2e_wgrad.h"
 #include <cstdlib>
 
 // raw buffer loads (the clang builtin __builtin_amdgcn_raw_buffer_load_b128 of this toolchain lowers to a splatted dword load)
@@ -109,7 +107,7 @@ static_assert(XROWS * XROWB + 16 == CSTR2 && TH * YROWB + 16 == CSTR2 && (CSTR2 
 //        (scale, shift) pair; the slab is un-scaled on store.
 __device__ unsigned long long g_wg_clock[2];     // as g_mm_clock (conv133_mm.hip)
 template <int G, int NPC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv133_wgrad_bf3v5_kernel(e2e::WgBf3Params p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv133_wgrad_bf3v5_kernel(WgParams p) {
   constexpr int XBn = NPC * SSTR2, BUFn = 2 * XBn;          // input image, one (input + dy) image
   static_assert(2 * 144 * 64 * 4 <= 2 * BUFn, "the reduction regions fit the images");
   constexpr int GTH = G ? 8 : 4, GTW = G ? 16 : 32;         // tile
@@ -118,15 +116,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   constexpr int GXROWB = G ? 32 : 64, GYROWB = G ? 48 : 96; // bytes per staged input / dy row
   static_assert((GTH + 2) * GXROWB + 16 <= CSTR2 && GTH * GYROWB + 16 <= CSTR2, "channel stride");
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUFn];
-  const int segs = p.segs;
-  const int n = blockIdx.x / segs, seg = blockIdx.x - n * segs;
+  const WgItemTiles tiles = chunk_tiles_per_item(p, blockIdx.x);
+  const int n = tiles.n, tile_lo = tiles.lo;
   const int cg = blockIdx.y % p.cblocks, ob = blockIdx.y / p.cblocks;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile_lo = seg * p.tiles_per_chunk;
-  int tile_hi = tile_lo + p.tiles_per_chunk;
-  if (tile_hi > p.tiles_per_n) tile_hi = p.tiles_per_n;
-  const int ntiles = tile_hi - tile_lo;
+  const int ntiles = tiles.hi - tiles.lo;
   const unsigned long long clk_c0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
   f32x16_t acc[9];
 #pragma unroll
@@ -157,9 +152,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int item = j * 64 + lane;
       const int chl = item / XIT, rem = item - chl * XIT;
       const int x_r = rem >> XQS, x_q = rem & ((1 << XQS) - 1);
-      const int c = cbase + sw * 8 + chl;
-      const bool val = c < p.Cin;
-      const ConcatChan chd = concat_chan(p.chans[val ? c : 0], n);
+      bool val;
+      const ConcatChan chd = concat_chan_or_first(p.chans, cbase + sw * 8 + chl, p.Cin, n, val);
       xdsh[j] = val ? chd.dshift : (1 << 30);                  // (absent channel: no depth is in range)
       xbase[j] = (gfloat_p)chd.base;
       xa[j] = chd.a; xb[j] = chd.b; xsl[j] = chd.slope;
@@ -436,7 +430,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   __syncthreads();
   if (wave == 0) {
     add(0);
-    float* sp = p.slab + (long long)blockIdx.x * p.Cout * p.Cin * 9;
+    float* sp = wg_slab(p, wg_slab_index(blockIdx.x, 0, 1));
     const int c = cg * 32 + (lane & 31);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -538,7 +532,7 @@ extern "C" int e2e_diag_split_gemm(const float* A, const float* Bt, float* D, in
 
 namespace e2e {
 
-int launch_wgrad_bf3(const WgBf3Params& p, int nchunks, int pairs, hipStream_t st) {
+int launch_wgrad_bf3(const WgParams& p, int nchunks, int pairs, hipStream_t st) {
   // the caller checked: 32-bit element offsets inside one batch item's channel block / dy block
   if (p.geom == 1) {                                         // 8 x 16 tiles (planes 16..31 wide)
     if (p.h2) {

@@ -15,6 +15,7 @@
 // The gradient GEMMs take their dy addresses from DyTile.
 #include "e2e_common.h"
 #include "e2e_split.h"
+#include "e2e_wgrad.h"
 #include <cstdlib>
 #include <type_traits>
 

@@ -115,48 +115,4 @@ inline void zero_async(void* p, size_t bytes, hipStream_t st) {
   hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (unsigned*)p, n);
 }
 
-// conv133_wgrad_bf3.hip: dense weight gradient on the bf16 matrix pipe with fp32-exact (three-piece) operands; planned and
-// dispatched by e2e_conv133_wgrad (conv133_wgrad.hip)
-struct WgBf3Params {
-  const e2e_in_chan_t* chans;
-  const float* dy;
-  float* slab;                 // [chunks][Cout][Cin][9]
-  int B, Cin, Cout, Di, Hi, Wi, Do, sd;
-  int tiles_x, tiles_y, tiles_per_n, tiles_per_chunk;
-  int segs;                    // chunks per batch item
-  int cblocks;                 // ceil(Cin / 32)
-  int geom;                    // 0: 4 x 32-pixel tiles, 1: 8 x 16-pixel tiles (planes 16..31 wide; v5 kernel only)
-  int h2;                      // 1: fp16 two-piece operands, three products (v5 kernel only); 0: bf16 three-piece, six products
-  const unsigned* dy_absmax;   // h2: bit pattern of max |dy| over the tensor (device; nullptr: dy is taken unscaled)
-  const unsigned* x_absmax;    // h2: bit pattern of (a bound of) max |x| over the input planes after normalise-on-load (nullptr: fixed 2^3)
-};
-int launch_wgrad_bf3(const WgBf3Params& p, int nchunks, int pairs, hipStream_t st);
-// conv133_wgrad.hip (wgrad_slab_reduce_kernel): dw[e] = sum of the nslabs slabs of numel floats, in a fixed order.  The last step of
-// every weight gradient of both conv families; call it only after the main launch passed check_launch
-int reduce_slabs(const float* slab, float* dw, long long numel, int nslabs, hipStream_t st);
-
-// Chunk arithmetic of the weight gradients (a workgroup walks one chunk of pixel tiles and writes one slab): `total` tiles in
-// chunks of equal size for about target_wgs workgroups over `pairs` channel-block pairs, at least min_tiles tiles per chunk
-// (every chunk is a slab the reduction has to read).  Returns the number of chunks.
-inline int split_tiles(long long total, int pairs, int target_wgs, int min_tiles, int* tiles_per_chunk) {
-  long long want = target_wgs / (pairs > 0 ? pairs : 1);
-  if (want < 1) want = 1;
-  long long tpc = cdivll(total, want);
-  if (tpc < min_tiles) tpc = min_tiles;
-  if (tpc > total) tpc = total;
-  *tiles_per_chunk = (int)tpc;
-  return (int)cdivll(total, tpc);
-}
-// The same where chunks never cross a batch item: `*segs` runs of *tiles_per_chunk tiles per item; returns segs * B chunks.
-inline int split_tiles_per_item(int tiles_per_n, int B, int pairs, int target_wgs, int min_tiles, int* tiles_per_chunk, int* segs) {
-  long long want = target_wgs / (pairs > 0 ? pairs : 1);
-  if (want < B) want = B;
-  int tpc = cdiv(tiles_per_n, (int)(want / B));
-  if (tpc < min_tiles) tpc = min_tiles;
-  if (tpc > tiles_per_n) tpc = tiles_per_n;
-  *tiles_per_chunk = tpc;
-  *segs = cdiv(tiles_per_n, tpc);
-  return *segs * B;
-}
-
 }  // namespace e2e

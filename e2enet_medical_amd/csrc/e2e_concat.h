@@ -1,8 +1,8 @@
 // The plane addressing of the virtual concat (include/e2e_hip.h: e2e_in_chan_t, e2e_out_chan_t): what a depth shift does to a
 // load and to a store, and who zero-fills.  Every 1x3x3 conv kernel that reads or writes through those tables takes the
 // arithmetic from here (K1 conv133.hip, K1s conv133_sparse.hip, K1m conv133_mm.hip, conv133_dense.hip, the weight gradients
-// conv133_wgrad.hip and conv133_wgrad_bf3.hip); storage (scalar registers, LDS tables), the substitute for a channel beyond Cin
-// and any pre-scaling stay with the kernels.  The host reaches the store rule through e2e_diag_concat_slice
+// conv133_wgrad.hip and conv133_wgrad_bf3.hip); storage (scalar registers, LDS tables) and any pre-scaling stay with the
+// kernels.  The host reaches the store rule through e2e_diag_concat_slice
 // (tests/test_host_cpu.py::test_concat_store_slices_partition_the_volume).
 #pragma once
 #include "e2e_common.h"
@@ -31,6 +31,13 @@ __device__ __forceinline__ ConcatChan concat_chan(const e2e_in_chan_t& ch, int n
     r.slope = ch.slope;
   }
   return r;
+}
+
+// A kernel that stages whole blocks of channels meets channels beyond Cin.  They resolve to channel 0, which is always
+// dereferenceable, with valid = false; the caller masks every element it stages from such a channel.
+__device__ __forceinline__ ConcatChan concat_chan_or_first(const e2e_in_chan_t* chans, int c, int Cin, int n, bool& valid) {
+  valid = c < Cin;
+  return concat_chan(chans[valid ? c : 0], n);
 }
 
 // the source slice behind depth d; takes the shift, not the table entry, so that a kernel which keeps resolved channels in a

@@ -254,6 +254,15 @@ int e2e_diag_split_gemm(const float* A, const float* Bt, float* D, int K, int mo
  * receives nothing and this launch is the buffer's first writer), 3 skip (it receives nothing and holds earlier writers' values). */
 int e2e_diag_concat_slice(int d, int dshift, int D, int accumulate, int* dd);
 
+/* Diagnostic, host only (no GPU call): the tile walk and slab layout of e2e_conv133_wgrad for a shape, through the plan the size
+ * query and the launch share and the functions the kernels walk with (csrc/e2e_wgrad.h).  For workgroup column `chunk` of the
+ * launch grid and the `tile`-th tile it walks: out[0..19] = chunks, pairs (the launch grid), slabs (what e2e_conv133_wgrad_ws_bytes
+ * counts), 1 if chunks never cross a batch item else 0, tiles per batch item, tiles in all, the chunk's tile range [lo, hi) as indices
+ * over all tiles, the batch items of its first and last tile, the first and last slab its workgroups write, the tile's batch item and
+ * origin (n, d0, h0, w0) in the output volume, the tile's extent (nd, th, tw), slabs per workgroup.  Returns the path (0 s2, 1 smallc,
+ * 2 split-operand on 4 x 32 tiles, 3 v3, 4 split-operand on 8 x 16 tiles, 5 v2, 6 v1), or -1 when chunk or tile is out of range. */
+int e2e_diag_wgrad_walk(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int chunk, int tile, long long out[20]);
+
 /* Diagnostic: the shader clock the hot kernels ran at.  Workgroup 0 of every launch of family 0 (K1m, conv133_mm) / 1 (the
  * matrix-pipe K1w, conv133_wgrad v5) adds its s_memtime span (shader-clock cycles) and its s_memrealtime span (100 MHz) to a
  * device-side pair; this call synchronises the device and returns *mhz = cycles / time over all launches since the last reset

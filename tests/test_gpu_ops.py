@@ -96,6 +96,8 @@ CONV_CASES = [
     (1, [(40, True)], 34, (1, 32, 32), (1, 1, 1), 1.0),                      # conv133_mm (conv133_dense under E2E_CONV_MM=0): one tile row pair, every shifted group vanishes
     (2, [(20, True), (13, False)], 34, (1, 20, 36), (1, 1, 1), 0.25),        # conv133_sparse: one slice, ragged tiles, two sources
     (1, [(20, True), (13, False)], 34, (2, 20, 36), (1, 1, 1), 0.25),        # conv133_sparse, D = 2: groups +-1 partly survive, groups +-2 vanish
+    # pipelined s2 weight gradient whose second chunk crosses the batch items (9 tiles per item in chunks of 8): descriptors reloaded
+    (2, [(20, True), (15, False)], 40, (6, 24, 32), (2, 2, 2), 1.0),
 ]
 
 
@@ -651,6 +653,7 @@ WGRAD_WS_CASES = [
     ("convT", 2, 40, 24, (4, 8, 8), (2, 2, 2), _CT_SPLIT, _CT_SPLIT),
     ("convT", 1, 9, 5, (3, 6, 8), (2, 2, 1), "convT_wgrad_v1<4> ", "convT_wgrad_v1<4> "),        # kw == 1
     ("convT", 2, 40, 33, (3, 5, 7), (2, 2, 2), "convT_wgrad_v1<8> ", "convT_wgrad_v1<8> "),      # odd W
+    ("conv", 2, 35, 40, (6, 24, 32), (2, 2, 2), "conv133_wgrad_s2 ", "conv133_wgrad_s2 "),     # second chunk spans both batch items
 ]
 
 

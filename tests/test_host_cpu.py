@@ -856,3 +856,102 @@ def test_concat_store_slices_partition_the_volume():
                         assert action == (SKIP if accumulate else ZERO_FILL), ctx
                     named.append(dd)
                 assert sorted(named) == list(range(D)), (D, dshift, accumulate, named)
+
+
+# ---- the tile walk and slab layout of the conv weight gradient (csrc/e2e_wgrad.h), through e2e_diag_wgrad_walk -----------------
+WG_PATHS = {0: "s2", 1: "smallc", 2: "split 4x32", 3: "v3", 4: "split 8x16", 5: "v2", 6: "v1"}
+WG_S2_CROSSING = (2, 35, 40, (6, 24, 32), (2, 2, 2))    # 9 tiles per item in chunks of 8: the second chunk spans both items
+# (B, Cin, Cout, (D, H, W), stride): B = 2 and ragged last tiles in every direction the path's tile has, one per path and v3 form
+WG_WALK_RAGGED = [
+    (2, 35, 40, (5, 22, 40), (2, 2, 2)),      # s2: 11 x 20 output planes on 4 x 16 tiles
+    (2, 3, 40, (3, 21, 36), (1, 1, 1)),       # smallc: 8 x 32 tiles
+    (2, 40, 40, (3, 21, 36), (1, 1, 1)),      # split operands on 4 x 32 tiles | v3<2,1,1>
+    (2, 40, 64, (3, 21, 36), (1, 1, 1)),      # the same | v3<1,2,1>
+    (2, 20, 24, (3, 21, 36), (1, 1, 1)),      # the same | v3<1,1,2>: two slabs per workgroup
+    (2, 40, 33, (3, 13, 20), (1, 1, 1)),      # split operands on 8 x 16 tiles | v2<1,16,16,2>
+    (2, 40, 33, (3, 13, 12), (1, 1, 1)),      # v2<1,16,16,2>
+    (2, 40, 33, (5, 7, 8), (1, 1, 1)),        # v2<4,8,8,1>: ragged in depth too
+    (2, 13, 9, (5, 9, 11), (1, 1, 1)),        # v1, stride 1
+    (2, 10, 12, (5, 11, 9), (2, 2, 2)),       # v1, strided: 6 x 5 output planes on 2 x 8 x 8 tiles
+    (2, 9, 5, (17, 4, 3), (1, 1, 1)),         # v1 on 16 x 4 x 4 tiles
+]
+
+
+def _wgrad_walk(rows):
+    """every chunk and tile of the launch of each row, as e2e_diag_wgrad_walk reports them (the plan reads E2E_WG_BF3 once per
+    process: the test calls this in child processes)"""
+    import ctypes
+    from e2enet_medical_amd._lib import lib
+    L = lib()
+    res = []
+    for B, cin, cout, dims, stride in rows:
+        out = (ctypes.c_longlong * 20)()
+        shape = (B, cin, cout) + tuple(dims) + tuple(stride)
+        path = L.diag_wgrad_walk(*shape, 0, 0, out)
+        rec = {"path": path, "chunks": out[0], "pairs": out[1], "slabs": out[2], "per_item": out[3], "tiles_per_n": out[4],
+               "total_tiles": out[5], "tile": list(out[16:19]), "slabs_per_wg": out[19],
+               "ws_bytes": L.conv133_wgrad_ws_bytes(*shape), "walk": []}
+        for chunk in range(rec["chunks"]):
+            assert L.diag_wgrad_walk(*shape, chunk, 0, out) == path, "chunk %d of %s walks no tile" % (chunk, shape)
+            c = {"lo": out[6], "hi": out[7], "n": [out[8], out[9]], "slab": [out[10], out[11]], "origins": []}
+            for t in range(c["hi"] - c["lo"]):
+                assert L.diag_wgrad_walk(*shape, chunk, t, out) == path
+                c["origins"].append(list(out[12:16]))
+            assert L.diag_wgrad_walk(*shape, chunk, c["hi"] - c["lo"], out) == -1
+            rec["walk"].append(c)
+        assert L.diag_wgrad_walk(*shape, rec["chunks"], 0, out) == -1
+        res.append(rec)
+    return res
+
+
+def test_wgrad_chunks_partition_the_tiles_and_the_slabs():
+    """e2e_conv133_wgrad takes a bare workspace pointer; what keeps its kernels inside it is csrc/e2e_wgrad.h: the host cuts the
+    tiles into chunks, the workgroup of a chunk walks a tile range and writes slabs, and the size query counts those slabs, all
+    through one set of functions.  Over the conv rows of the GPU workspace test, the s2 shape whose chunk crosses a batch item
+    and one ragged two-item shape per path, with the split-operand kernels on and off (E2E_WG_BF3, read once per process: child
+    processes): the chunks' tile ranges are disjoint and cover every tile once, every tile origin lies in the output volume and
+    the origins are exactly the tile grid of every batch item, no chunk of a per-item path crosses an item, the workgroups'
+    slabs are distinct and the largest index is slabs - 1, and the queried bytes are slabs * Cout * Cin * 9 floats."""
+    import itertools
+    import json
+    from tests.test_gpu_ops import WGRAD_WS_CASES
+    rows = [list(c[1:6]) for c in WGRAD_WS_CASES if c[0] == "conv"]
+    assert len(rows) >= 12 and list(WG_S2_CROSSING) in [[r[0], r[1], r[2], tuple(r[3]), tuple(r[4])] for r in rows]
+    rows += [list(r) for r in WG_WALK_RAGGED]
+    seen = set()
+    for bf3 in ("1", "0"):
+        env = {k: v for k, v in os.environ.items() if k != "E2E_WG_BF3"}
+        if bf3 == "0":
+            env["E2E_WG_BF3"] = "0"
+        r = subprocess.run([sys.executable, "-c", "import json, sys; from tests.test_host_cpu import _wgrad_walk; "
+                            "print('WALK ' + json.dumps(_wgrad_walk(json.loads(sys.argv[1]))))", json.dumps(rows)],
+                           env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        recs = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("WALK ")][-1][5:])
+        assert len(recs) == len(rows)
+        for (B, cin, cout, dims, stride), rec in zip(rows, recs):
+            ctx = (bf3, B, cin, cout, dims, stride, WG_PATHS[rec["path"]])
+            seen.add(rec["path"])
+            Do, Ho, Wo = [(d - 1) // s + 1 for d, s in zip(dims, stride)]
+            nd, th, tw = rec["tile"]
+            grid = set(itertools.product(range(B), range(0, Do, nd), range(0, Ho, th), range(0, Wo, tw)))
+            assert rec["total_tiles"] == len(grid) == B * rec["tiles_per_n"], ctx
+            walk = sorted(rec["walk"], key=lambda c: c["lo"])
+            assert len(walk) == rec["chunks"] and walk[0]["lo"] == 0 and walk[-1]["hi"] == rec["total_tiles"], ctx
+            assert all(a["lo"] < a["hi"] for a in walk) and all(a["hi"] == b["lo"] for a, b in zip(walk, walk[1:])), ctx
+            origins = [tuple(o) for c in walk for o in c["origins"]]
+            assert len(origins) == len(grid) and set(origins) == grid, ctx      # (inside the volume: the grid is)
+            for c in walk:
+                assert [o[0] for o in c["origins"]] == sorted(o[0] for o in c["origins"]) and \
+                    [c["origins"][0][0], c["origins"][-1][0]] == c["n"], ctx
+                if rec["per_item"]:
+                    assert c["n"][0] == c["n"][1], ctx
+            slabs = [s for c in rec["walk"] for s in range(c["slab"][0], c["slab"][1] + 1)]
+            assert all(c["slab"][1] - c["slab"][0] + 1 == rec["slabs_per_wg"] for c in rec["walk"]), ctx
+            assert sorted(slabs) == list(range(rec["slabs"])) and max(slabs) == rec["slabs"] - 1, ctx
+            assert rec["ws_bytes"] == rec["slabs"] * cout * cin * 9 * 4, ctx
+            if (B, cin, cout, tuple(dims), tuple(stride)) == WG_S2_CROSSING:
+                assert rec["path"] == 0 and any(c["n"][0] != c["n"][1] for c in walk), ("no chunk crosses the batch items", ctx, walk)
+            if rec["path"] == 1 or (rec["path"] == 3 and cin <= 32 and cout <= 32):
+                assert rec["slabs_per_wg"] == 2, ctx
+    assert seen == set(WG_PATHS), seen
