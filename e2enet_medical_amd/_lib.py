@@ -248,6 +248,15 @@ SIGNATURES = {
     "e2e_deflate_slot_bytes": (I, []),
     "e2e_deflate_encode": (I, [P, LL, I, P, P, P, P, P]),
     "e2e_deflate_gather": (I, [P, P, P, LL, P, LL, P]),
+    "e2e_resample_argmax_u8": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, P]),
+    "e2e_seg_onehot": (I, [P, P, P, I, I, I, I, I, I, LL, P]),
+    "e2e_morph_max_footprint": (I, []),
+    "e2e_morph_bits_words": (LL, [I, I, I]),
+    "e2e_morph_pack": (I, [P, P, I, I, I, P]),
+    "e2e_morph_pass": (I, [P, P, I, I, I, P, I, I, I, I, P]),
+    "e2e_morph_unpack": (I, [P, P, I, I, P, I, I, I, I, P]),
+    "e2e_rcc_ws_bytes": (LL, [I, I, I]),
+    "e2e_rcc_remove": (I, [P, P, I, I, I, C.c_double, C.c_double, P, P, P]),
 }
 
 _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv133_num_partials", "e2e_conv133_wgrad_ws_bytes", "e2e_conv133_dense_ws_bytes", "e2e_conv133_mm_ws_bytes", "e2e_conv133_sparse_eligible", "e2e_conv133_sparse_wpk_floats", "e2e_maxpool_bwd_num_records", "e2e_conv133_fwd_ws_bytes", "e2e_conv133_dgrad_ws_bytes",
@@ -257,7 +266,8 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
               "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
               "e2e_loader_crop_max_batch", "e2e_nifti_scan_grid_voxels", "e2e_deflate_chunk_bytes", "e2e_deflate_slot_bytes",
-              "e2e_diag_concat_slice", "e2e_diag_wgrad_walk"}
+              "e2e_diag_concat_slice", "e2e_diag_wgrad_walk",
+              "e2e_morph_max_footprint", "e2e_morph_bits_words", "e2e_rcc_ws_bytes"}
 
 
 class E2EError(RuntimeError):
@@ -295,7 +305,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 30          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 31          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -25,12 +25,53 @@ __device__ __forceinline__ void lin_coord(int o, int n_in, int n_out, int& i0, i
   t = c - f;
   i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
 }
+// The 2 x 2 x 2 taps of one output voxel of the order-1 resize (sliding.hip's resample_linear, cascade.hip's fused argmax): set up
+// once per voxel, evaluated once per class.  lowres = 0..2 picks that axis by nearest neighbour, -1 interpolates all three; an axis
+// whose size does not change has coordinate o exactly (weight 1 on tap 0).
+struct Lin3 {
+  int i0[3], i1[3];
+  double w0[3], w1[3];
+};
+__device__ __forceinline__ void lin3_setup(Lin3& L, const int (&o)[3], const int (&n_in)[3], const int (&n_out)[3], int lowres);
+// the value at the voxel: taps visited last axis fastest, the coefficient multiplied by the axis weights in axis order and added to
+// a double sum (scipy's NI_ZoomShift; the including file is built with -ffp-contract=off), cast to float32
+__device__ __forceinline__ float lin3_eval(const Lin3& L, const float* __restrict__ sp, const long long (&st)[3]) {
+  double acc = 0.0;
+#pragma unroll
+  for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+    for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+      for (int tc = 0; tc < 2; ++tc) {
+        const double wa = ta ? L.w1[0] : L.w0[0], wb = tb ? L.w1[1] : L.w0[1], wc = tc ? L.w1[2] : L.w0[2];
+        if (wa == 0.0 || wb == 0.0 || wc == 0.0) continue;       // (taps scipy does not visit: nearest axis, unchanged axis)
+        double coeff = (double)sp[(ta ? L.i1[0] : L.i0[0]) * st[0] + (tb ? L.i1[1] : L.i0[1]) * st[1] + (tc ? L.i1[2] : L.i0[2]) * st[2]];
+        coeff *= wa;
+        coeff *= wb;
+        coeff *= wc;
+        acc += coeff;
+      }
+  return (float)acc;
+}
 // order 0 (map_coordinates(order=0, mode='nearest')): floor(c + 0.5) of the clamped coordinate
 __device__ __forceinline__ int near_coord(int o, int n_in, int n_out) {
   double c = ((double)n_in / (double)n_out) * ((double)o + 0.5) - 0.5;
   if (c < 0.0) c = 0.0;
   if (c > (double)(n_in - 1)) c = (double)(n_in - 1);
   return (int)floor(c + 0.5);
+}
+__device__ __forceinline__ void lin3_setup(Lin3& L, const int (&o)[3], const int (&n_in)[3], const int (&n_out)[3], int lowres) {
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (d == lowres || n_in[d] == n_out[d]) {
+      L.i0[d] = L.i1[d] = (d == lowres) ? near_coord(o[d], n_in[d], n_out[d]) : o[d];
+      L.w0[d] = 1.0; L.w1[d] = 0.0;
+    } else {
+      double t;
+      lin_coord(o[d], n_in[d], n_out[d], L.i0[d], L.i1[d], t);
+      L.w0[d] = 1.0 - t; L.w1[d] = t;
+    }
+  }
 }
 
 }  // namespace rs

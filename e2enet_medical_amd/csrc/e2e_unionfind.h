@@ -1,11 +1,12 @@
-// Lock-free union-find over the voxels of a [D, H, W] volume, 6-neighbour connectivity: the labelling that components.hip
-// (connected components of a class set) and preprocess.hip (background components, for binary_fill_holes) share.  The mask is
-// a predicate on the flat voxel index, formed on load, so neither user materialises one for it.
+// Lock-free union-find over the voxels of a [D, H, W] volume: the 6-neighbour labelling that components.hip (connected components
+// of a class set) and preprocess.hip (background components, for binary_fill_holes) share, and its 26-neighbour form for
+// cascade.hip.  The mask is a predicate on the flat voxel index, formed on load, so no user materialises one for it.
 //
 //   init_runs   parent[i] = flat index of the first voxel of i's run of mask voxels along W (a segmented scan inside the row),
 //               NONE off the mask
 //   merge_back  every mask voxel unites with its mask neighbours at i - W and i - H W: find both roots, atomicMin(&parent[larger
 //               root], smaller root), and go on from the returned value when another thread linked that root first
+//   merge_back26  the same with the 13 neighbours that precede a voxel in raster order (full connectivity)
 //   find_root   after merge_back has run to its end (a kernel boundary), the root of i is its component's smallest voxel
 //   init_runs_labelled, merge_back_labelled (at the end of the file): the same two passes where voxels belong together only when
 //               they carry the same non-zero value, so that every class of a set is labelled at once (components.hip, P5)
@@ -122,6 +123,41 @@ __device__ __forceinline__ void merge_back(unsigned* parent, unsigned* giveup, u
   const bool left = w > 0u && parent[i - 1u] != NONE;
   if (i % HW >= W && parent[i - W] != NONE && !(left && parent[i - W - 1u] != NONE)) unite(parent, i, i - W, budget, giveup);
   if (i >= HW && parent[i - HW] != NONE && !(left && parent[i - HW - 1u] != NONE)) unite(parent, i, i - HW, budget, giveup);
+}
+
+// The 26-neighbour form of merge_back (skimage's label(), scipy's label(structure=np.ones((3, 3, 3))): cascade.hip): voxel
+// i = blockIdx.x * 256 + threadIdx.x unites with the mask voxels among the 13 neighbours that precede it in raster order.  The left
+// neighbour is implied by the run.  The other 12 lie in four rows (same plane one row back; the plane before, rows y - 1, y, y + 1),
+// at x - 1, x, x + 1 of each.  Per row:
+//   * x in the mask: x - 1 and x + 1, where in the mask, belong to x's run, so one union with x serves all three.  It is implied, and
+//     skipped, when i - 1 is in the mask: i ~ i - 1 by the run, and voxel i - 1 is a neighbour of both x - 1 and x of that row, so its
+//     own thread unites it with that run (directly, or by this rule one voxel further left; the run's first voxel has no left
+//     neighbour and always unites).
+//   * x not in the mask: x - 1 and x + 1 are separate runs.  The union with x - 1 is skipped when i - 1 is in the mask (x - 1 is the
+//     voxel straight across from i - 1: the case above for that thread); the union with x + 1 is always made.
+// find_root, unite, the invariants, the step budget and the give-up word are the ones above.
+__device__ __forceinline__ void merge_back26(unsigned* parent, unsigned* giveup, unsigned V, unsigned W, unsigned H) {
+  const unsigned long long i64 = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+  if (i64 >= V) return;
+  const unsigned i = (unsigned)i64;
+  if (parent[i] == NONE) return;                               // (NONE never changes after init)
+  unsigned budget = V + 64u;
+  const unsigned HW = H * W;
+  const unsigned x = i % W, y = i / W % H, z = i / HW;
+  const bool left = x > 0u && parent[i - 1u] != NONE;
+  for (int dz = -1; dz <= 0; ++dz) {
+    if (dz < 0 && z == 0u) continue;
+    for (int dy = -1; dy <= (dz < 0 ? 1 : -1); ++dy) {
+      if ((dy < 0 && y == 0u) || (dy > 0 && y + 1u == H)) continue;
+      const unsigned r = (unsigned)((long long)i + (long long)dz * HW + (long long)dy * W);      // (x, the row's voxel across)
+      if (parent[r] != NONE) {
+        if (!left) unite(parent, i, r, budget, giveup);
+        continue;
+      }
+      if (!left && x > 0u && parent[r - 1u] != NONE) unite(parent, i, r - 1u, budget, giveup);
+      if (x + 1u < W && parent[r + 1u] != NONE) unite(parent, i, r + 1u, budget, giveup);
+    }
+  }
 }
 
 // ---- labelled variants: every value of a class set is labelled in the same pass (the component table of components.hip) -----

@@ -182,39 +182,9 @@ __global__ __launch_bounds__(256) void resample_linear_kernel(const float* __res
   const int oa = (int)(idx / ((long long)OC * OB));
   const int n_in[3] = {A, B, C}, n_out[3] = {OA, OB, OC}, o[3] = {oa, ob, oc};
   const long long st[3] = {sa, sb, sc};
-  int i0[3], i1[3];
-  double w0[3], w1[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (d == lowres || n_in[d] == n_out[d]) {
-      // nearest along the separate axis; an axis whose size does not change has coordinate o exactly (weight 1 on tap 0)
-      i0[d] = i1[d] = (d == lowres) ? near_coord(o[d], n_in[d], n_out[d]) : o[d];
-      w0[d] = 1.0; w1[d] = 0.0;
-    } else {
-      double t;
-      lin_coord(o[d], n_in[d], n_out[d], i0[d], i1[d], t);
-      w0[d] = 1.0 - t; w1[d] = t;
-    }
-  }
-  for (int k = 0; k < K; ++k) {
-    const float* sp = src + (long long)k * kstride;
-    double acc = 0.0;
-#pragma unroll
-    for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int tc = 0; tc < 2; ++tc) {
-          const double wa = ta ? w1[0] : w0[0], wb = tb ? w1[1] : w0[1], wc = tc ? w1[2] : w0[2];
-          if (wa == 0.0 || wb == 0.0 || wc == 0.0) continue;       // (taps scipy does not visit: nearest axis, unchanged axis)
-          double coeff = (double)sp[(ta ? i1[0] : i0[0]) * st[0] + (tb ? i1[1] : i0[1]) * st[1] + (tc ? i1[2] : i0[2]) * st[2]];
-          coeff *= wa;
-          coeff *= wb;
-          coeff *= wc;
-          acc += coeff;
-        }
-    dst[(long long)k * ovol + idx] = (float)acc;
-  }
+  e2e::rs::Lin3 L;
+  e2e::rs::lin3_setup(L, o, n_in, n_out, lowres);
+  for (int k = 0; k < K; ++k) dst[(long long)k * ovol + idx] = e2e::rs::lin3_eval(L, src + (long long)k * kstride, st);
 }
 
 }  // namespace

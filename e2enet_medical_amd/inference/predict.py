@@ -250,13 +250,54 @@ def check_input_folder_and_return_caseIDs(input_folder: str, expected_num_modali
     return ids, "preprocessed"
 
 
+def default_seg_reader():
+    """``seg_reader(path_nii_gz) -> label array`` of ``predict_from_folder(lowres_segmentations=...)``: SimpleITK when importable,
+    else ``<case>.npy`` beside the requested ``.nii.gz`` path"""
+    try:
+        import SimpleITK as sitk
+    except ImportError:
+        sitk = None
+
+    def read(path):
+        if sitk is not None and os.path.isfile(path):
+            return sitk.GetArrayFromImage(sitk.ReadImage(path))
+        return np.load(path[:-7] + ".npy")
+    return read
+
+
+def append_lowres_segmentation(d, seg_prev, num_classes: int, transpose_forward: Sequence[int], original_shape=None, what: str = ""):
+    """The cascade's network input of one case (reference predict.py:52-62): ``seg_prev``, the previous stage's label volume in the
+    raw geometry, is checked against the image's array shape, transposed by ``transpose_forward``, resized to the preprocessed shape
+    ``d.shape[1:]`` with the per-label linear resize (``resize_segmentation(order=1)``, ``e2e_pp_resize_seg``) and appended to ``d``
+    [C, X, Y, Z] as ``num_classes - 1`` one-hot channels (``e2e_seg_onehot``).  Kept as the reference has it: the UNCROPPED volume is
+    resized to the cropped-and-resampled shape.  ``d``: a numpy array (a numpy array comes back) or a device tensor."""
+    from ..preprocessing.preprocessing import resample_data_or_seg
+    from ..training.data_augmentation.pyramid_augmentations import seg_onehot
+    s = torch.as_tensor(np.asarray(seg_prev.cpu()) if torch.is_tensor(seg_prev) else np.asarray(seg_prev))
+    if original_shape is not None:
+        assert all(int(i) == int(j) for i, j in zip(s.shape, original_shape)) and s.dim() == len(original_shape), \
+            "image and segmentation from previous stage don't have the same pixel array shape! image: %s, seg_prev: %s (%s)" \
+            % (tuple(int(v) for v in original_shape), tuple(s.shape), what)
+    was_numpy = not torch.is_tensor(d)
+    x = torch.as_tensor(d, dtype=torch.float32).cuda()
+    s = s.to("cuda", torch.float32).permute(*[int(i) for i in transpose_forward])
+    s = resample_data_or_seg(s[None], [int(v) for v in x.shape[1:]], is_seg=True, order=1).contiguous()
+    labels = list(range(1, int(num_classes)))
+    c = int(x.shape[0])
+    out = torch.empty((1, c + len(labels)) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    out[0, :c].copy_(x)
+    seg_onehot(s[None], 0, labels, out, c)
+    return out[0].cpu().numpy() if was_numpy else out[0]
+
+
 def predict_from_folder(model: str, input_folder: str, output_folder: str, folds: Union[Tuple[int], List[int], None],
                         save_npz: bool, num_threads_preprocessing: int, num_threads_nifti_save: int,
                         lowres_segmentations: Union[str, None], part_id: int, num_parts: int, tta: bool,
                         mixed_precision: bool = True, overwrite_existing: bool = True, mode: str = 'normal',
                         overwrite_all_in_gpu: bool = None, step_size: float = 0.5,
                         checkpoint_name: str = "model_final_checkpoint", segmentation_export_kwargs: dict = None,
-                        disable_postprocessing: bool = False, writer=None, reader=None, device_deflate: bool = False):
+                        disable_postprocessing: bool = False, writer=None, reader=None, device_deflate: bool = False,
+                        seg_reader=None):
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.
     The per-case work is ``predict_cases`` above (softmax resident in HBM).  ``num_threads_*`` are accepted and unused: there are
@@ -266,13 +307,15 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     is printed and the raw label maps are written.  A folder of raw cases (``<case>_XXXX.nii.gz``) is read through
     ``reader(list_of_files) -> (data [C, X, Y, Z], properties)`` -- default: the reference's SimpleITK loader -- and preprocessed on
     the device by ``trainer.preprocess_patient``; without a reader such a folder is refused before anything is loaded.
-    ``device_deflate`` (``simple_predict --device_deflate``): see ``predict_cases``."""
+    ``device_deflate`` (``simple_predict --device_deflate``): see ``predict_cases``.
+
+    ``lowres_segmentations`` (the cascade's second stage, reference :714-719): a folder with ``<case_id>.nii.gz`` of every case, the
+    ``3d_lowres`` model's prediction in the raw geometry, read through ``seg_reader(path) -> label array`` (default: SimpleITK, else
+    ``<case_id>.npy`` of the same stem) and appended to the case as one-hot channels (``append_lowres_segmentation``)."""
     import shutil
     from ..training.model_restore import load_model_and_checkpoint_files
     if mode != "normal":
         raise NotImplementedError("mode=%r: the engine implements the reference's 'normal' mode (predict.py:729-737)" % (mode,))
-    if lowres_segmentations is not None:
-        raise NotImplementedError("cascade inputs (lowres_segmentations) are outside the shiftConvPP hot path")
     os.makedirs(output_folder, exist_ok=True)
     assert os.path.isfile(os.path.join(model, "plans.pkl")), "Folder with saved model weights must contain a plans.pkl file"
     shutil.copy(os.path.join(model, 'plans.pkl'), output_folder)
@@ -282,12 +325,21 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
     if layout == "nifti":
         from ..preprocessing.cropping import require_reader
         reader = require_reader(reader, "predict_from_folder(%s: raw cases, <case>_XXXX.nii.gz)" % input_folder)
+    lowres_files = None
+    if lowres_segmentations is not None:
+        assert os.path.isdir(lowres_segmentations), "if lowres_segmentations is not None then it must point to a directory"
+        lowres_files = [os.path.join(lowres_segmentations, i + ".nii.gz") for i in case_ids]
+        assert all([os.path.isfile(i) or os.path.isfile(i[:-7] + ".npy") for i in lowres_files]), \
+            "not all lowres_segmentations files are present. (I was searching for case_id.nii.gz in that folder)"
+        lowres_files = lowres_files[part_id::num_parts]
+        seg_reader = default_seg_reader() if seg_reader is None else seg_reader
     case_ids = case_ids[part_id::num_parts]
     output_files = [os.path.join(output_folder, c + ".nii.gz") for c in case_ids]
     if not overwrite_existing:
         keep = [i for i, o in enumerate(output_files) if not (os.path.isfile(o) or os.path.isfile(o[:-7] + ".npy"))
                 or (save_npz and not os.path.isfile(o[:-7] + ".npz"))]          # (predict.py:233-234)
         case_ids, output_files = [case_ids[i] for i in keep], [output_files[i] for i in keep]
+        lowres_files = [lowres_files[i] for i in keep] if lowres_files is not None else None
     print("number of cases that still need to be predicted:", len(case_ids))
     if not case_ids:
         return []
@@ -306,19 +358,25 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
                   "consolidate_folds in the output folder of the model first!\nThe folder you need to run this in is "
                   "%s\n(python -m e2enet_medical_amd.postprocessing.consolidate_postprocessing -f %s)" % (model, model))
 
+    def with_lowres(i, d, props):
+        if lowres_files is None:
+            return d
+        return append_lowres_segmentation(d, seg_reader(lowres_files[i]), trainer.num_classes, trainer.plans['transpose_forward'],
+                                          props.get('original_size_of_raw_data'), lowres_files[i])
+
     def cases():
-        for c, out in zip(case_ids, output_files):
+        for i, (c, out) in enumerate(zip(case_ids, output_files)):
             if layout == "nifti":
                 files = [os.path.join(input_folder, c + "_%04.0d.nii.gz" % n) for n in range(expected_num_modalities)]
                 d, _, props = trainer.preprocess_patient(files, reader=reader)
-                yield out, (d, props)
+                yield out, (with_lowres(i, d, props), props)
                 continue
             npy, npz = os.path.join(input_folder, c + ".npy"), os.path.join(input_folder, c + ".npz")
             d = np.load(npy) if os.path.isfile(npy) else np.load(npz)['data']
             with open(os.path.join(input_folder, c + ".pkl"), 'rb') as f:
                 props = pickle.load(f)
             d = np.asarray(d)[:expected_num_modalities]          # (preprocessed training cases carry their labels as a last channel)
-            yield out, (d, props)
+            yield out, (with_lowres(i, d, props), props)
     return predict_cases(trainer, params, cases(), writer if writer is not None else nifti_writer(), do_tta=tta,
                          step_size=step_size, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision, postprocessing=postprocessing,
                          save_npz=save_npz, device_deflate=device_deflate)

@@ -9,8 +9,10 @@ optimizer state from the checkpoint (the reference re-draws the masks before loa
 is an extension (the reference hard-codes 48, nnUNetTrainer_simple.py:296); ``--synthetic_data`` trains on seeded noise when no
 preprocessed data exists (benchmarks / smoke tests); ``--resident_data GIB`` keeps the preprocessed cases on the device and cuts the
 training batches there; ``--validation_only`` really validates (the reference's call is commented out,
-:200-208); ``--find_lr`` and the 3d_lowres cascade hand-over are outside the engine."""
+:200-208); after a ``3d_lowres`` run the validation cases are predicted for the cascade's next stage
+(``training/cascade_stuff/predict_next_stage.py``) unless ``--disable_next_stage_pred``; ``--find_lr`` is outside the engine."""
 import argparse
+import os
 
 import torch
 
@@ -83,11 +85,16 @@ def select_validation_callbacks(args):
 
 def select_trainer_class(network_trainer):
     """the reference forces nnUNetTrainer_simple whatever --network_trainer says (simple_main.py:145); the one other trainer of
-    this package, the region trainer nnUNetTrainerV2BraTSRegions, is selected by its name"""
+    other trainers of this package, the region trainer nnUNetTrainerV2BraTSRegions and the cascade's second stage
+    nnUNetTrainerV2CascadeFullRes, are selected by their names.  ``3d_cascade_fullres`` with any other name trains the last stage
+    without the previous stage's segmentation, as the reference's simple_main does."""
     if network_trainer == 'nnUNetTrainerV2BraTSRegions':
         from .training.network_training.competitions_with_custom_Trainers.BraTS2020.nnUNetTrainerV2BraTSRegions import \
             nnUNetTrainerV2BraTSRegions
         return nnUNetTrainerV2BraTSRegions
+    if network_trainer == 'nnUNetTrainerV2CascadeFullRes':
+        from .training.network_training.nnUNetTrainerV2CascadeFullRes import nnUNetTrainerV2CascadeFullRes
+        return nnUNetTrainerV2CascadeFullRes
     return nnUNetTrainer_simple
 
 
@@ -166,7 +173,10 @@ def main(argv=None):
                          device_deflate=args.device_deflate)
     print(f'finish training {args.Tconv} !!!')
     if network == '3d_lowres' and not args.disable_next_stage_pred:
-        raise NotImplementedError("predict_next_stage (3d_lowres cascade) is outside the shiftConvPP hot path")
+        # reference :213-215: the validation cases of this fold, predicted and resampled for the full-resolution stage
+        from .training.cascade_stuff.predict_next_stage import predict_next_stage
+        print("predicting segmentations for the next stage of the cascade")
+        predict_next_stage(trainer, os.path.join(dataset_directory, trainer.plans['data_identifier'] + "_stage%d" % 1))
     return trainer
 
 

@@ -2,7 +2,9 @@
 engine: the same argv; the checkpoint name is prefixed with ``--Tconv`` (:152) and ``predict_from_folder`` runs the cases
 ``[part_id::num_parts]`` (one process per GPU; within a process ``SegmentationNetwork.shard_tiles`` can split the tiles of a case
 over a process group instead).  The input folder holds preprocessed cases (``<case>.npz|.npy`` + ``<case>.pkl``) or raw cases
-(``<case>_XXXX.nii.gz``); raw cases are read by a ``reader`` callback (default: SimpleITK) and preprocessed on the device."""
+(``<case>_XXXX.nii.gz``); raw cases are read by a ``reader`` callback (default: SimpleITK) and preprocessed on the device.
+``-m 3d_cascade_fullres`` picks the model of ``-ctr`` and reads the first stage's segmentations from ``-l``; without ``-l`` the
+``3d_lowres`` model predicts the input folder into ``<output>/3d_lowres_predictions`` first (reference :192-216)."""
 import argparse
 import os
 
@@ -74,9 +76,26 @@ def main(argv=None, reader=None, writer=None):
         raise ValueError("Unexpected value for argument folds")
     assert all_in_gpu in ['None', 'False', 'True']
     all_in_gpu = {"None": None, "True": True, "False": False}[all_in_gpu]
-    if model == "3d_cascade_fullres":
-        raise NotImplementedError("the 3d_cascade_fullres model is outside the shiftConvPP hot path")
-    model_folder_name = join(paths.network_training_output_dir, model, task_name, args.trainer_class_name + "__" + args.plans_identifier)
+    seg_reader = nifti.gt_reader if args.native_nifti else None
+    if model == "3d_cascade_fullres" and lowres_segmentations is None:
+        # reference :192-210: the first stage's predictions of the same input folder, into <output>/3d_lowres_predictions
+        print("lowres_segmentations is None. Attempting to predict 3d_lowres first...")
+        assert args.part_id == 0 and args.num_parts == 1, "if you don't specify a --lowres_segmentations folder for the " \
+                                                          "inference of the cascade, custom values for part_id and num_parts " \
+                                                          "are not supported. If you wish to have multiple parts, please " \
+                                                          "run the 3d_lowres inference first (separately)"
+        lowres_model = join(paths.network_training_output_dir, "3d_lowres", task_name, args.trainer_class_name + "__" + args.plans_identifier)
+        assert isdir(lowres_model), "model output folder not found. Expected: %s" % lowres_model
+        lowres_output_folder = join(args.output_folder, "3d_lowres_predictions")
+        predict_from_folder(lowres_model, args.input_folder, lowres_output_folder, folds, False, args.num_threads_preprocessing,
+                            args.num_threads_nifti_save, None, args.part_id, args.num_parts, not args.disable_tta,
+                            overwrite_existing=args.overwrite_existing, mode=args.mode, overwrite_all_in_gpu=all_in_gpu,
+                            mixed_precision=not args.disable_mixed_precision, step_size=args.step_size, checkpoint_name=args.chk,
+                            writer=writer, reader=reader, device_deflate=args.device_deflate)
+        lowres_segmentations = lowres_output_folder
+        print("3d_lowres done")
+    trainer_name = args.cascade_trainer_class_name if model == "3d_cascade_fullres" else args.trainer_class_name
+    model_folder_name = join(paths.network_training_output_dir, model, task_name, trainer_name + "__" + args.plans_identifier)
     print("using model stored in ", model_folder_name)
     assert isdir(model_folder_name), "model output folder not found. Expected: %s" % model_folder_name
     return predict_from_folder(model_folder_name, args.input_folder, args.output_folder, folds, args.save_npz,
@@ -84,7 +103,7 @@ def main(argv=None, reader=None, writer=None):
                                args.num_parts, not args.disable_tta, overwrite_existing=args.overwrite_existing, mode=args.mode,
                                overwrite_all_in_gpu=all_in_gpu, mixed_precision=not args.disable_mixed_precision,
                                step_size=args.step_size, checkpoint_name=args.chk, writer=writer, reader=reader,
-                               device_deflate=args.device_deflate)
+                               device_deflate=args.device_deflate, seg_reader=seg_reader)
 
 
 if __name__ == "__main__":

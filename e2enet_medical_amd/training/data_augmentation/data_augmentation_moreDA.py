@@ -21,8 +21,13 @@ the linear kernels.  ``dummy_2D`` (reference :58-60, :80-81; switched on by the 
 spatial transform runs on that view as a ONE-slice-deep volume -- one in-plane rotation (``rotation_x``) and scale per sample,
 shared by all slices, 2-D cubic B-spline per slice (prefilter along H and W only) -- through the same kernels; the
 low-resolution simulation then leaves the slice axis alone (``ignore_axes=(0,)``).  Not built, and rejected when asked for:
-elastic deformation (switched off by the trainer, nnUNetTrainer_simple.py:730), the cascade / pyramid transforms, region
-targets, additive brightness, independent per-axis scaling, random crops.
+elastic deformation (switched off by the trainer, nnUNetTrainer_simple.py:730), region targets, additive brightness, independent
+per-axis scaling, random crops.
+
+The cascade (``move_last_seg_chanel_to_data``, reference :119-138): after Mirror, Mask and RemoveLabel the previous stage's
+segmentation (seg channel 1) becomes one-hot data channels, and ApplyRandomBinaryOperatorTransform and
+RemoveRandomConnectedComponentFromOneHotEncodingTransform run on them (pyramid_augmentations.py, csrc/cascade.hip); their draws
+follow the mirror draws.  Without that parameter nothing of it is constructed, drawn or launched.
 """
 from typing import Iterable, Optional, Sequence
 
@@ -60,8 +65,9 @@ class DeviceAugmenter:
             p["do_elastic"] = False        # the table default is True; the trainer, the only caller in the reference, switches it off (:730)
         if p.get("do_elastic"):
             raise NotImplementedError("elastic deformation is not built (the trainer switches it off, nnUNetTrainer_simple.py:730)")
-        if p.get("move_last_seg_chanel_to_data"):
-            raise NotImplementedError("cascade augmentations are outside the 3D shiftConvPP path")
+        self.cascade_move, self.cascade_binop, self.cascade_rcc = cascade_transforms(p)
+        if self.cascade_move is not None and p.get("dummy_2D"):
+            raise NotImplementedError("move_last_seg_chanel_to_data together with dummy_2D is not built")
         self.dummy_2D = bool(p.get("dummy_2D"))
         if p.get("border_mode_data", "constant") != "constant":
             raise NotImplementedError("border_mode_data must be 'constant'")
@@ -159,6 +165,11 @@ class DeviceAugmenter:
                 for ax in (0, 1, 2):
                     if ax in p.get("mirror_axes", (0, 1, 2)) and rs.uniform() < 0.5:
                         d["mirror"][b, ax] = True
+        # the cascade's transforms, in the order the reference composes them (:119-138), after everything above
+        if self.cascade_binop is not None:
+            d["cascade_binop"] = self.cascade_binop.draw(rs, B)
+        if self.cascade_rcc is not None:
+            d["cascade_rcc"] = self.cascade_rcc.draw(rs, B)
         return d
 
     # ---- device execution ------------------------------------------------------------------------------------------------------
@@ -324,6 +335,14 @@ class DeviceAugmenter:
                 um_t = torch.tensor([1 if um[c] else 0 for c in range(C)], dtype=torch.int32, device=self.device)
             L.aug_finish(out.data_ptr(), oseg.data_ptr(), um_t.data_ptr() if um_t is not None else None, B, C, oseg.shape[1], vol,
                          _stream())
+        if self.cascade_move is not None:
+            # MoveSegAsOneHotToData(1, all_segmentation_labels) and the two random transforms on the new channels (reference :119-138)
+            assert oseg is not None and oseg.shape[1] >= 2, "the cascade needs the previous stage's segmentation as seg channel 1"
+            out, oseg = self.cascade_move.apply(out, oseg)
+            if self.cascade_binop is not None:
+                self.cascade_binop.apply(out, draws["cascade_binop"])
+            if self.cascade_rcc is not None:
+                self.cascade_rcc.apply(out, draws["cascade_rcc"])
         return out, oseg
 
     def __call__(self, data, seg=None):
@@ -342,6 +361,35 @@ class DeviceAugmenter:
         if oseg is not None:
             res["target"] = (downsample_seg_for_ds_transform2(oseg, self.ds_scales, order=0) if self.ds_scales is not None else oseg)
         return res
+
+
+def cascade_transforms(params):
+    """(MoveSegAsOneHotToData, ApplyRandomBinaryOperatorTransform or None, RemoveRandomConnectedComponent... or None) as the
+    reference composes them from ``params`` (:119-138), or three Nones without ``move_last_seg_chanel_to_data``.  Kept as the
+    reference has it: ``cascade_remove_conn_comp_max_size_percent_threshold`` is handed over as ``fill_with_other_class_p`` and
+    ``cascade_remove_conn_comp_fill_with_other_class_p`` as ``dont_do_if_covers_more_than_X_percent`` (:136-138, swapped), so with
+    the cascade trainer's defaults the size threshold is 0.0 and nothing is ever removed."""
+    if not params.get("move_last_seg_chanel_to_data"):
+        return None, None, None
+    from .pyramid_augmentations import (ApplyRandomBinaryOperatorTransform, MoveSegAsOneHotToData,
+                                        RemoveRandomConnectedComponentFromOneHotEncodingTransform)
+    labels = params.get("all_segmentation_labels")
+    assert labels is not None and len(labels) > 0, "move_last_seg_chanel_to_data needs all_segmentation_labels"
+    move = MoveSegAsOneHotToData(1, labels, 'seg', 'data')
+    binop = rcc = None
+    if params.get("cascade_do_cascade_augmentations"):
+        channels = list(range(-len(labels), 0))
+        if params.get("cascade_random_binary_transform_p") > 0:
+            binop = ApplyRandomBinaryOperatorTransform(
+                channel_idx=channels, p_per_sample=params.get("cascade_random_binary_transform_p"), key="data",
+                strel_size=params.get("cascade_random_binary_transform_size"),
+                p_per_label=params.get("cascade_random_binary_transform_p_per_label"))
+        if params.get("cascade_remove_conn_comp_p") > 0:
+            rcc = RemoveRandomConnectedComponentFromOneHotEncodingTransform(
+                channel_idx=channels, key="data", p_per_sample=params.get("cascade_remove_conn_comp_p"),
+                fill_with_other_class_p=params.get("cascade_remove_conn_comp_max_size_percent_threshold"),
+                dont_do_if_covers_more_than_X_percent=params.get("cascade_remove_conn_comp_fill_with_other_class_p"))
+    return move, binop, rcc
 
 
 class _DeviceGenerator:
@@ -399,6 +447,8 @@ def get_moreDA_augmentation(dataloader_train, dataloader_val, patch_size, params
             seg = seg[:, list(params["selected_seg_channels"])].contiguous()
         lib().aug_finish(data.data_ptr(), seg.data_ptr(), None, data.shape[0], data.shape[1], seg.shape[1],
                          int(np.prod(seg.shape[2:])), _stream())            # RemoveLabelTransform(-1, 0)
+        if aug.cascade_move is not None:                                    # MoveSegAsOneHotToData only (:176-177)
+            data, seg = aug.cascade_move.apply(data, seg)
         tgt = downsample_seg_for_ds_transform2(seg, deep_supervision_scales, order=0) if deep_supervision_scales is not None else seg
         return {"data": data, "target": tgt}
     if to_regions is not None:

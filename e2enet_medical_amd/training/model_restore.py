@@ -12,7 +12,8 @@ def trainer_classes():
     from .network_training.nnUNetTrainer_simple import nnUNetTrainer_simple
     from .network_training.competitions_with_custom_Trainers.BraTS2020.nnUNetTrainerV2BraTSRegions import \
         nnUNetTrainerV2BraTSRegions
-    return {c.__name__: c for c in (nnUNetTrainer_simple, nnUNetTrainerV2BraTSRegions)}
+    from .network_training.nnUNetTrainerV2CascadeFullRes import nnUNetTrainerV2CascadeFullRes
+    return {c.__name__: c for c in (nnUNetTrainer_simple, nnUNetTrainerV2BraTSRegions, nnUNetTrainerV2CascadeFullRes)}
 
 
 def recursive_find_python_class(name):

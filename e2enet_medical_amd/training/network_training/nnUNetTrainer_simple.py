@@ -363,6 +363,11 @@ class nnUNetTrainer_simple(object):
         """called by validate() behind aggregate_scores with its cases [(prediction, ground truth, prediction file, ground-truth
         file)] and the summary.json it wrote; a subclass adds its own rows"""
 
+    def _validation_network_input(self, key, data):
+        """what validate() feeds the network for the preprocessed case ``data`` [C + 1, X, Y, Z]: its modalities (the cascade's
+        trainer appends the previous stage's segmentation)"""
+        return data[:-1]
+
     def _rank(self):
         """(rank, world, group) of the data-parallel job; (0, 1, None) for a single process"""
         import torch.distributed as dist
@@ -989,7 +994,7 @@ class nnUNetTrainer_simple(object):
                     data[-1][data[-1] == -1] = 0
                     net.keep_on_device = True
                     seg_grid, softmax = self.predict_preprocessed_data_return_seg_and_softmax(
-                        data[:-1], do_mirroring=do_mirroring, mirror_axes=mirror_axes, use_sliding_window=use_sliding_window,
+                        self._validation_network_input(k, data), do_mirroring=do_mirroring, mirror_axes=mirror_axes, use_sliding_window=use_sliding_window,
                         step_size=step_size, use_gaussian=use_gaussian, all_in_gpu=all_in_gpu, verbose=False,
                         mixed_precision=self.fp16)
                     net.keep_on_device = keep

@@ -855,6 +855,46 @@ int e2e_deflate_encode(const void* src, long long nbytes, int elem, unsigned cha
 int e2e_deflate_gather(const unsigned char* slots, const unsigned* counts, const long long* offsets, long long nchunks,
                        unsigned char* out, long long out_bytes, void* stream);
 
+/* ---- N7: the two-stage cascade (csrc/cascade.hip) -------------------------------------------------------------------------------
+ * Replaces: resample_and_save of the 3d_lowres hand-over (e2enet/training/cascade_stuff/predict_next_stage.py:31-43:
+ * resample_data_or_seg(order 1) of the [K, ...] softmax on the host, argmax(0), uint8) and the three transforms of
+ * e2enet/training/data_augmentation/pyramid_augmentations.py:23-136 (skimage's ball / binary_dilation / binary_erosion /
+ * binary_closing / binary_opening / label on every one-hot channel of the previous stage's segmentation).  Every result is an integer
+ * or a bit, all atomics are integer: the same bits on every run.
+ *   resample_argmax_u8: src as e2e_resample_linear reads it ([K] volumes of the frame [A,B,C] through strides, class stride kstride);
+ *     seg (contiguous uint8 [OA,OB,OC]) = first maximum over k of the K order-1 values e2e_resample_linear(lowres_axis = -1) forms
+ *     (the same expression, e2e_resample.h; a NaN counts as a maximum, as in e2e_export_argmax_u8).  1 <= K <= 256.
+ *   seg_onehot: out[b, c0 + l, i] = (seg[b, channel, i] == labels[l]) as 0.0 / 1.0; seg [B, CS, vol], out [B, CO, vol]; labels is a
+ *     HOST array of n_labels (1 .. 64) ints, read before the call returns.
+ *   morph_*: binary morphology of one fp32 channel [D, H, W] on bit-packed rows.  pack: bits[(z H + y) ceil(W / 64) + w] holds
+ *     x != 0 of voxels 64 w .. 64 w + 63 of the row, zero behind its end; e2e_morph_bits_words is the word count.  pass: the
+ *     footprint of N^3 voxels with origin c = N / 2 is a HOST table of n_rows x (oz, oy, x_lo, x_hi), offsets from the origin, one
+ *     contiguous x-run per (z, y) row.  dst[p] = OR over footprint offsets o of src[p - o], 0 outside the volume (scipy's
+ *     binary_dilation); reflect != 0 reads src[p + o]; complement != 0 complements the source on load and the result on store, so
+ *     that reflect = complement = 1 is binary_erosion(border_value = 1): AND over o of src[p + o], 1 outside.  src != dst.
+ *     E2E_ERR_UNSUPPORTED, nothing launched: N > e2e_morph_max_footprint() (17), two runs in one (oz, oy) row (a row with a gap).
+ *     unpack: sample[channel][i] = bit as 0.0 / 1.0 of a sample [n_channels, D, H, W]; where the bit is 1 and the channel was 0
+ *     ("was added") the n_others (0 .. 64) channels of the HOST list `others` are set to 0 at that voxel.
+ *   rcc_remove: x, one fp32 channel [D, H, W], is labelled with 26-neighbour connectivity (x != 0).  Of the components with
+ *     (double)size < threshold, in the order of their first voxel in raster order (the label order of skimage and scipy), number
+ *     floor(u * count) is set to 0 in x and, when fill != NULL, to 1 in fill.  0 <= u < 1.  result (device, 4 x u64): components,
+ *     eligible components, size of the removed component (0: none), give-up word of the union-find (then nothing is removed).
+ *     ws: e2e_rcc_ws_bytes(D, H, W) bytes; D H W <= 2^31 - 2.                                                                    */
+int e2e_resample_argmax_u8(const float* src, unsigned char* seg, int K, long long kstride, int A, int B, int C, long long sa,
+                           long long sb, long long sc, int OA, int OB, int OC, void* stream);
+int e2e_seg_onehot(const float* seg, float* out, const int* labels, int n_labels, int B, int CS, int channel, int CO, int c0,
+                   long long vol, void* stream);
+int e2e_morph_max_footprint(void);
+long long e2e_morph_bits_words(int D, int H, int W);
+int e2e_morph_pack(const float* x, unsigned long long* bits, int D, int H, int W, void* stream);
+int e2e_morph_pass(const unsigned long long* src, unsigned long long* dst, int D, int H, int W, const int* table, int n_rows, int N,
+                   int reflect, int complement, void* stream);
+int e2e_morph_unpack(const unsigned long long* bits, float* sample, int n_channels, int channel, const int* others, int n_others,
+                     int D, int H, int W, void* stream);
+long long e2e_rcc_ws_bytes(int D, int H, int W);
+int e2e_rcc_remove(float* x, float* fill, int D, int H, int W, double threshold, double u, void* ws, unsigned long long* result,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
