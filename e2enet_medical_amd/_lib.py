@@ -247,6 +247,7 @@ SIGNATURES = {
     "e2e_deflate_chunk_bytes": (I, []),
     "e2e_deflate_slot_bytes": (I, []),
     "e2e_deflate_encode": (I, [P, LL, I, P, P, P, P, P]),
+    "e2e_deflate_encode_dynamic": (I, [P, LL, I, P, P, P, P, P, P]),
     "e2e_deflate_gather": (I, [P, P, P, LL, P, LL, P]),
     "e2e_resample_argmax_u8": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, P]),
     "e2e_seg_onehot": (I, [P, P, P, I, I, I, I, I, I, LL, P]),
@@ -305,7 +306,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 31          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 32          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

@@ -8,7 +8,7 @@ import json
 import os
 import shutil
 
-from . import nifti, paths
+from . import deflate, nifti, paths
 from .experiment_planning.DatasetAnalyzer import DEFAULT_NUM_THREADS, DatasetAnalyzer
 from .experiment_planning.utils import crop
 from .utilities.task_name_id_conversion import convert_id_to_task_name
@@ -22,6 +22,7 @@ def build_parser():
     parser.add_argument('--override', action='store_true',
                         help='empty the cropped folder and crop every case again, and recompute the intensity properties')
     nifti.add_argument(parser)
+    deflate.add_argument(parser, what="the <case>.npz of every case")
     return parser
 
 
@@ -37,7 +38,7 @@ def main(argv=None, reader=None):
         task_name = convert_id_to_task_name(int(task_name))
     raw = os.path.join(paths.nnUNet_raw_data, task_name)
     assert os.path.isfile(os.path.join(raw, "dataset.json")), "dataset.json not found. Expected: %s" % os.path.join(raw, "dataset.json")
-    crop(task_name, args.override, args.tf, reader=select_reader(args, reader))
+    crop(task_name, args.override, args.tf, reader=select_reader(args, reader), device_deflate=deflate.from_args(args))
     cropped = os.path.join(paths.nnUNet_cropped_data, task_name)
     preprocessed = os.path.join(paths.preprocessing_output_dir, task_name)
     # the intensity properties are collected only when one of the modalities is CT

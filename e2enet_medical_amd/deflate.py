@@ -1,17 +1,21 @@
 """Raw DEFLATE of device buffers (csrc/deflate.hip) and the two containers the package writes with it: a gzip member (``.nii.gz``)
-and a ``.npz``.  Opt-in (``device_deflate=True`` / ``--device_deflate``): the default routes keep compressing on the host with zlib,
-byte for byte as before.
+and a ``.npz``.  Opt-in (``device_deflate=True`` / ``--device_deflate``, ``device_deflate="dynamic"`` / ``--dynamic_huffman``): the
+default routes keep compressing on the host with zlib, byte for byte as before.
 
-What the device writes is a valid but plain stream: chunks of ``chunk_bytes()`` bytes, each one fixed-Huffman block whose only
-matches say "the same element again" (distance = the element size), or one stored block where that is shorter (include/e2e_hip.h
-states the format; tests/test_gpu_deflate.py restates it in Python).  No dynamic Huffman codes, no search for other distances: a
-constant background shrinks about 150-fold, noisy values do not shrink at all.  What it saves is the download of the uncompressed
-volume and the host's single-threaded pass over it; only compressed bytes cross the link.
+What the device writes is a valid but plain stream: chunks of ``chunk_bytes()`` bytes, each one Huffman block whose only matches
+say "the same element again" (distance = the element size), or one stored block where that is shorter (include/e2e_hip.h states
+the format; tests/test_gpu_deflate.py and tests/deflate_dynamic_oracle.py restate it in Python).  No search for other distances.
+With ``codes="fixed"`` (``device_deflate=True``) the block uses the fixed code: a constant background shrinks about 150-fold, noisy
+values do not shrink at all.  With ``codes="dynamic"`` every chunk gets a Huffman code built from its own tokens and is written in
+the shortest of the three forms: values whose bytes are unevenly distributed (floating point, labels) shrink about as far as zlib's
+Huffman coding takes them.  What either saves is the download of the uncompressed volume and the host's single-threaded pass
+over it; only compressed bytes cross the link.
 
 A container member is ``host prefix + device buffer``: the prefix (a NIfTI header, a ``.npy`` header) goes through host zlib as a raw
 stream ended with a sync flush, which leaves it byte-aligned and not final; the device's chunks follow, every one byte-aligned and not
 final; ``03 00`` -- an empty final fixed-Huffman block -- closes the stream.  The CRC-32 of the member is combined from the prefix's
 and the device's with the GF(2) shift operator (``crc32_combine``; Python's zlib module does not export zlib's)."""
+import argparse
 import io
 import struct
 import zlib
@@ -78,19 +82,49 @@ def _as_device_bytes(tensor, elem, who):
     return nbytes, elem
 
 
-def raw_deflate(tensor, elem=None):
+CODES = ("fixed", "dynamic")
+STORED, FIXED, DYNAMIC = 0, 1, 2         # what ``chunk_kinds`` reports per chunk
+
+
+def check_codes(codes, who="deflate"):
+    if codes not in CODES:
+        raise ValueError("%s: codes %r is neither 'fixed' nor 'dynamic'" % (who, codes))
+    return codes
+
+
+def codes_of(device_deflate, who="device_deflate"):
+    """The ``device_deflate`` argument of the writers as ``codes``: ``True`` is the fixed code, ``"dynamic"`` the per-chunk code
+    (``"fixed"`` is accepted too); a false value is None, the host route."""
+    if not device_deflate:
+        return None
+    if device_deflate is True:
+        return "fixed"
+    if device_deflate in CODES:
+        return device_deflate
+    raise ValueError("%s=%r: True, 'fixed', 'dynamic' or False" % (who, device_deflate))
+
+
+def raw_deflate(tensor, elem=None, codes="fixed"):
     """``(stream, crc32, nbytes)`` of a contiguous device tensor: its bytes as a raw DEFLATE stream that is complete (ends with the
     final block), ``zlib.crc32`` of the bytes, and their number.  ``elem``: the distance of the matches, 1, 2, 4 or 8 bytes and a
-    divisor of the byte count; default the tensor's element size.  The stream depends on the bytes and ``elem`` only.  Only the
-    compressed bytes and one CRC word are downloaded."""
-    body, crc, nbytes = _raw_body(tensor, elem, "raw_deflate")
+    divisor of the byte count; default the tensor's element size.  ``codes``: ``"fixed"`` or ``"dynamic"`` (a Huffman code per
+    chunk).  The stream depends on the bytes, ``elem`` and ``codes`` only.  Only the compressed bytes and one CRC word are
+    downloaded."""
+    body, crc, nbytes = _raw_body(tensor, elem, "raw_deflate", codes)
     return body + STREAM_END, crc, nbytes
 
 
-def _raw_body(tensor, elem, who):
+def chunk_kinds(tensor, elem=None, codes="dynamic"):
+    """The form of every chunk of ``raw_deflate(tensor, elem, codes)`` as a uint8 array: 0 stored, 1 fixed, 2 dynamic.  For the
+    fixed codes the form is read off the chunk's first byte (a stored block begins with a zero byte)."""
+    return _raw_body(tensor, elem, "chunk_kinds", codes, want_kinds=True)[3]
+
+
+def _raw_body(tensor, elem, who, codes="fixed", want_kinds=False):
     """the chunks without the closing block"""
     import torch
     from ._lib import lib
+    check_codes(codes, who)
     nbytes, elem = _as_device_bytes(tensor, elem, who)
     L = lib()
     st = torch.cuda.current_stream(tensor.device).cuda_stream
@@ -100,19 +134,29 @@ def _raw_body(tensor, elem, who):
         crc = torch.empty(1, dtype=torch.int32, device=tensor.device)
         if nchunks == 0:
             L.deflate_encode(None, 0, elem, None, None, None, crc.data_ptr(), st)
-            return b"", int(crc.item()) & 0xFFFFFFFF, 0
+            return (b"", int(crc.item()) & 0xFFFFFFFF, 0) + ((np.zeros(0, dtype=np.uint8),) if want_kinds else ())
         slots = torch.empty(nchunks * slot, dtype=torch.uint8, device=tensor.device)
         counts = torch.empty(nchunks, dtype=torch.int32, device=tensor.device)
         chunk_crcs = torch.empty(nchunks, dtype=torch.int32, device=tensor.device)
-        L.deflate_encode(tensor.data_ptr(), nbytes, elem, slots.data_ptr(), counts.data_ptr(), chunk_crcs.data_ptr(), crc.data_ptr(),
-                         st)
+        kinds = None
+        if codes == "dynamic":
+            kinds = torch.empty(nchunks, dtype=torch.uint8, device=tensor.device)
+            L.deflate_encode_dynamic(tensor.data_ptr(), nbytes, elem, slots.data_ptr(), counts.data_ptr(), kinds.data_ptr(),
+                                     chunk_crcs.data_ptr(), crc.data_ptr(), st)
+        else:
+            L.deflate_encode(tensor.data_ptr(), nbytes, elem, slots.data_ptr(), counts.data_ptr(), chunk_crcs.data_ptr(),
+                             crc.data_ptr(), st)
         ends = torch.cumsum(counts, 0, dtype=torch.int64)                 # 64-bit offsets: 4 GiB and more by construction
         offsets = (ends - counts).contiguous()
         total = int(ends[-1].item())
         out = torch.empty(total, dtype=torch.uint8, device=tensor.device)
         L.deflate_gather(slots.data_ptr(), counts.data_ptr(), offsets.data_ptr(), nchunks, out.data_ptr(), total, st)
         body = out.cpu().numpy().tobytes()
-        return body, int(crc.item()) & 0xFFFFFFFF, nbytes
+        if not want_kinds:
+            return body, int(crc.item()) & 0xFFFFFFFF, nbytes
+        if kinds is None:
+            kinds = (out[offsets] != 0).to(torch.uint8)
+        return body, int(crc.item()) & 0xFFFFFFFF, nbytes, kinds.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------- members
@@ -137,11 +181,11 @@ def gzip_bytes(stream, crc, length):
     return GZIP_HEADER + stream + struct.pack("<II", crc & 0xFFFFFFFF, length & 0xFFFFFFFF)
 
 
-def gzip_member(host_prefix, tensor):
+def gzip_member(host_prefix, tensor, codes="fixed"):
     """The bytes of a ``.gz`` file that inflates to ``host_prefix`` followed by the bytes of the device tensor: the header
-    ``nifti.write`` stores (mtime 0, no name), the prefix through host zlib, the device's stream, CRC-32 and length (mod 2^32) of
-    the whole."""
-    body, crc, nbytes = _raw_body(tensor, None, "gzip_member")
+    ``nifti.write`` stores (mtime 0, no name), the prefix through host zlib, the device's stream (``codes`` as in ``raw_deflate``),
+    CRC-32 and length (mod 2^32) of the whole."""
+    body, crc, nbytes = _raw_body(tensor, None, "gzip_member", codes)
     return gzip_bytes(*member_stream(host_prefix, body, crc, nbytes))
 
 
@@ -193,21 +237,41 @@ def zip_bytes_parts(members):
     return parts
 
 
+def _npz_path(path):
+    path = str(path)
+    return path if path.endswith(".npz") else path + ".npz"          # (np.savez's rule)
+
+
+def _member_parts(members):
+    return zip_bytes_parts([(key + ".npy", stream, crc, length) for key, stream, crc, length in members])
+
+
 def write_npz(path, members):
     """``members``: ``(key, raw stream, crc32, length)`` of ``<key>.npy`` each"""
-    path = str(path)
-    if not path.endswith(".npz"):
-        path += ".npz"                       # (np.savez's rule)
-    with open(path, "wb") as f:
-        for part in zip_bytes_parts([(key + ".npy", stream, crc, length) for key, stream, crc, length in members]):
+    write_parts(path, _member_parts(members))
+
+
+def write_parts(path, parts):
+    """what ``npz_parts`` returned, written to ``path`` (``.npz`` appended where it is missing): the half of ``savez`` that needs no
+    device, for a writer thread"""
+    with open(_npz_path(path), "wb") as f:
+        for part in parts:
             f.write(part)
 
 
-def savez(path, **arrays):
+def savez(path, codes="fixed", **arrays):
     """``np.savez_compressed(path, **arrays)`` with the arrays deflated on the device: a ``.npz`` that ``np.load`` reads.  A member
-    is the ``.npy`` header (host prefix) and the array's bytes (device stream).  Device tensors never reach the host uncompressed;
-    host arrays are uploaded first.  Every array is C-contiguous (a non-contiguous device tensor is a ValueError)."""
+    is the ``.npy`` header (host prefix) and the array's bytes (device stream, ``codes`` as in ``raw_deflate``; an array cannot be
+    called ``codes``).  Device tensors never reach the host uncompressed; host arrays are uploaded first.  Every array is
+    C-contiguous (a non-contiguous device tensor is a ValueError)."""
+    write_parts(path, npz_parts(codes=codes, **arrays))
+
+
+def npz_parts(codes="fixed", **arrays):
+    """The byte strings ``savez`` writes one after the other, without writing them: the thread that owns the GPU compresses, and any
+    other thread can write (``write_parts``).  The bytes depend on the arrays, their order and ``codes`` alone."""
     import torch
+    check_codes(codes, "deflate.savez")
     members = []
     for key, a in arrays.items():
         if not isinstance(a, torch.Tensor):
@@ -218,13 +282,31 @@ def savez(path, **arrays):
             a = a.contiguous().to("cuda")
         if str(a.dtype) not in _TORCH_TO_NUMPY:
             raise ValueError("deflate.savez: %s: dtype %s has no .npy descr" % (key, a.dtype))
-        body, crc, nbytes = _raw_body(a, None, "deflate.savez(%s)" % key)
+        body, crc, nbytes = _raw_body(a, None, "deflate.savez(%s)" % key, codes)
         members.append((key,) + member_stream(npy_header(_TORCH_TO_NUMPY[str(a.dtype)], a.shape), body, crc, nbytes))
-    write_npz(path, members)
+    return _member_parts(members)
 
 
-def add_argument(parser):
-    """the ``--device_deflate`` switch of the command-line tools"""
+class _DynamicHuffman(argparse.Action):
+    """``--dynamic_huffman`` sets ``--device_deflate`` too"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.dynamic_huffman = True
+        namespace.device_deflate = True
+
+
+def add_argument(parser, what=".npz class probabilities, .nii.gz of the native NIfTI writer"):
+    """the ``--device_deflate`` and ``--dynamic_huffman`` switches of the command-line tools; ``from_args`` reads them"""
     parser.add_argument("--device_deflate", action="store_true", default=False,
-                        help="compress what is written (.npz class probabilities, .nii.gz of the native NIfTI writer) on the GPU and "
-                             "download only compressed bytes; default: download and compress with zlib on the host")
+                        help="compress what is written (%s) on the GPU and download only compressed bytes; default: download and "
+                             "compress with zlib on the host" % what)
+    parser.add_argument("--dynamic_huffman", action=_DynamicHuffman, nargs=0, default=False,
+                        help="implies --device_deflate: every 32 KiB chunk gets a Huffman code built from its own bytes instead of "
+                             "DEFLATE's fixed code (smaller files, floating-point data above all)")
+
+
+def from_args(args):
+    """the ``device_deflate`` argument of the writers from the parsed switches: False, True or ``"dynamic"``"""
+    if getattr(args, "dynamic_huffman", False):
+        return "dynamic"
+    return bool(getattr(args, "device_deflate", False))

@@ -284,7 +284,8 @@ class ExperimentPlanner(object):
         self._write_mask_decision(self.plans['use_mask_for_norm'])
 
     # ---------------------------------------------------------------------------------------------------------- preprocessing
-    def run_preprocessing(self, num_threads):
+    def run_preprocessing(self, num_threads, device_deflate=False):
         """``gt_segmentations`` copied and every stage preprocessed on the device (``preprocessing.run_preprocessing``, which holds the
-        reference's handling of ``num_threads``: one number, or (lowres, fullres))"""
-        run_preprocessing(self.plans, self.folder_with_cropped_data, self.preprocessed_output_folder, num_threads)
+        reference's handling of ``num_threads``: one number, or (lowres, fullres), and says what ``device_deflate`` does)"""
+        run_preprocessing(self.plans, self.folder_with_cropped_data, self.preprocessed_output_folder, num_threads,
+                          device_deflate=device_deflate)

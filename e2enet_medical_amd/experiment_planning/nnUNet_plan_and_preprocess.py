@@ -15,7 +15,7 @@ import json
 import os
 import shutil
 
-from .. import nifti, paths
+from .. import deflate, nifti, paths
 from ..preprocessing.sanity_checks import verify_dataset_integrity
 from ..utilities.task_name_id_conversion import convert_id_to_task_name
 from .DatasetAnalyzer import DatasetAnalyzer
@@ -50,6 +50,7 @@ def build_parser():
     parser.add_argument("-overwrite_plans_identifier", type=str, default=None, required=False,
                         help="goes with -overwrite_plans: not built")
     nifti.add_argument(parser)
+    deflate.add_argument(parser, what="the <case>.npz of every case")
     return parser
 
 
@@ -79,7 +80,7 @@ def main(argv=None, reader=None):
         task_name = convert_id_to_task_name(int(i))
         if args.verify_dataset_integrity:
             verify_dataset_integrity(os.path.join(paths.nnUNet_raw_data, task_name), args.tf)
-        crop(task_name, False, args.tf, reader=reader)
+        crop(task_name, False, args.tf, reader=reader, device_deflate=deflate.from_args(args))
         tasks.append(task_name)
 
     for t in tasks:
@@ -103,7 +104,7 @@ def main(argv=None, reader=None):
             exp_planner = planner_3d(cropped_out_dir, preprocessing_output_dir_this_task)
             exp_planner.plan_experiment()
             if not args.no_pp:
-                exp_planner.run_preprocessing(threads)
+                exp_planner.run_preprocessing(threads, device_deflate=deflate.from_args(args))
 
 
 if __name__ == "__main__":

@@ -32,9 +32,10 @@ def create_lists_from_splitted_dataset(base_folder_splitted):
     return lists, {int(i): d['modality'][str(i)] for i in d['modality'].keys()}
 
 
-def crop(task_string, override=False, num_threads=DEFAULT_NUM_THREADS, reader=None):
+def crop(task_string, override=False, num_threads=DEFAULT_NUM_THREADS, reader=None, device_deflate=False):
     """Reference :122-135: ``<nnUNet_raw_data>/<task>`` into ``<nnUNet_cropped_data>/<task>``; ``override`` empties that folder first
-    and crops every case again.  ``reader``: see preprocessing/cropping.py (default: the SimpleITK loader)."""
+    and crops every case again.  ``reader``: see preprocessing/cropping.py (default: the SimpleITK loader).  ``device_deflate``: see
+    ``ImageCropper.run_cropping``."""
     cropped_out_dir = os.path.join(paths.nnUNet_cropped_data, task_string)
     os.makedirs(cropped_out_dir, exist_ok=True)
     if override and os.path.isdir(cropped_out_dir):
@@ -43,7 +44,7 @@ def crop(task_string, override=False, num_threads=DEFAULT_NUM_THREADS, reader=No
     splitted_4d_output_dir_task = os.path.join(paths.nnUNet_raw_data, task_string)
     lists, _ = create_lists_from_splitted_dataset(splitted_4d_output_dir_task)
     imgcrop = ImageCropper(num_threads, cropped_out_dir)
-    imgcrop.run_cropping(lists, overwrite_existing=override, reader=reader)
+    imgcrop.run_cropping(lists, overwrite_existing=override, reader=reader, device_deflate=device_deflate)
     shutil.copy(os.path.join(paths.nnUNet_raw_data, task_string, "dataset.json"), cropped_out_dir)
 
 

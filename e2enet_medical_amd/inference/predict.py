@@ -103,17 +103,19 @@ def softmax_to_f16(softmax: torch.Tensor, dims: Sequence[int], strides: Sequence
 
 
 def save_softmax_npz(softmax_f16: torch.Tensor, resampled_npz_fname: str, properties_dict: dict,
-                     region_class_order: Optional[Sequence[int]] = None, device_deflate: bool = False):
+                     region_class_order: Optional[Sequence[int]] = None, device_deflate: Union[bool, str] = False):
     """``<case>.npz`` (key ``softmax``, fp16) and ``<case>.pkl`` as segmentation_export.py:117-122 leaves them for the ensembling
     step (inference/ensemble_predictions.py); the pickle names ``regions_class_order`` when there is one.  ``device_deflate``: the
     device tensor is deflated where it lies (``deflate.savez``) and only compressed bytes are downloaded; ``np.load`` reads the same
-    array, the archive's bytes differ from the default route's.  A CPU or non-contiguous tensor is then a ValueError."""
+    array, the archive's bytes differ from the default route's.  A CPU or non-contiguous tensor is then a ValueError.  ``True``
+    selects DEFLATE's fixed Huffman code, ``"dynamic"`` a code per chunk (``deflate.savez(codes=...)``)."""
     if device_deflate:
         from .. import deflate
+        codes = deflate.codes_of(device_deflate, "save_softmax_npz: device_deflate")
         if not (softmax_f16.is_cuda and softmax_f16.is_contiguous()):
             raise ValueError("save_softmax_npz(device_deflate=True): the probabilities must be a contiguous device tensor (got %s)"
                              % ("a non-contiguous tensor" if softmax_f16.is_cuda else "a CPU tensor",))
-        deflate.savez(resampled_npz_fname, softmax=softmax_f16)
+        deflate.savez(resampled_npz_fname, codes=codes, softmax=softmax_f16)
     else:
         np.savez_compressed(resampled_npz_fname, softmax=softmax_f16.cpu().numpy())
     if region_class_order is not None:
@@ -125,7 +127,7 @@ def save_softmax_npz(softmax_f16: torch.Tensor, resampled_npz_fname: str, proper
 def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_backward: Optional[Sequence[int]] = None,
                         region_class_order: Optional[Sequence[int]] = None, force_separate_z: Optional[bool] = None,
                         order: int = 1, interpolation_order_z: int = 0, postprocessing=None,
-                        resampled_npz_fname: Optional[str] = None, device_deflate: bool = False,
+                        resampled_npz_fname: Optional[str] = None, device_deflate: Union[bool, str] = False,
                         keep_on_device: bool = False) -> Union[np.ndarray, torch.Tensor]:
     """uint8 label volume in the ORIGINAL (uncropped) geometry from a device softmax [K, X, Y, Z]
     (reference predict.py:298-301 + segmentation_export.py:73-136).
@@ -181,15 +183,15 @@ def export_segmentation(softmax: torch.Tensor, properties_dict: dict, transpose_
 def predict_cases(trainer, params: Sequence[dict], preprocessed: Iterable[Tuple[str, Tuple[np.ndarray, dict]]],
                   writer: Callable[[np.ndarray, str, dict], None], do_tta: bool = True, step_size: float = 0.5,
                   all_in_gpu: bool = False, mixed_precision: bool = True, postprocessing=None, save_npz: bool = False,
-                  device_deflate: bool = False):
+                  device_deflate: Union[bool, str] = False):
     """The per-case loop of reference predict_cases (predict.py:273-331) on preprocessed cases
     ``(output_filename, (data [C,X,Y,Z], properties_dict))``; ``writer(seg_uint8, output_filename, properties_dict)``
     stores the label volume (the reference's SimpleITK NIfTI writer, segmentation_export.py:144-148, is host tooling).
     ``postprocessing``: see ``export_segmentation``.  ``save_npz``: ``<case>.npz`` and ``<case>.pkl`` beside every label file
     (predict.py:303-304), what ``inference/ensemble_predictions.py`` merges.  ``device_deflate``: the ``.npz`` is deflated on the
     device, and a writer that carries ``accepts_device = True`` (``nifti.writer``) is called as ``writer(device_seg, output_filename,
-    properties_dict, device_deflate=True)``: it receives the label volume as a device tensor and compresses it there.  Any other
-    writer gets the host array as before."""
+    properties_dict, device_deflate=device_deflate)``: it receives the label volume as a device tensor and compresses it there.  Any
+    other writer gets the host array as before.  ``True``: the fixed Huffman code; ``"dynamic"``: a code per chunk."""
     done = []
     to_writer = device_deflate and getattr(writer, "accepts_device", False)
     for output_filename, (d, dct) in preprocessed:
@@ -201,7 +203,7 @@ def predict_cases(trainer, params: Sequence[dict], preprocessed: Iterable[Tuple[
                                   resampled_npz_fname=output_filename[:-7] + ".npz" if save_npz else None,
                                   device_deflate=device_deflate, keep_on_device=to_writer)
         if to_writer:
-            writer(seg.contiguous(), output_filename, dct, device_deflate=True)
+            writer(seg.contiguous(), output_filename, dct, device_deflate=device_deflate)
         else:
             writer(seg, output_filename, dct)
         done.append(output_filename)
@@ -296,7 +298,7 @@ def predict_from_folder(model: str, input_folder: str, output_folder: str, folds
                         mixed_precision: bool = True, overwrite_existing: bool = True, mode: str = 'normal',
                         overwrite_all_in_gpu: bool = None, step_size: float = 0.5,
                         checkpoint_name: str = "model_final_checkpoint", segmentation_export_kwargs: dict = None,
-                        disable_postprocessing: bool = False, writer=None, reader=None, device_deflate: bool = False,
+                        disable_postprocessing: bool = False, writer=None, reader=None, device_deflate: Union[bool, str] = False,
                         seg_reader=None):
     """reference predict.py:675-764 with the same arguments: the cases ``[part_id::num_parts]`` of ``input_folder`` through
     ``load_model_and_checkpoint_files`` (model_restore.py:108-154) -> fold ensemble -> export, written to ``output_folder``.

@@ -373,9 +373,9 @@ def _check_shape(shape):
         raise ValueError("write: an axis of %s does not fit dim (1 .. 32767)" % (tuple(shape),))
 
 
-def _write_device(seg, path, properties):
+def _write_device(seg, path, properties, codes="fixed"):
     """``write`` of a device label volume: the 352 bytes in front of the voxels go through host zlib, the voxels are deflated on the
-    device (deflate.gzip_member) and only compressed bytes are downloaded"""
+    device (deflate.gzip_member, ``codes`` as there) and only compressed bytes are downloaded"""
     import torch
     from . import deflate
     if not (isinstance(seg, torch.Tensor) and seg.is_cuda):
@@ -393,7 +393,7 @@ def _write_device(seg, path, properties):
             raise ValueError("write: the volume holds values that are no labels in [0, 255]")
         seg = as_u8
     body = build_header(tuple(seg.shape), *_geometry_of(properties)) + b"\0\0\0\0"
-    member = deflate.gzip_member(body, seg)
+    member = deflate.gzip_member(body, seg, codes)
     with open(path, "wb") as fh:
         fh.write(member)
 
@@ -402,10 +402,11 @@ def write(seg, path, properties=None, device_deflate=False):
     """A uint8 label volume ``[Z, Y, X]`` as a NIfTI-1 ``.nii.gz`` (``.nii`` for a path without ``.gz``) with the geometry of
     ``properties`` (``itk_origin``, ``itk_spacing``, ``itk_direction``; without them identity LPS and spacing 1).  Deterministic:
     the same volume and geometry give the same bytes.  ``device_deflate``: the volume is a contiguous device tensor (anything else
-    is a ValueError) and is compressed where it lies (csrc/deflate.hip); the file inflates to the same bytes as the default
-    route's, its compressed bytes differ."""
+    is a ValueError) and is compressed where it lies (csrc/deflate.hip), with the fixed Huffman code for ``True`` and a code per
+    chunk for ``"dynamic"``; the file inflates to the same bytes as the default route's, its compressed bytes differ."""
     if device_deflate:
-        return _write_device(seg, path, properties)
+        from . import deflate
+        return _write_device(seg, path, properties, deflate.codes_of(device_deflate, "write: device_deflate"))
     if hasattr(seg, "cpu"):
         seg = seg.cpu().numpy()
     seg = np.asarray(seg)
@@ -429,7 +430,7 @@ def write(seg, path, properties=None, device_deflate=False):
 
 def writer(seg, path, properties, device_deflate=False):
     """``writer(seg_uint8, path, properties)`` of ``predict_cases``, ``validate`` and ``ensemble_predictions``.  ``accepts_device``:
-    ``predict_cases(device_deflate=True)`` hands it the device label volume and the flag"""
+    ``predict_cases(device_deflate=True or "dynamic")`` hands it the device label volume and the flag"""
     write(seg, path, properties, device_deflate=device_deflate)
 
 

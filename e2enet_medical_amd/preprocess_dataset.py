@@ -7,7 +7,7 @@ with the reference."""
 import argparse
 import os
 
-from . import paths
+from . import deflate, paths
 from .preprocessing.preprocessing import DEFAULT_NUM_THREADS, run_preprocessing
 from .utilities.task_name_id_conversion import convert_id_to_task_name
 
@@ -19,6 +19,7 @@ def build_parser():
     parser.add_argument('-tf', type=int, default=DEFAULT_NUM_THREADS, required=False,
                         help='host threads that compress and write finished cases (at most 16); the GPU work is one process')
     parser.add_argument('--unpack', action='store_true', help='also write <case>.npy, the file the training loader memory-maps')
+    deflate.add_argument(parser, what="the <case>.npz of every case")
     return parser
 
 
@@ -33,7 +34,7 @@ def main(argv=None):
     assert os.path.isdir(cropped), "cropped data folder not found. Expected: %s" % cropped
     assert os.path.isfile(plans_file), "plans file not found. Expected: %s" % plans_file
     print("preprocessing", cropped, "with", plans_file)
-    run_preprocessing(plans_file, cropped, preprocessed, args.tf, unpack_npy=args.unpack)
+    run_preprocessing(plans_file, cropped, preprocessed, args.tf, unpack_npy=args.unpack, device_deflate=deflate.from_args(args))
 
 
 if __name__ == "__main__":

@@ -281,25 +281,34 @@ class ImageCropper(object):
     def _is_done(self, case_identifier):
         return all(os.path.isfile(os.path.join(self.output_folder, case_identifier + e)) for e in (".npz", ".pkl"))
 
-    def _crop_case(self, case, reader):
-        """the device half of load_crop_save: ``(vstack((data, seg)) as fp32 numpy, properties)``"""
+    def _crop_case(self, case, reader, device_deflate=False):
+        """the device half of load_crop_save: ``(vstack((data, seg)) as fp32 numpy, properties)``; with ``device_deflate`` the
+        stacked array stays on the device and comes back deflated there, as a ``DeflatedCase``"""
         import torch
+        from .. import deflate
+        from .preprocessing import DeflatedCase
+        codes = deflate.codes_of(device_deflate)
         data, seg, properties = load_case_with_reader(case[:-1], case[-1], reader, "ImageCropper.load_crop_save")
         data, seg, properties = self.crop(to_device(data)[0], properties, to_device(seg)[0] if seg is not None else None)
-        return torch.cat((data, seg)).cpu().numpy(), properties
+        all_data = torch.cat((data, seg))
+        return DeflatedCase(all_data, codes) if codes is not None else all_data.cpu().numpy(), properties
 
     def _write_case(self, all_data, properties, case_identifier):
-        """the host half: ``<case>.npz`` (key ``data``) with a fixed time stamp, ``<case>.pkl``.  Touches no device."""
-        from .preprocessing import save_npz
-        save_npz(os.path.join(self.output_folder, "%s.npz" % case_identifier), all_data)
+        """the host half: ``<case>.npz`` (key ``data``) with a fixed time stamp, ``<case>.pkl``.  Touches no device: a
+        ``DeflatedCase`` brings the bytes of its ``.npz``."""
+        from .preprocessing import DeflatedCase, save_npz
+        if isinstance(all_data, DeflatedCase):
+            all_data.write(os.path.join(self.output_folder, "%s.npz" % case_identifier))
+        else:
+            save_npz(os.path.join(self.output_folder, "%s.npz" % case_identifier), all_data)
         self.save_properties(case_identifier, properties)
 
-    def load_crop_save(self, case, case_identifier, overwrite_existing=False, reader=None):
+    def load_crop_save(self, case, case_identifier, overwrite_existing=False, reader=None, device_deflate=False):
         """Reference :157-174.  ``case``: the modality files and, last, the segmentation file (or None)"""
         try:
             print(case_identifier)
             if overwrite_existing or not self._is_done(case_identifier):
-                self._write_case(*self._crop_case(case, reader), case_identifier)
+                self._write_case(*self._crop_case(case, reader, device_deflate), case_identifier)
         except Exception as e:
             print("Exception in", case_identifier, ":")
             print(e)
@@ -313,12 +322,16 @@ class ImageCropper(object):
         """Reference :179-180"""
         return [i.split("/")[-1][:-4] for i in self.get_list_of_cropped_files()]
 
-    def run_cropping(self, list_of_files, overwrite_existing=False, output_folder=None, reader=None):
+    def run_cropping(self, list_of_files, overwrite_existing=False, output_folder=None, reader=None, device_deflate=False):
         """Reference :182-208: copies the ground-truth files into ``gt_segmentations`` and crops every case of ``list_of_files``
         (``[[modality files ..., seg file], ...]``) into ``<case>.npz`` (key ``data``: modalities and seg stacked, fp32) and
         ``<case>.pkl``.  ``overwrite_existing=False`` skips a case whose two files exist.  This process owns the GPU and walks the
-        cases; the writer threads compress and write finished ones.  The files do not depend on their number."""
+        cases; the writer threads compress and write finished ones.  The files do not depend on their number.  ``device_deflate``
+        (True: fixed codes, ``"dynamic"``: a Huffman code per chunk): the stacked array is deflated on the device by this thread and
+        the writer threads only write; ``np.load`` gives the same ``data``, the ``.pkl`` is the same."""
         from concurrent.futures import ThreadPoolExecutor
+        from .. import deflate
+        deflate.codes_of(device_deflate)
         if output_folder is not None:
             self.output_folder = output_folder
         output_folder_gt = os.path.join(self.output_folder, "gt_segmentations")
@@ -335,7 +348,7 @@ class ImageCropper(object):
                 print(case_identifier)
                 if not overwrite_existing and self._is_done(case_identifier):
                     continue
-                done = self._crop_case(case, reader)
+                done = self._crop_case(case, reader, device_deflate)
                 while len(pending) >= workers:               # bounds the finished cases held in host memory
                     pending.popleft().result()
                 pending.append(pool.submit(self._write_case, *done, case_identifier))

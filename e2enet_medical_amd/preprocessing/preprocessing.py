@@ -219,6 +219,20 @@ def save_npz(path, data):
             np.lib.format.write_array(f, np.asanyarray(data), allow_pickle=False)
 
 
+class DeflatedCase(object):
+    """A finished case whose ``<case>.npz`` the device has already compressed (``device_deflate``): the byte strings of the file
+    (``deflate.npz_parts(data=...)``), and the array itself only where ``--unpack`` needs it for the ``.npy``"""
+
+    def __init__(self, all_data, codes, unpack_npy=False):
+        from .. import deflate
+        self.parts = deflate.npz_parts(codes=codes, data=all_data)
+        self.array = all_data.cpu().numpy() if unpack_npy else None
+
+    def write(self, npz_path):
+        from .. import deflate
+        deflate.write_parts(npz_path, self.parts)
+
+
 def preprocessor_class(preprocessor_name, three_d=True):
     """The class the plans' ``preprocessor_name`` names (None: GenericPreprocessor); NotImplementedError for anything but the two
     built classes, or for 2-D plans"""
@@ -337,8 +351,10 @@ class GenericPreprocessor(object):
         return data.cpu().numpy().astype(np.float32), (seg.astype(int) if made_up_seg else seg), properties
 
 
-    def _preprocess_cropped(self, target_spacing, case_identifier, cropped_output_dir, force_separate_z, all_classes):
-        """the device half of _run_internal (:333-361): ``(vstack((data, seg)) as fp32 numpy, properties with class_locations)``"""
+    def _preprocess_cropped(self, target_spacing, case_identifier, cropped_output_dir, force_separate_z, all_classes,
+                            keep_on_device=False):
+        """the device half of _run_internal (:333-361): ``(vstack((data, seg)) as fp32 numpy, properties with class_locations)``;
+        ``keep_on_device``: the stacked array stays the device tensor it is"""
         import torch
         data, seg, properties = self.load_cropped(cropped_output_dir, case_identifier)
         perm = (0, *[i + 1 for i in self.transpose_forward])
@@ -348,32 +364,47 @@ class GenericPreprocessor(object):
         for c, locs in properties['class_locations'].items():
             if len(locs):
                 print(c, len(locs))
-        return torch.cat((data, seg)).cpu().numpy(), properties
+        all_data = torch.cat((data, seg))
+        return all_data if keep_on_device else all_data.cpu().numpy(), properties
 
     @staticmethod
     def _write_case(all_data, properties, output_folder_stage, case_identifier, unpack_npy=False):
         """the host half of _run_internal (:363-367): ``<case>.npz`` (key ``data``), ``<case>.pkl``; ``unpack_npy`` also writes the
-        ``<case>.npy`` that DataLoader3D memory-maps (the reference's unpack_dataset).  Touches no device."""
+        ``<case>.npy`` that DataLoader3D memory-maps (the reference's unpack_dataset).  Touches no device: a ``DeflatedCase`` brings
+        the bytes of its ``.npz``."""
         print("saving: ", os.path.join(output_folder_stage, "%s.npz" % case_identifier))
-        save_npz(os.path.join(output_folder_stage, "%s.npz" % case_identifier), all_data)
+        if isinstance(all_data, DeflatedCase):
+            all_data.write(os.path.join(output_folder_stage, "%s.npz" % case_identifier))
+            all_data = all_data.array
+        else:
+            save_npz(os.path.join(output_folder_stage, "%s.npz" % case_identifier), all_data)
         if unpack_npy:
             np.save(os.path.join(output_folder_stage, "%s.npy" % case_identifier), all_data)
         with open(os.path.join(output_folder_stage, "%s.pkl" % case_identifier), 'wb') as f:
             pickle.dump(properties, f)
 
     def _run_internal(self, target_spacing, case_identifier, output_folder_stage, cropped_output_dir, force_separate_z, all_classes,
-                      unpack_npy=False):
+                      unpack_npy=False, device_deflate=False):
         """Reference :331-367"""
+        from .. import deflate
+        codes = deflate.codes_of(device_deflate)
         all_data, properties = self._preprocess_cropped(target_spacing, case_identifier, cropped_output_dir, force_separate_z,
-                                                        all_classes)
+                                                        all_classes, keep_on_device=codes is not None)
+        if codes is not None:
+            all_data = DeflatedCase(all_data, codes, unpack_npy)
         self._write_case(all_data, properties, output_folder_stage, case_identifier, unpack_npy)
 
     def run(self, target_spacings, input_folder_with_cropped_npz, output_folder, data_identifier, num_threads=DEFAULT_NUM_THREADS,
-            force_separate_z=None, unpack_npy=False):
+            force_separate_z=None, unpack_npy=False, device_deflate=False):
         """Reference :369-407: every ``<case>.npz`` + ``<case>.pkl`` of a cropped folder into ``<output_folder>/<data_identifier>_stage<i>``
         for each target spacing.  This process owns the GPU and walks the cases; ``num_threads`` (one number, or one per stage; at most
-        16) host threads compress and write finished cases while the device works on the next ones.  The files do not depend on it."""
+        16) host threads compress and write finished cases while the device works on the next ones.  The files do not depend on it.
+        ``device_deflate`` (True: fixed codes, ``"dynamic"``: a Huffman code per chunk): the stacked array stays on the device, this
+        thread deflates it there (``deflate.npz_parts``) and the writer threads only write; ``np.load`` gives the same ``data``, the
+        ``.pkl`` is the same, only the bytes of the ``.npz`` differ from the host route's."""
         from concurrent.futures import ThreadPoolExecutor
+        from .. import deflate
+        codes = deflate.codes_of(device_deflate)
         print("Initializing to run preprocessing")
         print("npz folder:", input_folder_with_cropped_npz)
         print("output_folder:", output_folder)
@@ -394,7 +425,9 @@ class GenericPreprocessor(object):
                 pending = deque()
                 for case_identifier in cases:
                     done = self._preprocess_cropped(target_spacings[i], case_identifier, input_folder_with_cropped_npz,
-                                                    force_separate_z, all_classes)
+                                                    force_separate_z, all_classes, keep_on_device=codes is not None)
+                    if codes is not None:
+                        done = (DeflatedCase(done[0], codes, unpack_npy), done[1])
                     while len(pending) >= workers:           # bounds the finished cases held in host memory
                         pending.popleft().result()
                     pending.append(pool.submit(self._write_case, *done, output_folder_stage, case_identifier, unpack_npy))
@@ -402,11 +435,12 @@ class GenericPreprocessor(object):
                     pending.popleft().result()
 
 
-def run_preprocessing(plans, folder_with_cropped_data, preprocessed_output_folder, num_threads=DEFAULT_NUM_THREADS, unpack_npy=False):
+def run_preprocessing(plans, folder_with_cropped_data, preprocessed_output_folder, num_threads=DEFAULT_NUM_THREADS, unpack_npy=False,
+                      device_deflate=False):
     """ExperimentPlanner.run_preprocessing (experiment_planner_baseline_3DUNet.py:425-445) from a plans dict or plans file: copies
     ``gt_segmentations`` when the cropped folder has one, then runs the plans' preprocessor over every stage's ``current_spacing``
     into ``<preprocessed_output_folder>/<data_identifier>_stage<i>``.  Plans that name another preprocessor than the two built
-    classes, or 2-D plans, raise NotImplementedError before any file is touched."""
+    classes, or 2-D plans, raise NotImplementedError before any file is touched.  ``device_deflate``: see ``GenericPreprocessor.run``."""
     if not isinstance(plans, dict):
         with open(plans, 'rb') as f:
             plans = pickle.load(f)
@@ -430,7 +464,8 @@ def run_preprocessing(plans, folder_with_cropped_data, preprocessed_output_folde
         num_threads = num_threads[-1]
     from ..paths import default_data_identifier
     preprocessor.run(target_spacings, folder_with_cropped_data, preprocessed_output_folder,
-                     plans.get('data_identifier', default_data_identifier), num_threads, unpack_npy=unpack_npy)
+                     plans.get('data_identifier', default_data_identifier), num_threads, unpack_npy=unpack_npy,
+                     device_deflate=device_deflate)
 
 
 class GenericPreprocessor_linearResampling(GenericPreprocessor):

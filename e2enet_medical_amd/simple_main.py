@@ -166,11 +166,12 @@ def main(argv=None):
             trainer.load_final_checkpoint(train=False)
     trainer.network.eval()
     if args.validation_only:
+        from . import deflate
         writer, gt_reader = select_validation_callbacks(args)
         trainer.validate(save_softmax=args.npz, validation_folder_name=args.val_folder,
                          run_postprocessing_on_folds=not args.disable_postprocessing_on_folds, overwrite=args.val_disable_overwrite,
                          determine_postprocessing=args.determine_postprocessing, writer=writer, gt_reader=gt_reader,
-                         device_deflate=args.device_deflate)
+                         device_deflate=deflate.from_args(args))
     print(f'finish training {args.Tconv} !!!')
     if network == '3d_lowres' and not args.disable_next_stage_pred:
         # reference :213-215: the validation cases of this fold, predicted and resampled for the full-resolution stage

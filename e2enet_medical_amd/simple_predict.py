@@ -91,7 +91,7 @@ def main(argv=None, reader=None, writer=None):
                             args.num_threads_nifti_save, None, args.part_id, args.num_parts, not args.disable_tta,
                             overwrite_existing=args.overwrite_existing, mode=args.mode, overwrite_all_in_gpu=all_in_gpu,
                             mixed_precision=not args.disable_mixed_precision, step_size=args.step_size, checkpoint_name=args.chk,
-                            writer=writer, reader=reader, device_deflate=args.device_deflate)
+                            writer=writer, reader=reader, device_deflate=deflate.from_args(args))
         lowres_segmentations = lowres_output_folder
         print("3d_lowres done")
     trainer_name = args.cascade_trainer_class_name if model == "3d_cascade_fullres" else args.trainer_class_name
@@ -103,7 +103,7 @@ def main(argv=None, reader=None, writer=None):
                                args.num_parts, not args.disable_tta, overwrite_existing=args.overwrite_existing, mode=args.mode,
                                overwrite_all_in_gpu=all_in_gpu, mixed_precision=not args.disable_mixed_precision,
                                step_size=args.step_size, checkpoint_name=args.chk, writer=writer, reader=reader,
-                               device_deflate=args.device_deflate, seg_reader=seg_reader)
+                               device_deflate=deflate.from_args(args), seg_reader=seg_reader)
 
 
 if __name__ == "__main__":

@@ -907,7 +907,8 @@ class nnUNetTrainer_simple(object):
 
         ``device_deflate`` (``simple_main --device_deflate``): the probabilities of ``save_softmax`` are rounded to fp16 and permuted
         on the device (``softmax_to_f16``) and deflated there (``deflate.savez``); only compressed bytes are downloaded.  ``np.load``
-        reads the array the default route stores, the archive's bytes differ."""
+        reads the array the default route stores, the archive's bytes differ.  ``True``: DEFLATE's fixed Huffman code;
+        ``"dynamic"`` (``--dynamic_huffman``): a code per chunk."""
         import json
         import shutil
         from ...inference.predict import export_segmentation
@@ -1008,7 +1009,7 @@ class nnUNetTrainer_simple(object):
                             from ... import deflate
                             from ...inference.predict import softmax_to_f16
                             dev = softmax.contiguous()
-                            deflate.savez(join(output_folder, fname + ".npz"),
+                            deflate.savez(join(output_folder, fname + ".npz"), codes=deflate.codes_of(device_deflate),
                                           softmax=softmax_to_f16(dev, [int(dev.shape[1 + i]) for i in tb],
                                                                  [int(dev.stride(1 + i)) for i in tb]))
                         else:

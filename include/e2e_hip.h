@@ -855,6 +855,32 @@ int e2e_deflate_encode(const void* src, long long nbytes, int elem, unsigned cha
 int e2e_deflate_gather(const unsigned char* slots, const unsigned* counts, const long long* offsets, long long nchunks,
                        unsigned char* out, long long out_bytes, void* stream);
 
+/* ---- N5b: the same stream with one Huffman code per chunk (csrc/deflate.hip) -------------------------------------------------
+ * e2e_deflate_encode_dynamic is e2e_deflate_encode with a third form of a chunk: one dynamic-Huffman block (RFC 1951, 3.2.7) over
+ * exactly the tokens of the fixed form, with a literal/length code built from the chunk's own token counts (symbol 256 counts
+ * once).  A chunk is written in the shortest of its three forms: fixed where fixed <= stored as before, dynamic only where it is
+ * strictly shorter than both others; kinds[nchunks] (bytes) receives 0 for stored, 1 for fixed, 2 for dynamic.  A chunk that is not
+ * dynamic carries the bytes e2e_deflate_encode gives it, so slots, counts, chunk_crcs, crc, the gather and the closing 03 00 are
+ * those of N5, and counts[c] never exceeds N5's.  tests/deflate_dynamic_oracle.py restates the format in Python.
+ *   code lengths, for the literal/length code (286 symbols, at most 15 bits) and the code-length code (19 symbols, at most 7):
+ *     the used symbols are ordered by count descending, equal counts by symbol number ascending; their counts go through the
+ *     two-queue Huffman construction, a leaf before an internal node of the same weight; only the number of leaves per depth is
+ *     kept.  Leaves deeper than the limit count at the limit, and for every 2^-limit that the Kraft sum then exceeds 1 by, the
+ *     deepest level below the limit that has a leaf gives one up: it becomes an internal node with two leaves one level down, one
+ *     of them taken from the limit's level (the step of zlib's gen_bitlen).  The lengths are then dealt out along the order,
+ *     shortest first: of two symbols with equal counts the smaller symbol number never has the longer code.  Codes are the
+ *     canonical ones of 3.2.2; both codes are complete.
+ *   distance code: one symbol, the one of distance elem (0, 1, 3, 5), with length 1 and HDIST = that symbol + 1, when the chunk has
+ *     a match (distance 8 carries its extra bit, set); HDIST = 1 and one zero length when it has none.
+ *   header: BFINAL 0, BTYPE 10, HLIT (the last used symbol, at least 257 symbols), HDIST, HCLEN (at least 4), the code-length
+ *     code's lengths in the permuted order, then the literal/length lengths and the distance lengths, each sequence on its own in
+ *     the run codes 16, 17, 18 as zlib's scan_tree cuts runs (zeros: up to 138 per code 18, 3..10 per code 17; a non-zero length
+ *     once and then up to 6 repeats per code 16).
+ *   ending: the end-of-block code, an empty stored block as byte alignment (00 00 FF FF), as in the fixed form.
+ * Refusals as e2e_deflate_encode's, and kinds null with nbytes > 0.                                                            */
+int e2e_deflate_encode_dynamic(const void* src, long long nbytes, int elem, unsigned char* slots, unsigned* counts,
+                               unsigned char* kinds, unsigned* chunk_crcs, unsigned* crc, void* stream);
+
 /* ---- N7: the two-stage cascade (csrc/cascade.hip) -------------------------------------------------------------------------------
  * Replaces: resample_and_save of the 3d_lowres hand-over (e2enet/training/cascade_stuff/predict_next_stage.py:31-43:
  * resample_data_or_seg(order 1) of the [K, ...] softmax on the host, argmax(0), uint8) and the three transforms of

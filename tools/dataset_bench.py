@@ -5,8 +5,11 @@
                                                       selection (events, ranks resident), wall time of class_locations with the
                                                       host's draw and the transfers, and the host time of the reference's method
                                                       (np.argwhere + RandomState.choice per class) on the same downloaded volume
-   python tools/dataset_bench.py run [threads]        GenericPreprocessor.run over a synthetic cropped folder: wall time per case,
-                                                      the share of the device half and of the compression + writing
+   python tools/dataset_bench.py run [threads] [--device_deflate | --dynamic_huffman]
+                                                      GenericPreprocessor.run over a synthetic cropped folder: wall time per case,
+                                                      the share of the device half and of the compression + writing, the bytes of
+                                                      the .npz files; with a switch the .npz is deflated on the device
+                                                      (run(device_deflate=True or "dynamic"))
    python tools/dataset_bench.py fingerprint          the dataset fingerprint of one 256 x 400 x 400 CT-like case (two modalities, about
                                                       30 % foreground): device time of the two sample passes, of the statistics over
                                                       the case's sample and over 100 copies of it behind one another, wall time of
@@ -111,9 +114,12 @@ def bench_select(kind):
                       "s_reference_method_host": round(s_host, 4), "threads": os.environ.get("OMP_NUM_THREADS")}))
 
 
-def bench_run(threads):
+def bench_run(threads, device_deflate=False):
     import torch
+    from e2enet_medical_amd import deflate
     from e2enet_medical_amd.preprocessing import GenericPreprocessor
+    from e2enet_medical_amd.preprocessing.preprocessing import DeflatedCase
+    codes = deflate.codes_of(device_deflate)
     shape, spacing, target, n_cases, classes = (64, 256, 256), (5.0, 0.8, 0.8), (2.5, 0.8, 0.8), 3, [1, 2, 3]
     rng = np.random.default_rng(3)
     with tempfile.TemporaryDirectory() as tmp:
@@ -128,7 +134,10 @@ def bench_run(threads):
         with open(os.path.join(cropped, "dataset_properties.pkl"), "wb") as f:
             pickle.dump({"all_classes": classes}, f)
         pre = GenericPreprocessor({0: "nonCT", 1: "nonCT"}, {0: True, 1: True}, [0, 1, 2])
-        pre._preprocess_cropped(np.array(target), "case_0", cropped, None, classes)          # code objects
+        warm = pre._preprocess_cropped(np.array(target), "case_0", cropped, None, classes, keep_on_device=codes is not None)
+        if codes is not None:
+            DeflatedCase(warm[0], codes)                                                     # code objects
+        del warm
         torch.cuda.synchronize()
         os.makedirs(out)
         s_load = s_dev = s_write = 0.0
@@ -136,9 +145,12 @@ def bench_run(threads):
             t0 = time.perf_counter()
             pre.load_cropped(cropped, "case_%d" % ci)
             t1 = time.perf_counter()
-            done = pre._preprocess_cropped(np.array(target), "case_%d" % ci, cropped, None, classes)
+            done = pre._preprocess_cropped(np.array(target), "case_%d" % ci, cropped, None, classes, keep_on_device=codes is not None)
             torch.cuda.synchronize()
             t2 = time.perf_counter()
+            shape_out = list(done[0].shape)
+            if codes is not None:                                # (the device's deflate counts as compression + writing)
+                done = (DeflatedCase(done[0], codes), done[1])
             pre._write_case(*done, out, "case_%d" % ci)
             t3 = time.perf_counter()
             s_load += t1 - t0
@@ -147,9 +159,11 @@ def bench_run(threads):
         walls = {}
         for th in threads:
             t0 = time.perf_counter()
-            pre.run([np.array(target)], cropped, os.path.join(tmp, "run%d" % th), "bench", th)
+            pre.run([np.array(target)], cropped, os.path.join(tmp, "run%d" % th), "bench", th, device_deflate=device_deflate)
             walls[str(th)] = round((time.perf_counter() - t0) / n_cases, 3)
-        print(json.dumps({"mode": "run", "cases": n_cases, "cropped_shape": [3] + list(shape), "resampled_shape": list(done[0].shape),
+        npz_bytes = sum(os.path.getsize(os.path.join(out, "case_%d.npz" % ci)) for ci in range(n_cases)) // n_cases
+        print(json.dumps({"mode": "run", "device_deflate": device_deflate, "cases": n_cases, "cropped_shape": [3] + list(shape),
+                          "resampled_shape": shape_out, "npz_bytes_per_case": npz_bytes,
                           "s_per_case_read_cropped_npz": round(s_load / n_cases, 3),
                           "s_per_case_device_half_incl_transfers": round(s_dev / n_cases, 3),
                           "s_per_case_savez_and_pickle": round(s_write / n_cases, 3), "s_per_case_run_by_threads": walls,
@@ -276,7 +290,8 @@ def main(argv):
     elif mode == "fingerprint":
         bench_fingerprint()
     else:
-        bench_run([int(v) for v in argv[1:]] or [1, 8])
+        flag = "dynamic" if "--dynamic_huffman" in argv else "--device_deflate" in argv
+        bench_run([int(v) for v in argv[1:] if not v.startswith("--")] or [1, 8], flag)
 
 
 if __name__ == "__main__":

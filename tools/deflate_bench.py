@@ -4,15 +4,16 @@
    python tools/deflate_bench.py OUT [--shape D H W] [--classes K] [--repeats R] [--npz FILE ...] [--skip labels|probs]
 
    labels   a synthetic uint8 label volume (blobs of K - 1 classes in background, shape + (6, 12, 12) as an uncropped case has):
-            nifti.write (download, gzip level 6 on the host)             against   nifti.write(device_deflate=True)
+            nifti.write (download, gzip level 6 on the host)   against   nifti.write(device_deflate=True)  and  (device_deflate="dynamic")
    probs    synthetic fp16 class probabilities [K, D, H, W] (confident over smooth regions, noisy at the borders):
-            download + np.savez_compressed (what save_softmax_npz does)  against   deflate.savez
-   --npz    the first array of a real .npz (a saved prediction), uploaded once before the clock starts: the same two routes
+            download + np.savez_compressed (what save_softmax_npz does)   against   deflate.savez  and  deflate.savez(codes="dynamic")
+   --npz    the first array of a real .npz (a saved prediction), uploaded once before the clock starts: the same three routes
 
 Every route starts from the tensor resident on the device and ends with the closed file, so the time includes the download and the
-write.  Host clock around work that ends in a device synchronise; one warm-up of each route, then R repeats with the two routes
-alternating; median, minimum and maximum are reported.  The device route is also split: the two encoder passes and the CRC (device
-events) and the bytes that cross the link.  Each case prints one JSON line.  Needs a GPU: there is no fallback."""
+write.  Host clock around work that ends in a device synchronise; one warm-up of each route, then R repeats with the three routes
+alternating; median, minimum and maximum are reported.  The device routes are also split: the two encoder passes and the CRC (device
+events), the bytes that cross the link, and for the dynamic codes the share of chunks per form (stored, fixed, dynamic).  Each case
+prints one JSON line.  Needs a GPU: there is no fallback."""
 import argparse
 import json
 import os
@@ -47,16 +48,17 @@ def _alternate(routes, repeats):
     return {name: dict(_stats(times[name]), file_bytes=sizes[name]) for name in routes}
 
 
-def _device_split(dev, repeats):
-    """the device route's own parts: encoder + CRC kernels and the gather (device events), compressed bytes downloaded"""
+def _device_split(dev, repeats, codes="fixed"):
+    """a device route's own parts: encoder + CRC kernels and the gather (device events), compressed bytes downloaded, and the share
+    of chunks per form"""
     import torch
     from e2enet_medical_amd import deflate
-    deflate.raw_deflate(dev)
+    kinds = deflate.chunk_kinds(dev, None, codes)
     ms, nbytes = [], 0
     for _ in range(repeats):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        stream, _, _ = deflate.raw_deflate(dev)
+        stream, _, _ = deflate.raw_deflate(dev, None, codes)
         e1.record()
         torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
@@ -64,7 +66,9 @@ def _device_split(dev, repeats):
     raw = dev.numel() * dev.element_size()
     return {"raw_deflate_ms_median": round(float(np.median(ms)), 3), "raw_deflate_ms_min": round(min(ms), 3),
             "raw_deflate_ms_max": round(max(ms), 3), "input_bytes": raw, "stream_bytes": nbytes,
-            "input_gb_per_s": round(raw / (float(np.median(ms)) * 1e-3) / 1e9, 2)}
+            "input_gb_per_s": round(raw / (float(np.median(ms)) * 1e-3) / 1e9, 2),
+            "chunk_share": {name: round(float((kinds == k).mean()), 4) if kinds.size else 0.0
+                            for k, name in enumerate(("stored", "fixed", "dynamic"))}}
 
 
 def labels(out, shape, classes, repeats):
@@ -76,7 +80,7 @@ def labels(out, shape, classes, repeats):
     seg = torch.clamp((field - 0.6) * (classes - 1) / 2.4, 0, classes - 1).to(torch.uint8).contiguous()
     del zz, yy, xx, field
     props = {"itk_spacing": (0.8, 0.8, 2.0), "itk_origin": (0., 0., 0.), "itk_direction": (1., 0., 0., 0., 1., 0., 0., 0., 1.)}
-    a, b = os.path.join(out, "labels_host.nii.gz"), os.path.join(out, "labels_device.nii.gz")
+    a, b, c = (os.path.join(out, "labels_%s.nii.gz" % n) for n in ("host", "device", "dynamic"))
 
     def host():
         nifti.write(seg, a, props)
@@ -85,17 +89,23 @@ def labels(out, shape, classes, repeats):
     def device():
         nifti.write(seg, b, props, device_deflate=True)
         return b
+
+    def dynamic():
+        nifti.write(seg, c, props, device_deflate="dynamic")
+        return c
     rec = {"case": "labels", "shape": [D, H, W], "foreground_share": round(float((seg != 0).float().mean().item()), 3)}
-    rec.update(_alternate({"host_gzip6": host, "device_deflate": device}, repeats))
+    rec.update(_alternate({"host_gzip6": host, "device_deflate": device, "device_dynamic": dynamic}, repeats))
     rec["device_parts"] = _device_split(seg, repeats)
+    rec["dynamic_parts"] = _device_split(seg, repeats, "dynamic")
     import gzip
-    rec["same_content"] = gzip.decompress(open(a, "rb").read()) == gzip.decompress(open(b, "rb").read())
+    rec["same_content"] = gzip.decompress(open(a, "rb").read()) == gzip.decompress(open(b, "rb").read()) == \
+        gzip.decompress(open(c, "rb").read())
     return rec
 
 
 def _probs_routes(out, tag, dev, repeats):
     from e2enet_medical_amd import deflate
-    a, b = os.path.join(out, tag + "_host.npz"), os.path.join(out, tag + "_device.npz")
+    a, b, c = (os.path.join(out, tag + "_%s.npz" % n) for n in ("host", "device", "dynamic"))
     downloads = []
 
     def host():
@@ -108,11 +118,17 @@ def _probs_routes(out, tag, dev, repeats):
     def device():
         deflate.savez(b, softmax=dev)
         return b
-    rec = _alternate({"host_savez_compressed": host, "device_deflate": device}, repeats)
+
+    def dynamic():
+        deflate.savez(c, codes="dynamic", softmax=dev)
+        return c
+    rec = _alternate({"host_savez_compressed": host, "device_deflate": device, "device_dynamic": dynamic}, repeats)
     rec["host_savez_compressed"]["of_which_download_s_median"] = round(float(np.median(downloads[1:])), 4)
     rec["device_parts"] = _device_split(dev, repeats)
-    x, y = np.load(a)["softmax"], np.load(b)["softmax"]
-    rec["same_content"] = bool(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes())
+    rec["dynamic_parts"] = _device_split(dev, repeats, "dynamic")
+    x = np.load(a)["softmax"]
+    rec["same_content"] = all(bool(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes())
+                              for y in (np.load(b)["softmax"], np.load(c)["softmax"]))
     return rec
 
 
