@@ -17,17 +17,19 @@
 // first walk also counts the tokens into an LDS histogram (ds_add); the code is built between two walks (a rank per lane, the
 // tree and the header's run codes in lane 0: at most 286 symbols); a walk with the new lengths and a second prefix sum size the
 // dynamic form, and the chunk is written in the shortest of the three forms.  What both kernels do is one set of functions below.
+//
+// e2e_crc32 is the two CRC kernels on their own (launch_crc), for a buffer that inflate.hip wrote; the way back is that file.
 #include "e2e_common.h"
+#include "e2e_deflate.h"
 
 #include <cstdint>
 
 namespace {
 
-constexpr int CHUNK = 32768;                       // bytes per chunk (<= 65535: a stored block's LEN is 16 bits).  32768 = 127 * 258 + 2:
-                                                   // a chunk of one value is 127 matches and a match or two literals
+using e2e::deflate::CHUNK;                         // (the format's constants: e2e_deflate.h, shared with inflate.hip)
+using e2e::deflate::STORED_EXTRA;
 constexpr int THREADS = 512;
 constexpr int PER = CHUNK / THREADS;               // 64: one mask bit per byte in one 64-bit word
-constexpr int STORED_EXTRA = 5;                    // header byte, LEN, NLEN
 constexpr int SLOT = (CHUNK + STORED_EXTRA + 15) / 16 * 16;
 constexpr int OUT_WORDS = SLOT / 4 + 2;            // the fixed form is written only when it is no longer than the stored one,
                                                    // so every token (and the word its last bits spill into) lands inside
@@ -697,6 +699,16 @@ __global__ __launch_bounds__(THREADS) void deflate_gather_kernel(const unsigned 
   }
 }
 
+// zlib.crc32 of nbytes > 0 bytes: one raw CRC per chunk, then the fold (the encoders and e2e_crc32)
+int launch_crc(const unsigned char* p, long long nbytes, unsigned* chunk_crcs, unsigned* crc, hipStream_t st) {
+  const long long nchunks = e2e::cdivll(nbytes, CHUNK);
+  hipLaunchKernelGGL(deflate_crc_kernel, dim3((unsigned)nchunks), dim3(THREADS), 0, st, p, nbytes, chunk_crcs);
+  const int rc = e2e::check_launch("deflate_crc_kernel");
+  if (rc != E2E_OK) return rc;
+  hipLaunchKernelGGL(deflate_crc_combine_kernel, dim3(1), dim3(THREADS), 0, st, chunk_crcs, nchunks, nbytes, crc);
+  return e2e::check_launch("deflate_crc_combine_kernel");
+}
+
 // both encoder entries: the same refusals, the same CRC kernels; only the dynamic one writes kinds
 int encode(const char* what, bool dynamic, const void* src, long long nbytes, int elem, unsigned char* slots, unsigned* counts,
            unsigned char* kinds, unsigned* chunk_crcs, unsigned* crc, void* stream) {
@@ -733,14 +745,23 @@ int encode(const char* what, bool dynamic, const void* src, long long nbytes, in
     rc = e2e::check_launch("deflate_encode_kernel");
   }
   if (rc != E2E_OK) return rc;
-  hipLaunchKernelGGL(deflate_crc_kernel, grid, block, 0, st, p, nbytes, chunk_crcs);
-  rc = e2e::check_launch("deflate_crc_kernel");
-  if (rc != E2E_OK) return rc;
-  hipLaunchKernelGGL(deflate_crc_combine_kernel, dim3(1), block, 0, st, chunk_crcs, nchunks, nbytes, crc);
-  return e2e::check_launch("deflate_crc_combine_kernel");
+  return launch_crc(p, nbytes, chunk_crcs, crc, st);
 }
 
 }  // namespace
+
+extern "C" int e2e_crc32(const void* buf, long long nbytes, unsigned* chunk_crcs, unsigned* crc, void* stream) {
+  const char* what = "crc32";
+  const hipStream_t st = (hipStream_t)stream;
+  E2E_REQUIRE(nbytes >= 0 && nbytes <= (1ll << 37), "%s: %lld bytes, at most 2^37", what, nbytes);
+  E2E_REQUIRE(crc != nullptr, "%s: null pointer", what);
+  if (nbytes == 0) {
+    hipLaunchKernelGGL(deflate_crc_zero_kernel, dim3(1), dim3(1), 0, st, crc);
+    return e2e::check_launch("deflate_crc_zero_kernel");
+  }
+  E2E_REQUIRE(buf && chunk_crcs, "%s: null pointer", what);
+  return launch_crc((const unsigned char*)buf, nbytes, chunk_crcs, crc, st);
+}
 
 extern "C" int e2e_deflate_chunk_bytes(void) { return CHUNK; }
 extern "C" int e2e_deflate_slot_bytes(void) { return SLOT; }

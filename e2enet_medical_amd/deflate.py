@@ -14,9 +14,14 @@ over it; only compressed bytes cross the link.
 A container member is ``host prefix + device buffer``: the prefix (a NIfTI header, a ``.npy`` header) goes through host zlib as a raw
 stream ended with a sync flush, which leaves it byte-aligned and not final; the device's chunks follow, every one byte-aligned and not
 final; ``03 00`` -- an empty final fixed-Huffman block -- closes the stream.  The CRC-32 of the member is combined from the prefix's
-and the device's with the GF(2) shift operator (``crc32_combine``; Python's zlib module does not export zlib's)."""
+and the device's with the GF(2) shift operator (``crc32_combine``; Python's zlib module does not export zlib's).
+
+The way back is here too (csrc/inflate.hip; opt-in, ``device_inflate=True`` / ``--device_inflate``): ``inflate`` turns the device
+part of a member into a device tensor, one wave per chunk, and ``load_npz`` is ``np.load`` for the ``.npz`` files written above,
+with every other member read by ``np.load`` itself."""
 import argparse
 import io
+import re
 import struct
 import zlib
 
@@ -285,6 +290,331 @@ def npz_parts(codes="fixed", **arrays):
         body, crc, nbytes = _raw_body(a, None, "deflate.savez(%s)" % key, codes)
         members.append((key,) + member_stream(npy_header(_TORCH_TO_NUMPY[str(a.dtype)], a.shape), body, crc, nbytes))
     return _member_parts(members)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- inflate
+# The way back (csrc/inflate.hip): what the device wrote is a sequence of byte-aligned chunk records that need nothing from each
+# other but the 8 bytes in front of them, so the device inflates them one wave each.  The stream carries no index of where records
+# start.  The host therefore proposes candidate offsets, ``e2e_inflate_scan`` parses one record at each, and the chain of valid
+# records is walked from offset 0 on the downloaded table.  A stream that is not this encoder's fails one of the checks before
+# anything is written, and ``inflate`` returns None: the caller inflates on the host, with the same result.
+CHUNK = 32768                            # e2e_deflate_chunk_bytes(), asserted where the library is loaded
+TAIL = 8                                 # bytes in front of a record that its matches may read (distances 1, 2, 4, 8)
+RECORD_WORDS = 8                         # one scan record (include/e2e_hip.h, N8)
+DEP_VALUE = 15                           # a nibble of a record's tail descriptor: the byte is a value, not a byte of the tail before
+_MARKER = re.compile(b"\x00\x00\xff\xff")          # the empty stored block that closes a Huffman record (and whatever looks like it)
+
+
+def candidate_cap(nbytes, chunk=CHUNK):
+    """how many candidate starts ``inflate`` scans at most: 8 per record and 64"""
+    return 8 * (-(-int(nbytes) // chunk)) + 64
+
+
+def candidate_starts(stream, nbytes, chunk=CHUNK):
+    """Sorted offsets at which a record may start, or None when there are more than ``candidate_cap``: offset 0, the byte behind
+    every ``00 00 FF FF``, and transitively the byte behind every candidate that looks like a stored block (first byte 0, LEN =
+    ~NLEN, 0 < LEN <= chunk): a stored record is not followed by the marker, so the record behind it is found only this way."""
+    n, cap = len(stream), candidate_cap(nbytes, chunk)
+    if n == 0:
+        return []
+    found = {0}
+    for m in _MARKER.finditer(stream):
+        if m.end() < n:
+            found.add(m.end())
+            if len(found) > cap:
+                return None
+    first = np.fromiter(found, dtype=np.int64, count=len(found))
+    view = stream if isinstance(stream, np.ndarray) else np.frombuffer(stream, dtype=np.uint8)
+    todo = first[view[first] == 0].tolist()            # (only a candidate whose first byte is 0 can look like a stored block)
+    while todo:
+        s = todo.pop()
+        head = bytes(stream[s:s + 5])
+        if len(head) < 5 or head[0] != 0:
+            continue
+        length, nlength = struct.unpack("<HH", head[1:])
+        t = s + 5 + length
+        if length == (~nlength & 0xFFFF) and 0 < length <= chunk and t < n and t not in found:
+            found.add(t)
+            todo.append(t)
+            if len(found) > cap:
+                return None
+    return sorted(found)
+
+
+def unpack_record(words):
+    """one scan record as a dict: ``ok``, and for a valid record ``kind``, ``d``, ``reach``, ``length``, ``end`` and ``tail``, the
+    last 8 output bytes oldest first, each ``(value, None)`` or ``(None, j)`` = byte j of the 8 bytes in front of the record"""
+    w = [int(v) for v in words]
+    if w[0] != 0:
+        return {"ok": False}
+    vals = struct.pack("<II", w[5], w[6])
+    deps = [(w[7] >> (4 * i)) & 15 for i in range(TAIL)]
+    return {"ok": True, "kind": w[1] & 0xFF, "d": (w[1] >> 8) & 0xFF, "reach": (w[1] >> 16) & 0xFF, "length": w[2],
+            "end": w[3] | (w[4] << 32), "tail": [(vals[i], None) if deps[i] == DEP_VALUE else (None, deps[i]) for i in range(TAIL)]}
+
+
+def inflate_plan(stream, nbytes, scan, chunk=CHUNK):
+    """The host half of ``inflate``: ``(starts int64 [n], prev_tails uint8 [n, 8], candidates)`` of the n = ceil(nbytes / chunk)
+    records of ``stream``, or None when the stream is not a chain of this encoder's records: too many candidates, a record that is
+    invalid or missing where the one before ends, a record whose output is not a whole chunk (the last: the remainder), a first
+    record that reads in front of itself, a chain that does not end with the stream.  ``scan(stream, starts) -> uint32 [len(starts),
+    8]`` parses one record per candidate (the device's ``e2e_inflate_scan``; ``tests/inflate_oracle.py`` without one).
+    prev_tails[k] are the 8 bytes in front of record k: the tail descriptors resolved with a forward fill per byte index."""
+    nbytes = int(nbytes)
+    nrec = -(-nbytes // chunk)
+    if nbytes < 0 or (nbytes == 0) != (len(stream) == 0):
+        return None
+    if nbytes == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros((0, TAIL), dtype=np.uint8), 0
+    cands = candidate_starts(stream, nbytes, chunk)
+    if cands is None:
+        return None
+    cands = np.asarray(cands, dtype=np.int64)
+    ncand = len(cands)
+    table = np.ascontiguousarray(np.asarray(scan(stream, cands), dtype=np.uint32).reshape(ncand, RECORD_WORDS))
+    # the chain: every valid record points at the candidate that is its end (whole arrays; the walk itself is a loop over ints)
+    ok = table[:, 0] == 0
+    ends = table[:, 3].astype(np.int64) | (table[:, 4].astype(np.int64) << 32)
+    at = np.minimum(np.searchsorted(cands, ends), ncand - 1)
+    follower = np.where(ok & (cands[at] == ends), at, -1).tolist()
+    chain, i = [], 0                                  # (candidate 0 is offset 0)
+    for k in range(nrec):
+        if i < 0 or not ok[i]:
+            return None
+        chain.append(i)
+        i = follower[i]
+    chain = np.asarray(chain, dtype=np.int64)
+    lengths = table[chain, 2].astype(np.int64)
+    if (lengths[:-1] != chunk).any() or lengths[-1] != nbytes - (nrec - 1) * chunk or ends[chain[-1]] != len(stream) \
+            or (table[chain[0], 1] >> 16) & 0xFF:
+        return None
+    # the tails: values where the record has them; a dependent byte takes byte j of the resolved tail in front (records in order)
+    resolved = np.ascontiguousarray(table[chain, 5:7]).view(np.uint8).reshape(nrec, TAIL).copy()
+    deps = (table[chain, 7][:, None] >> (4 * np.arange(TAIL, dtype=np.uint32))[None, :]) & 15
+    rows = np.flatnonzero((deps != DEP_VALUE).any(axis=1)).tolist()
+    if rows:
+        res, dep = resolved.tolist(), deps.tolist()
+        for k in rows:
+            front = res[k - 1] if k else [0] * TAIL
+            res[k] = [v if j == DEP_VALUE else front[j & 7] for v, j in zip(res[k], dep[k])]
+        resolved = np.asarray(res, dtype=np.uint8).reshape(nrec, TAIL)
+    tails = np.zeros((nrec, TAIL), dtype=np.uint8)
+    tails[1:] = resolved[:-1]
+    return cands[chain], tails, ncand
+
+
+def _byte_array(stream):
+    """the stream as a writable uint8 array (torch.from_numpy does not take a read-only one silently)"""
+    a = stream if isinstance(stream, np.ndarray) else np.frombuffer(stream, dtype=np.uint8)
+    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise ValueError("inflate: the stream must be bytes or a contiguous uint8 array")
+    return a if a.flags.writeable else a.copy()
+
+
+def inflate(stream, nbytes, device="cuda", stats=None, scan=None, chunks=None):
+    """The ``nbytes`` bytes that the chunk records ``stream`` inflate to, as a uint8 device tensor; ``stream`` is what
+    ``raw_deflate`` returns without its closing ``03 00`` (the device part of a member).  None when the stream is not a chain of
+    this encoder's records (``inflate_plan``); nothing has been written then and host zlib gives the result.  A ValueError when a
+    record of the chain turns out corrupt on the second, writing pass (``e2e_inflate_chunks`` trusts nothing of the scan).
+    ``stats`` (a dict) receives ``candidates`` and ``records``.  ``scan`` and ``chunks`` replace the two device steps (tests without
+    a device): ``scan`` as in ``inflate_plan``, ``chunks(stream, starts, prev_tails, nbytes) -> the result``."""
+    nbytes = int(nbytes)
+    data = _byte_array(stream)
+    dev = {}
+
+    def upload():
+        import torch
+        from ._lib import lib
+        if "comp" not in dev:
+            dev["lib"], dev["torch"] = lib(), torch
+            assert int(dev["lib"].deflate_chunk_bytes()) == CHUNK and int(dev["lib"].inflate_record_words()) == RECORD_WORDS
+            dev["comp"] = torch.from_numpy(data).to(device)
+            dev["stream"] = torch.cuda.current_stream(dev["comp"].device).cuda_stream
+        return dev["lib"], dev["torch"], dev["comp"], dev["stream"]
+
+    def device_scan(_, starts):
+        L, torch, comp, st = upload()
+        with torch.cuda.device(comp.device):
+            starts_d = torch.from_numpy(starts).to(comp.device)
+            records = torch.empty((len(starts), RECORD_WORDS), dtype=torch.int32, device=comp.device)
+            L.inflate_scan(comp.data_ptr(), comp.numel(), starts_d.data_ptr(), len(starts), records.data_ptr(), st)
+            return records.cpu().numpy().view(np.uint32)
+
+    def device_chunks(_, starts, tails, nbytes):
+        L, torch, comp, st = upload()
+        with torch.cuda.device(comp.device):
+            out = torch.empty(nbytes, dtype=torch.uint8, device=comp.device)
+            status = torch.empty(1, dtype=torch.int32, device=comp.device)
+            starts_d, tails_d = torch.from_numpy(starts).to(comp.device), torch.from_numpy(tails).to(comp.device)
+            L.inflate_chunks(comp.data_ptr() if len(starts) else None, comp.numel(), starts_d.data_ptr() if len(starts) else None,
+                             tails_d.data_ptr() if len(starts) else None, len(starts), out.data_ptr() if nbytes else None, nbytes,
+                             status.data_ptr(), st)
+            bad = int(status.item())
+            if bad:
+                raise ValueError("inflate: %d of %d records are corrupt" % (bad, len(starts)))
+            return out
+
+    plan = inflate_plan(data, nbytes, device_scan if scan is None else scan)
+    if plan is None:
+        return None
+    starts, tails, ncand = plan
+    if stats is not None:
+        stats["candidates"], stats["records"] = ncand, len(starts)
+    return (device_chunks if chunks is None else chunks)(data, starts, tails, nbytes)
+
+
+def device_crc32(tensor):
+    """``zlib.crc32`` of the bytes of a contiguous device tensor (``e2e_crc32``: the encoder's two CRC kernels)"""
+    import torch
+    from ._lib import lib
+    nbytes, _ = _as_device_bytes(tensor, 1, "device_crc32")
+    with torch.cuda.device(tensor.device):
+        crc = torch.empty(1, dtype=torch.int32, device=tensor.device)
+        work = torch.empty(max(1, -(-nbytes // CHUNK)), dtype=torch.int32, device=tensor.device)
+        lib().crc32(tensor.data_ptr() if nbytes else None, nbytes, work.data_ptr(), crc.data_ptr(),
+                    torch.cuda.current_stream(tensor.device).cuda_stream)
+        return int(crc.item()) & 0xFFFFFFFF
+
+
+# ------------------------------------------------------------------------------------------------------------------ reading npz
+_NUMPY_TO_TORCH = {np.dtype(v): k for k, v in _TORCH_TO_NUMPY.items()}
+_HEAD_WINDOW = 1 << 16                   # compressed bytes looked at for a member's .npy header
+
+
+class NpzMember:
+    """One ``<key>.npy`` of an archive as ``read_npz_raw`` found it.  ``stream`` is the member's raw DEFLATE stream (a view of the
+    file's bytes).  ``body`` is the device part of it and ``header`` the .npy header in front when the member is laid out as this
+    package's writers lay it out (``member_stream``); otherwise ``body`` is None and ``why`` says what was different."""
+
+    def __init__(self, key, crc, size):
+        self.key, self.crc, self.size = key, crc, size
+        self.stream = self.body = self.header = self.dtype = self.shape = None
+        self.nbytes = 0
+        self.why = None
+
+
+class NpzRaw:
+    """what ``read_npz_raw`` returns: the file's bytes, and its members by key in directory order"""
+
+    def __init__(self, path, data, members):
+        self.path, self.data, self.members = path, data, members
+
+
+def _npy_header(stream):
+    """``(header bytes, dtype, shape, fortran_order)`` from the front of a member's raw stream, or None: the magic, the version and
+    the header's own length are inflated under ``max_length``, so only the header is ever inflated on the host"""
+    d = zlib.decompressobj(-15)
+    try:
+        head = d.decompress(bytes(stream[:_HEAD_WINDOW]), 10)
+        if len(head) < 10 or head[:6] != b"\x93NUMPY" or head[6] not in (1, 2):
+            return None
+        if head[6] == 2:
+            head += d.decompress(d.unconsumed_tail, 2)
+            if len(head) < 12:
+                return None
+        total = len(head) + (struct.unpack("<H", head[8:10])[0] if head[6] == 1 else struct.unpack("<I", head[8:12])[0])
+        if total > _HEAD_WINDOW:
+            return None
+        head += d.decompress(d.unconsumed_tail, total - len(head))
+        if len(head) != total:
+            return None
+        f = io.BytesIO(head)
+        version = np.lib.format.read_magic(f)
+        shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0)(f)
+    except (zlib.error, ValueError):
+        return None
+    return head, dtype, tuple(int(v) for v in shape), bool(fortran)
+
+
+def read_npz_raw(path):
+    """The host-only half of ``load_npz``, for a read-ahead thread (it shares no state and touches no device): the file's bytes, the
+    zip directory, and per member the .npy header and where the device part of its stream lies."""
+    import zipfile
+    path = str(path)
+    data = np.fromfile(path, dtype=np.uint8)
+    members = {}
+    with zipfile.ZipFile(path) as z:
+        infos = z.infolist()
+    for info in infos:
+        key = info.filename[:-4] if info.filename.endswith(".npy") else info.filename
+        m = members[key] = NpzMember(key, info.CRC, info.file_size)
+        o = info.header_offset
+        if o + 30 > data.size or bytes(data[o:o + 4]) != b"PK\x03\x04":
+            raise ValueError("%s: member %s has no local header at %d" % (path, key, o))
+        name_len, extra_len = struct.unpack("<HH", bytes(data[o + 26:o + 30]))
+        first = o + 30 + name_len + extra_len
+        if first + info.compress_size > data.size:
+            raise ValueError("%s: member %s runs past the end of the file" % (path, key))
+        m.stream = data[first:first + info.compress_size]
+        if info.compress_type != zipfile.ZIP_DEFLATED or not info.filename.endswith(".npy"):
+            m.why = "not a deflated .npy member"
+            continue
+        parsed = _npy_header(m.stream)
+        if parsed is None:
+            m.why = "no .npy header of version 1 or 2 at the front of the stream"
+            continue
+        head, dtype, shape, fortran = parsed
+        m.dtype, m.shape = dtype, shape
+        m.nbytes = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
+        prefix = deflate_prefix(head)
+        if fortran or dtype.hasobject or dtype not in _NUMPY_TO_TORCH:
+            m.why = "Fortran order, or a dtype without a device tensor"
+        elif len(head) + m.nbytes != info.file_size:
+            m.why = "the member's length is not header + array"
+        elif m.stream.size < len(prefix) + len(STREAM_END) or bytes(m.stream[:len(prefix)]) != prefix:
+            m.why = "the stream does not begin with the header as its own sync-flushed block"
+        elif bytes(m.stream[-len(STREAM_END):]) != STREAM_END:
+            m.why = "the stream does not end with 03 00"
+        else:
+            m.header, m.body = head, m.stream[len(prefix):m.stream.size - len(STREAM_END)]
+    return NpzRaw(path, data, members)
+
+
+def load_npz(path, keys=None, device="cuda", stats=None, inflater=None):
+    """``np.load(path)`` as a dict of device tensors, the members this package's writers deflated (``savez``, ``-z`` with
+    ``--device_deflate``, stage folders) inflated on the device: only compressed bytes cross the link and the host inflates a few
+    hundred header bytes.  ``path``: a file, or what ``read_npz_raw`` returned for it.  ``keys``: the members wanted, default all.
+    Any other member (``np.savez_compressed``'s, a stored one, Fortran order, a stream with too many candidate offsets) takes
+    ``np.load`` and an upload, with the same result.  A device-route member whose bytes do not give the directory's CRC-32, or whose
+    chain has a corrupt record, is a ValueError that names the file and the member.  ``stats`` (a dict) receives per member
+    ``route`` ("device" / "host"), ``candidates``, ``records``, ``compressed`` and ``inflated`` bytes.  ``inflater`` replaces
+    ``inflate`` and the CRC of its result: ``inflater(body, nbytes, stats) -> (tensor or None, crc32)`` (tests without a device)."""
+    import torch
+    raw = path if isinstance(path, NpzRaw) else read_npz_raw(path)
+    missing = [k for k in (keys or ()) if k not in raw.members]
+    if missing:
+        raise KeyError("%s: no member %s (it holds %s)" % (raw.path, ", ".join(missing), ", ".join(raw.members)))
+    out, host = {}, None
+    for key in (raw.members if keys is None else keys):
+        m = raw.members[key]
+        st = {"route": "host", "candidates": 0, "records": 0, "compressed": int(m.stream.size), "inflated": int(m.size)}
+        got = None
+        if m.body is not None:
+            try:
+                if inflater is None:
+                    got = inflate(m.body, m.nbytes, device, st)
+                    crc = device_crc32(got) if got is not None else 0
+                else:
+                    got, crc = inflater(m.body, m.nbytes, st)
+            except ValueError as e:
+                raise ValueError("%s: member %s: %s" % (raw.path, key, e)) from None
+            if got is not None:
+                if crc32_combine(zlib.crc32(m.header), crc, m.nbytes) != m.crc:
+                    raise ValueError("%s: member %s: the inflated bytes do not give the CRC-32 of the directory (%08x)"
+                                     % (raw.path, key, m.crc))
+                st["route"] = "device"
+                if isinstance(got, torch.Tensor):
+                    dtype = getattr(torch, _NUMPY_TO_TORCH[m.dtype][6:])
+                    # (an empty tensor has no stride to view by)
+                    got = got.view(dtype).reshape(m.shape) if m.nbytes else torch.empty(m.shape, dtype=dtype, device=got.device)
+        if got is None:
+            if host is None:
+                host = np.load(io.BytesIO(raw.data.tobytes()))
+            got = torch.from_numpy(np.ascontiguousarray(host[key])).to(device)
+        out[key] = got
+        if stats is not None:
+            stats[key] = st
+    return out
 
 
 class _DynamicHuffman(argparse.Action):

@@ -100,6 +100,19 @@ def _load_softmax(f):
     return np.load(f)['softmax']
 
 
+def _read_raw(f):
+    """the read-ahead half of ``--device_inflate``: file bytes, zip directory and .npy headers; no device"""
+    from .. import deflate
+    return deflate.read_npz_raw(f)
+
+
+def _inflate_softmax(raw):
+    """the other half, on the thread that owns the GPU: ``softmax`` of one file as a device tensor.  A file that the device
+    encoder did not write is inflated on the host inside ``load_npz``."""
+    from .. import deflate
+    return deflate.load_npz(raw, keys=("softmax",))["softmax"]
+
+
 def _load_properties(f):
     with open(f, 'rb') as fh:
         return pickle.load(fh)
@@ -147,22 +160,26 @@ def _written(out_file):
     return isfile(out_file) or isfile(out_file[:-7] + ".npy")          # (nifti_writer without SimpleITK stores <case>.npy)
 
 
-def merge_files(files, properties_files, out_file, override, store_npz, writer=None, postprocessing=None, postprocessed_file=None):
+def merge_files(files, properties_files, out_file, override, store_npz, writer=None, postprocessing=None, postprocessed_file=None,
+                device_inflate=False):
     """Reference :26-53 for one case.  ``postprocessing`` (as ``load_postprocessing`` returns it) with ``postprocessed_file``: the raw
-    label volume goes to ``out_file`` and the post-processed one to ``postprocessed_file``."""
+    label volume goes to ``out_file`` and the post-processed one to ``postprocessed_file``.  ``device_inflate``: as in ``merge``."""
     from .predict import nifti_writer
     _refuse_too_many(len(files))
     if not override and _written(out_file) and (postprocessing is None or _written(postprocessed_file)):
         return
-    softmax = [_load_softmax(f) for f in files]
+    softmax = [_inflate_softmax(_read_raw(f)) if device_inflate else _load_softmax(f) for f in files]
     props = [_load_properties(f) for f in properties_files]
     seg, raw, mean = _merge_loaded(softmax, props, files, store_npz, postprocessing)
     _write_case(seg, raw, mean, props, out_file, postprocessed_file, writer if writer is not None else nifti_writer())
 
 
-def merge(folders, output_folder, threads, override=True, postprocessing_file=None, store_npz=False, writer=None):
+def merge(folders, output_folder, threads, override=True, postprocessing_file=None, store_npz=False, writer=None,
+          device_inflate=False):
     """Reference :56-95.  With ``postprocessing_file`` the raw results go to ``<output_folder>/not_postprocessed``, the post-processed
-    ones to ``output_folder``, and the json is copied there."""
+    ones to ``output_folder``, and the json is copied there.  ``device_inflate``: the read-ahead threads only read the files
+    (``deflate.read_npz_raw``) and this thread inflates ``softmax`` on the device (``deflate.load_npz``) where the device encoder
+    wrote the file; the files written are those of the default route byte for byte."""
     from concurrent.futures import ThreadPoolExecutor
     from .predict import nifti_writer
     writer = writer if writer is not None else nifti_writer()
@@ -198,12 +215,12 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
         def read_ahead():
             job = next(todo, None)
             if job is not None:
-                loading.append((job, [pool.submit(_load_softmax, f) for f in job[0]]))
+                loading.append((job, [pool.submit(_read_raw if device_inflate else _load_softmax, f) for f in job[0]]))
         for _ in range(PREFETCH_CASES):
             read_ahead()
         while loading:
             (files, property_files, out_file, pp_file), reads = loading.popleft()
-            softmax = [r.result() for r in reads]
+            softmax = [_inflate_softmax(r.result()) if device_inflate else r.result() for r in reads]
             read_ahead()
             props = [_load_properties(f) for f in property_files]
             seg, raw, mean = _merge_loaded(softmax, props, files, store_npz, postprocessing)
@@ -232,6 +249,9 @@ def build_parser():
                         help="postprocessing.json of the ensemble; the raw results then go to <output_folder>/not_postprocessed")
     parser.add_argument('--npz', action="store_true", required=False,
                         help="also store the averaged probabilities (<case>.npz) and the list of properties (<case>.pkl)")
+    parser.add_argument('--device_inflate', action="store_true", required=False,
+                        help="inflate the npz files that --device_deflate wrote on the GPU: the threads only read them (other "
+                             "files are inflated on the host as before; the label volumes are the same)")
     from .. import nifti
     nifti.add_argument(parser)
     return parser
@@ -248,7 +268,7 @@ def select_writer(args, writer=None):
 def main(argv=None, writer=None):
     args = build_parser().parse_args(argv)
     merge(args.folders, args.output_folder, args.threads, override=True, postprocessing_file=args.postprocessing_file,
-          store_npz=args.npz, writer=select_writer(args, writer))
+          store_npz=args.npz, writer=select_writer(args, writer), device_inflate=args.device_inflate)
 
 
 if __name__ == "__main__":

@@ -67,6 +67,9 @@ def build_parser():
                         help='keep up to GIB GiB of preprocessed cases on the device and cut every training batch there with one '
                              'kernel launch (negative: no limit; 0: stage every case, still crop and pad on the device); '
                              'default: the host loader')
+    parser.add_argument('--device_inflate', action='store_true', default=False,
+                        help='with --resident_data: a case without an unpacked .npy is inflated from its .npz on the GPU (members '
+                             'that --device_deflate wrote; others are inflated on the host as before) instead of on the host')
     from . import deflate, nifti
     nifti.add_argument(parser)
     deflate.add_argument(parser)
@@ -118,6 +121,8 @@ def load_pretrained_weights(network, fname, verbose=False):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.device_inflate and args.resident_data is None:
+        parser.error("--device_inflate needs --resident_data: it inflates the cases that are kept on the device")
     print(args)
     task, fold, network = args.task, args.fold, args.network
     if not task.startswith("Task"):
@@ -134,6 +139,7 @@ def main(argv=None):
     trainer.base_num_features_override = args.base_num_features
     trainer.synthetic_data = bool(args.synthetic_data)
     trainer.resident_data_gib = args.resident_data
+    trainer.device_inflate = bool(args.device_inflate)
     if args.disable_saving:
         trainer.save_final_checkpoint = False
         trainer.save_best_checkpoint = False

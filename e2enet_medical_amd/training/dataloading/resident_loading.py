@@ -15,6 +15,7 @@ launch; the host keeps the ``numpy.random`` draws, a few dozen scalars per batch
 There is no CPU path: without a GPU the loader refuses to be built.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -27,20 +28,49 @@ _PAD_MODES = {"constant": 0, "edge": 1}
 
 class DeviceCaseCache:
     """budget_bytes: None keeps every case, 0 keeps none.  ``upload(array) -> device tensor`` is replaceable (tests of the
-    bookkeeping run without a GPU)."""
+    bookkeeping run without a GPU).  ``device_inflate``: a case that has no unpacked ``.npy`` is admitted from the shape in its
+    ``.npy`` header, before any device work, and its ``data`` member is inflated into HBM by ``deflate.load_npz`` (``loader``
+    replaces it in tests: ``loader(raw) -> tensor``) and converted to fp32 there; a member that is not this package's goes
+    through ``np.load`` inside ``load_npz``.  The cases on the device hold the same bits either way."""
 
-    def __init__(self, budget_bytes=None, device="cuda", upload=None):
+    def __init__(self, budget_bytes=None, device="cuda", upload=None, device_inflate=False, loader=None):
         if budget_bytes is not None and budget_bytes < 0:
             raise ValueError("budget_bytes %r: None means no limit, a number of bytes is not negative" % (budget_bytes,))
         self.budget_bytes = None if budget_bytes is None else int(budget_bytes)
         self.device = device
         self._upload = self._to_device if upload is None else upload
+        self.device_inflate = bool(device_inflate)
+        self._loader = self._inflate_to_device if loader is None else loader
+        self.inflated_cases = 0
         self._cases = {}
         self.resident_bytes = 0
 
     def _to_device(self, array):
         # (a copy: a memory-mapped case is read-only, which torch.from_numpy does not take silently; once per case)
         return torch.from_numpy(np.array(array, dtype=np.float32, order='C')).to(self.device)
+
+    def _inflate_to_device(self, raw):
+        from ... import deflate
+        return deflate.load_npz(raw, keys=("data",), device=self.device)["data"]
+
+    def _fetch_inflated(self, path):
+        """(case, resident) of a packed case under ``device_inflate``, or None where the host route has to take it: the archive has
+        no ``data`` member with a readable header, or the budget has no room"""
+        from ... import deflate
+        raw = deflate.read_npz_raw(path)
+        member = raw.members.get("data")
+        if member is None or member.shape is None:
+            return None
+        nbytes = int(np.prod(member.shape, dtype=np.int64)) * 4
+        if self.budget_bytes is not None and self.resident_bytes + nbytes > self.budget_bytes:
+            return None
+        case = self._loader(raw)
+        if case.dtype != torch.float32:
+            case = case.to(torch.float32)
+        self._cases[path] = case.contiguous()
+        self.resident_bytes += nbytes
+        self.inflated_cases += 1
+        return self._cases[path], True
 
     def __len__(self):
         return len(self._cases)
@@ -56,6 +86,10 @@ class DeviceCaseCache:
         case = self._cases.get(path)
         if case is not None:
             return case, True
+        if self.device_inflate and not os.path.isfile(path[:-4] + ".npy"):
+            got = self._fetch_inflated(path)
+            if got is not None:
+                return got
         host = _dl._load_case(entry, memmap_mode)
         nbytes = int(np.prod(host.shape)) * 4
         if self.budget_bytes is not None and self.resident_bytes + nbytes > self.budget_bytes:

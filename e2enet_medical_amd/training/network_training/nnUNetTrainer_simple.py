@@ -105,6 +105,7 @@ class nnUNetTrainer_simple(object):
         # GiB of preprocessed cases to keep on the device (training/dataloading/resident_loading.py): None is the host loader,
         # a negative number no limit, 0 stages every case but still crops and pads on the device
         self.resident_data_gib = None
+        self.device_inflate = False          # with resident_data: packed cases are inflated on the device
         self.num_input_channels = self.num_classes = self.net_pool_per_axis = self.patch_size = self.batch_size = \
             self.threeD = self.base_num_features = self.intensity_properties = self.normalization_schemes = \
             self.net_num_pool_op_kernel_sizes = self.net_conv_kernel_sizes = None
@@ -1140,12 +1141,15 @@ class nnUNetTrainer_simple(object):
         from ..dataloading.dataset_loading import DataLoader3D
         self.load_dataset()
         self.do_split()
+        if self.device_inflate and self.resident_data_gib is None:
+            raise ValueError("--device_inflate inflates the cases that --resident_data keeps on the device; "
+                             "without --resident_data there is nothing for it to do")
         if self.resident_data_gib is not None:
             from ..dataloading.resident_loading import DeviceCaseCache, ResidentDataLoader3D
             gib = float(self.resident_data_gib)
             # one cache for both loaders: fold 'all' trains and validates on the same cases
             cache = DeviceCaseCache(None if gib < 0 else int(gib * 2 ** 30), torch.device("cuda", torch.cuda.current_device())
-                                    if torch.cuda.is_available() else "cuda")
+                                    if torch.cuda.is_available() else "cuda", device_inflate=self.device_inflate)
             dl_tr = ResidentDataLoader3D(self.dataset_tr, self.basic_generator_patch_size, self.patch_size, self.batch_size, False,
                                          oversample_foreground_percent=self.oversample_foreground_percent, pad_mode="constant",
                                          pad_sides=self.pad_all_sides, memmap_mode='r', cache=cache)

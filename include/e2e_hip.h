@@ -881,6 +881,46 @@ int e2e_deflate_gather(const unsigned char* slots, const unsigned* counts, const
 int e2e_deflate_encode_dynamic(const void* src, long long nbytes, int elem, unsigned char* slots, unsigned* counts,
                                unsigned char* kinds, unsigned* chunk_crcs, unsigned* crc, void* stream);
 
+/* ---- N8: inflate on the device what N5 / N5b wrote (csrc/inflate.hip), and zlib's CRC-32 of a device buffer --------------------
+ * Replaces: the host's single-threaded zlib pass over a .npz member this package wrote, and the upload of the inflated bytes.
+ * General DEFLATE is serial; the stream of N5 is a sequence of byte-aligned chunk records, each inflating to exactly
+ * e2e_deflate_chunk_bytes() bytes (the last to the remainder), each one stored block or one fixed / dynamic Huffman block closed by
+ * the empty stored block 00 00 FF FF, every match of a record at one distance d of 1, 2, 4 or 8.  A record needs nothing from
+ * outside itself but the 8 bytes in front of it, so one wave inflates one record and no wave waits for another.  The stream has
+ * no index: the host proposes candidate offsets (e2enet_medical_amd/deflate.py), scan parses one record at each, the host walks
+ * the chain of valid records from offset 0 and resolves every record's 8 front bytes from the tail descriptors.
+ *   scan: records[c] (e2e_inflate_record_words() = 8 words) for the candidate starts[c] (64-bit byte offsets, device):
+ *     word 0  status: 0 a valid record, 1 invalid (all other words are 0 then);
+ *     word 1  kind (0 stored, 1 fixed, 2 dynamic) | d << 8 (0: no match) | reach << 16 (how many bytes in front of the record its
+ *             matches read, 0 .. 8);
+ *     word 2  output bytes, 1 .. chunk;  words 3, 4  the end offset (the byte behind the record), low and high half;
+ *     words 5, 6  the values and word 7 the dependences of the record's last 8 output bytes, oldest first: nibble i of word 7 is
+ *             15 when byte i of words 5, 6 is the value, else j = 0 .. 7 and the byte equals byte j of the 8 bytes in front of the
+ *             record (the byte of words 5, 6 is 0).  A record shorter than 8 bytes passes the front bytes on; a match copies the
+ *             dependence with the value, so the dependent bytes need not be a prefix of the record.
+ *     No output byte is written.  Invalid: BFINAL set; BTYPE 11; HLIT > 286 or HDIST > 30 symbols; a code-length or
+ *     literal/length code that is over-subscribed or incomplete, a distance code that is over-subscribed, or incomplete other than
+ *     by having one code of length 1 or none (zlib's rules); a repeat with nothing to repeat or lengths running over HLIT + HDIST;
+ *     no end-of-block code; a bit pattern without a symbol; a symbol > 285, a distance code > 29; a distance that is not 1, 2, 4
+ *     or 8, or two different distances; more than chunk output bytes, or none; a stored block with LEN != ~NLEN, LEN = 0 or
+ *     LEN > chunk; a Huffman block not followed by 000, padding and 00 00 FF FF; a record that ends behind ncomp (bytes behind
+ *     ncomp read as zeros meanwhile); a start outside [0, ncomp).
+ *   chunks: record k of the chain, at starts[k], is parsed again with the same rules (nothing of the scan is trusted) into an LDS
+ *     image that begins with prev_tails[k][8], the bytes in front of it (record 0: not read by a valid stream; a record 0 that
+ *     reaches in front of itself is bad), and the image is stored to out + k chunk when the record is valid and gives exactly
+ *     min(chunk, nbytes - k chunk) bytes.  Otherwise nothing of that record is stored and *status (device, zeroed by the call)
+ *     counts it.  nchunks = ceil(nbytes / chunk).  out is aligned to 16 bytes.
+ *   crc32: *crc (device) = zlib.crc32 of buf[0, nbytes); chunk_crcs[ceil(nbytes / chunk)] is workspace.  The kernels are those
+ *     of e2e_deflate_encode.  nbytes == 0 only sets *crc = 0.
+ * Refused with E2E_ERR_ARG before anything is launched: a null pointer, ncomp > 2^38, nbytes > 2^37, more than 2^26 candidates,
+ * nchunks != ceil(nbytes / chunk), starts not aligned to 8 bytes, out not aligned to 16.                                        */
+int e2e_inflate_record_words(void);
+int e2e_inflate_scan(const unsigned char* comp, long long ncomp, const long long* starts, long long nstarts, unsigned* records,
+                     void* stream);
+int e2e_inflate_chunks(const unsigned char* comp, long long ncomp, const long long* starts, const unsigned char* prev_tails,
+                       long long nchunks, unsigned char* out, long long nbytes, unsigned* status, void* stream);
+int e2e_crc32(const void* buf, long long nbytes, unsigned* chunk_crcs, unsigned* crc, void* stream);
+
 /* ---- N7: the two-stage cascade (csrc/cascade.hip) -------------------------------------------------------------------------------
  * Replaces: resample_and_save of the 3d_lowres hand-over (e2enet/training/cascade_stuff/predict_next_stage.py:31-43:
  * resample_data_or_seg(order 1) of the [K, ...] softmax on the host, argmax(0), uint8) and the three transforms of

@@ -132,7 +132,8 @@ def _probs_routes(out, tag, dev, repeats):
     return rec
 
 
-def probs(out, shape, classes, repeats):
+def synthetic_probs(shape, classes):
+    """the fp16 class probabilities [K, D, H, W] of the ``probs`` case on the device (tools/inflate_bench.py reads them back)"""
     import torch
     D, H, W = shape
     K = classes
@@ -145,7 +146,13 @@ def probs(out, shape, classes, repeats):
     logits = torch.stack([-(field * K / 6.0 + K / 2.0 - k) ** 2 for k in range(K)]) * 8.0
     logits += torch.rand(logits.shape, generator=g, device="cuda")
     dev.copy_(torch.softmax(logits, 0))
-    del logits, field
+    return dev
+
+
+def probs(out, shape, classes, repeats):
+    D, H, W = shape
+    K = classes
+    dev = synthetic_probs(shape, classes)
     rec = {"case": "probs", "shape": [K, D, H, W], "dtype": "float16",
            "share_exactly_0_or_1": round(float(((dev == 0) | (dev == 1)).float().mean().item()), 3)}
     rec.update(_probs_routes(out, "probs", dev, repeats))
