@@ -253,6 +253,13 @@ SIGNATURES = {
     "e2e_inflate_record_words": (I, []),
     "e2e_inflate_scan": (I, [P, LL, P, LL, P, P]),
     "e2e_inflate_chunks": (I, [P, LL, P, P, LL, P, LL, P, P]),
+    "e2e_inflate_any_record_words": (I, []),
+    "e2e_inflate_any_window_bytes": (I, []),
+    "e2e_inflate_find": (I, [P, LL, LL, LL, P, P]),
+    "e2e_inflate_spans_count": (I, [P, LL, P, LL, LL, P, P]),
+    "e2e_inflate_spans_write": (I, [P, LL, P, P, LL, LL, P, LL, P, P]),
+    "e2e_inflate_windows": (I, [P, P, LL, LL, P, P, P]),
+    "e2e_inflate_resolve": (I, [P, P, LL, P, P, LL, P, P]),
     "e2e_resample_argmax_u8": (I, [P, P, I, LL, I, I, I, LL, LL, LL, I, I, I, P]),
     "e2e_seg_onehot": (I, [P, P, P, I, I, I, I, I, I, LL, P]),
     "e2e_morph_max_footprint": (I, []),
@@ -271,6 +278,7 @@ _NO_STATUS = {"e2e_last_error", "e2e_abi_version", "e2e_last_kernel", "e2e_conv1
               "e2e_fingerprint_sample_chunk", "e2e_fingerprint_sample_ws_bytes", "e2e_fingerprint_stats_max_ranks",
               "e2e_fingerprint_stats_ws_bytes", "e2e_eval_census_max_slots", "e2e_eval_census_chunk", "e2e_eval_census_workgroups",
               "e2e_loader_crop_max_batch", "e2e_nifti_scan_grid_voxels", "e2e_deflate_chunk_bytes", "e2e_deflate_slot_bytes", "e2e_inflate_record_words",
+              "e2e_inflate_any_record_words", "e2e_inflate_any_window_bytes",
               "e2e_diag_concat_slice", "e2e_diag_wgrad_walk",
               "e2e_morph_max_footprint", "e2e_morph_bits_words", "e2e_rcc_ws_bytes"}
 
@@ -310,7 +318,7 @@ class _Lib:
 _lib = None
 
 
-ABI_VERSION = 33          # e2e_abi_version() of the library this binding was written against
+ABI_VERSION = 34          # e2e_abi_version() of the library this binding was written against
 
 
 def lib() -> _Lib:

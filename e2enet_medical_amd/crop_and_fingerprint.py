@@ -28,7 +28,8 @@ def build_parser():
 
 def select_reader(args, reader=None):
     """the ``reader`` the cropping is handed: the caller's; with ``--native_nifti`` and none given, ``nifti.reader``"""
-    return nifti.reader if (args.native_nifti and reader is None) else reader
+    cb = nifti.from_args(args)                         # (refuses --inflate_any without --native_nifti)
+    return cb.reader if (args.native_nifti and reader is None) else reader
 
 
 def main(argv=None, reader=None):

@@ -22,7 +22,7 @@ void note_kernel(const char* fmt, ...) {
 
 extern "C" const char* e2e_last_error(void) { return e2e::g_err; }
 extern "C" const char* e2e_last_kernel(void) { return e2e::g_kernel; }
-extern "C" int e2e_abi_version(void) { return 33; }
+extern "C" int e2e_abi_version(void) { return 34; }
 
 extern "C" int e2e_diag_concat_slice(int d, int dshift, int D, int accumulate, int* dd) {
   const e2e::ConcatSlice sl = e2e::concat_store_slice(d, dshift, D, accumulate);

@@ -463,6 +463,164 @@ def inflate(stream, nbytes, device="cuda", stats=None, scan=None, chunks=None):
     return (device_chunks if chunks is None else chunks)(data, starts, tails, nbytes)
 
 
+# ------------------------------------------------------------------------------------------------------------------ inflate any
+# Any raw DEFLATE stream (csrc/inflate_any.hip; opt-in).  The compressed bytes are cut into segments; ``e2e_inflate_find`` reports
+# the first valid non-final dynamic block header of every segment; the stream is cut into spans at those bit positions; the spans
+# are counted, then decoded into 16-bit symbols (a byte, or "byte j of the 32 KiB in front of this span"), the windows are handed
+# down the chain of spans and the markers replaced.  The host sees three small tables: the starts, the span records, the offsets.
+WINDOW = 32768
+SPAN_RECORD_WORDS = 8                    # one record of e2e_inflate_spans_count (include/e2e_hip.h, N9)
+SEGMENT_BYTES = 16384                    # default segment: zlib at its default settings starts a dynamic block every 15-25 KiB
+SPAN_STATUS = ("good", "BTYPE 11", "a block header rule", "a bit pattern without a symbol", "a symbol over 285",
+               "a distance code over 29", "stored LEN != ~NLEN", "BFINAL before the end of the stream", "a block runs behind the stream",
+               "overshoot", "a span over the cap", "length", "a reach in front of the output", "a start outside the stream")
+OVERSHOOT = 9
+
+
+def span_gaps(starts, n):
+    """bits from every start to the next, the last to the end of the ``n`` compressed bytes"""
+    return np.diff(np.concatenate([np.asarray(starts, dtype=np.int64), [8 * int(n)]]))
+
+
+def unpack_span_records(records):
+    """``(status, final, end bit, output length)`` of span records as int64 arrays"""
+    r = np.asarray(records, dtype=np.uint32).reshape(-1, SPAN_RECORD_WORDS).astype(np.int64)
+    return r[:, 0], r[:, 1], r[:, 2] | (r[:, 3] << 32), r[:, 4] | (r[:, 5] << 32)
+
+
+def inflate_any(stream, nbytes, device="cuda", segment_bytes=None, max_span_bytes=None, stats=None, find=None, count=None, write=None):
+    """The ``nbytes`` bytes that the raw DEFLATE stream ``stream`` (RFC 1951, any encoder's) inflates to, as a uint8 device tensor.
+    ``stream``: bytes, a uint8 array, or a uint8 device tensor, which is used as it is.  ``segment_bytes`` (S >= 16, default
+    ``SEGMENT_BYTES``): the stream is searched for one block start per S compressed bytes.  ``max_span_bytes`` (default 8 S): no
+    span of more compressed bytes is ever decoded by one wave.
+
+    None -- take the host route, which gives the default's result or the default's error -- when a gap between two starts is over
+    the cap (a stream of stored or fixed blocks only has no start at all), a span has a status (a start that is no block start ends
+    in ``overshoot``), the counted lengths do not sum to ``nbytes``, or the last span does not end with the final block at the
+    stream's end.  All of that is decided on the count pass: nothing has been written.  A status of the writing kernels after a clean
+    count pass is a ValueError.  ``stats`` (a dict) receives ``starts`` (found by the search), ``spans``, ``largest_gap`` (bits),
+    ``sym_bytes``, ``window_bytes`` and ``refused`` (None, or the rule that said None).
+
+    ``find(data, S) -> int64 [ceil(n / S)]``, ``count(data, starts, cap) -> uint32 [m, 8]`` and ``write(data, starts, offs, cap,
+    nbytes) -> the result`` replace the device steps (tests without a device; tests/inflate_any_oracle.py)."""
+    nbytes = int(nbytes)
+    S = SEGMENT_BYTES if segment_bytes is None else int(segment_bytes)
+    cap = 8 * S if max_span_bytes is None else int(max_span_bytes)
+    if S < 16 or cap < 1 or nbytes < 0:
+        raise ValueError("inflate_any: segment_bytes %d (at least 16), max_span_bytes %d (at least 1), nbytes %d" % (S, cap, nbytes))
+    hooks = (find, count, write)
+    on_device = not isinstance(stream, (bytes, bytearray, memoryview, np.ndarray))
+    dev = {}
+
+    def host_bytes():
+        if "data" not in dev:
+            dev["data"] = stream.cpu().numpy() if on_device else _byte_array(stream)
+        return dev["data"]
+
+    def upload():
+        import torch
+        from ._lib import lib
+        if "comp" not in dev:
+            L = lib()
+            assert int(L.inflate_any_record_words()) == SPAN_RECORD_WORDS and int(L.inflate_any_window_bytes()) == WINDOW
+            if on_device:
+                nb, _ = _as_device_bytes(stream, 1, "inflate_any")
+                if stream.dtype != torch.uint8 or stream.dim() != 1:
+                    raise ValueError("inflate_any: a device stream is a one-dimensional uint8 tensor")
+                comp = stream
+            else:
+                comp = torch.from_numpy(host_bytes()).to(device)
+            dev.update(lib=L, torch=torch, comp=comp, stream=torch.cuda.current_stream(comp.device).cuda_stream)
+        return dev["lib"], dev["torch"], dev["comp"], dev["stream"]
+
+    def device_find(_, seg):
+        L, torch, comp, st = upload()
+        with torch.cuda.device(comp.device):
+            nseg = -(-comp.numel() // seg)
+            starts_d = torch.full((max(nseg, 1),), -1, dtype=torch.int64, device=comp.device)
+            L.inflate_find(comp.data_ptr(), comp.numel(), seg, nseg, starts_d.data_ptr(), st)
+            return starts_d.cpu().numpy()
+
+    def device_count(_, starts, span_cap):
+        L, torch, comp, st = upload()
+        with torch.cuda.device(comp.device):
+            dev["starts"] = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(comp.device)
+            records = torch.empty((len(starts), SPAN_RECORD_WORDS), dtype=torch.int32, device=comp.device)
+            L.inflate_spans_count(comp.data_ptr(), comp.numel(), dev["starts"].data_ptr(), len(starts), span_cap, records.data_ptr(), st)
+            return records.cpu().numpy().view(np.uint32)
+
+    def device_write(_, starts, offs, span_cap, total):
+        L, torch, comp, st = upload()
+        with torch.cuda.device(comp.device):
+            m = len(starts)
+            out = torch.empty(total, dtype=torch.uint8, device=comp.device)
+            if total == 0:
+                return out
+            starts_d = dev["starts"] if "starts" in dev else torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(comp.device)
+            offs_d = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.int64)).to(comp.device)
+            sym = torch.empty(total, dtype=torch.int16, device=comp.device)
+            wins = torch.empty(m * WINDOW, dtype=torch.uint8, device=comp.device) if m > 1 else None
+            status = torch.empty(3, dtype=torch.int32, device=comp.device)
+            L.inflate_spans_write(comp.data_ptr(), comp.numel(), starts_d.data_ptr(), offs_d.data_ptr(), m, span_cap, sym.data_ptr(),
+                                  total, status[0:].data_ptr(), st)
+            L.inflate_windows(sym.data_ptr(), offs_d.data_ptr(), m, total, wins.data_ptr() if m > 1 else None, status[1:].data_ptr(), st)
+            L.inflate_resolve(sym.data_ptr(), offs_d.data_ptr(), m, wins.data_ptr() if m > 1 else None, out.data_ptr(), total,
+                              status[2:].data_ptr(), st)
+            bad = status.cpu().tolist()
+            if any(bad):
+                raise ValueError("inflate_any: the writing pass found %d corrupt spans of %d (windows: %d, markers: %d)"
+                                 % (bad[0], m, bad[1], bad[2]))
+            return out
+
+    st = {} if stats is None else stats
+    st.update(starts=0, spans=0, largest_gap=0, sym_bytes=0, window_bytes=0, refused=None)
+
+    def refuse(rule):
+        st["refused"] = rule
+        return None
+
+    if all(h is None for h in hooks):
+        n = int(upload()[2].numel())
+        data = None
+    else:
+        data = host_bytes()
+        n = int(data.size)
+    if n == 0:
+        return refuse("an empty stream")
+    found = np.array((device_find if find is None else find)(data, S), dtype=np.int64).reshape(-1)
+    found[0] = 0                                       # the stream's first block starts at bit 0
+    starts = found[found >= 0]
+    gaps = span_gaps(starts, n)
+    st.update(starts=len(starts) - 1, spans=len(starts), largest_gap=int(gaps.max()))
+    if gaps.max() > 8 * cap or gaps.min() <= 0:
+        return refuse("a gap of %d bits between block starts, over the cap of %d bytes" % (int(gaps.max()), cap))
+    status, final, _, lengths = unpack_span_records((device_count if count is None else count)(data, starts, cap))
+    if status.any():
+        k = int(np.flatnonzero(status)[0])
+        code = int(status[k])
+        return refuse("span %d: %s" % (k, SPAN_STATUS[code] if code < len(SPAN_STATUS) else "status %d" % code))
+    if not final[-1]:
+        return refuse("the last span does not end with the final block")
+    if int(lengths.sum()) != nbytes:
+        return refuse("the spans inflate to %d bytes, not %d" % (int(lengths.sum()), nbytes))
+    offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    st.update(sym_bytes=2 * nbytes, window_bytes=WINDOW * len(starts) if len(starts) > 1 else 0)
+    return (device_write if write is None else write)(data, starts, offs, cap, nbytes)
+
+
+def foreign_of(device_inflate, who="device_inflate"):
+    """The ``device_inflate`` argument of the readers as the ``foreign`` argument of ``load_npz``: a false value is None (the host
+    reads everything), ``True`` is ``"host"`` (only this package's members are inflated on the device, exactly as before),
+    ``"any"`` is ``"device"`` (members of other writers go through ``inflate_any``)."""
+    if not device_inflate:
+        return None
+    if device_inflate is True:
+        return "host"
+    if device_inflate == "any":
+        return "device"
+    raise ValueError("%s=%r: True, 'any' or False" % (who, device_inflate))
+
+
 def device_crc32(tensor):
     """``zlib.crc32`` of the bytes of a contiguous device tensor (``e2e_crc32``: the encoder's two CRC kernels)"""
     import torch
@@ -488,7 +646,7 @@ class NpzMember:
 
     def __init__(self, key, crc, size):
         self.key, self.crc, self.size = key, crc, size
-        self.stream = self.body = self.header = self.dtype = self.shape = None
+        self.stream = self.body = self.header = self.foreign_header = self.dtype = self.shape = None
         self.nbytes = 0
         self.why = None
 
@@ -561,6 +719,10 @@ def read_npz_raw(path):
             m.why = "Fortran order, or a dtype without a device tensor"
         elif len(head) + m.nbytes != info.file_size:
             m.why = "the member's length is not header + array"
+        else:
+            m.foreign_header = head                    # any encoder's member that holds a C-ordered array: inflate_any can take it
+        if m.why is not None:
+            pass
         elif m.stream.size < len(prefix) + len(STREAM_END) or bytes(m.stream[:len(prefix)]) != prefix:
             m.why = "the stream does not begin with the header as its own sync-flushed block"
         elif bytes(m.stream[-len(STREAM_END):]) != STREAM_END:
@@ -570,43 +732,67 @@ def read_npz_raw(path):
     return NpzRaw(path, data, members)
 
 
-def load_npz(path, keys=None, device="cuda", stats=None, inflater=None):
+def load_npz(path, keys=None, device="cuda", stats=None, inflater=None, foreign="host"):
     """``np.load(path)`` as a dict of device tensors, the members this package's writers deflated (``savez``, ``-z`` with
     ``--device_deflate``, stage folders) inflated on the device: only compressed bytes cross the link and the host inflates a few
     hundred header bytes.  ``path``: a file, or what ``read_npz_raw`` returned for it.  ``keys``: the members wanted, default all.
     Any other member (``np.savez_compressed``'s, a stored one, Fortran order, a stream with too many candidate offsets) takes
-    ``np.load`` and an upload, with the same result.  A device-route member whose bytes do not give the directory's CRC-32, or whose
-    chain has a corrupt record, is a ValueError that names the file and the member.  ``stats`` (a dict) receives per member
-    ``route`` ("device" / "host"), ``candidates``, ``records``, ``compressed`` and ``inflated`` bytes.  ``inflater`` replaces
-    ``inflate`` and the CRC of its result: ``inflater(body, nbytes, stats) -> (tensor or None, crc32)`` (tests without a device)."""
+    ``np.load`` and an upload, with the same result -- unless ``foreign="device"``: then a deflated member of any other writer that
+    holds a C-ordered array of a native dtype goes through ``inflate_any`` (the whole member, .npy header included; its length is the
+    directory's), and only where that says None through ``np.load``.  A device-route member whose bytes do not give the directory's
+    CRC-32, or whose chain has a corrupt record, is a ValueError that names the file and the member.  ``stats`` (a dict) receives
+    per member ``route`` ("device" / "any" / "host"), ``candidates``, ``records``, ``compressed`` and ``inflated`` bytes, and for the
+    members ``inflate_any`` was asked about its statistics under ``any``.  ``inflater`` replaces ``inflate`` / ``inflate_any`` and
+    the CRC of the result: ``inflater(stream, nbytes, stats) -> (tensor or None, crc32)`` (tests without a device)."""
     import torch
+    if foreign not in ("host", "device"):
+        raise ValueError("load_npz: foreign=%r is neither 'host' nor 'device'" % (foreign,))
     raw = path if isinstance(path, NpzRaw) else read_npz_raw(path)
     missing = [k for k in (keys or ()) if k not in raw.members]
     if missing:
         raise KeyError("%s: no member %s (it holds %s)" % (raw.path, ", ".join(missing), ", ".join(raw.members)))
     out, host = {}, None
+
+    def typed(flat, m):
+        if not isinstance(flat, torch.Tensor):
+            flat = torch.from_numpy(np.ascontiguousarray(flat))
+        dtype = getattr(torch, _NUMPY_TO_TORCH[m.dtype][6:])
+        if flat.data_ptr() % m.dtype.itemsize:
+            flat = flat.clone()                        # (a header that is no multiple of the element size: one device copy)
+        # (an empty tensor has no stride to view by)
+        return flat.view(dtype).reshape(m.shape) if m.nbytes else torch.empty(m.shape, dtype=dtype, device=flat.device)
+
     for key in (raw.members if keys is None else keys):
         m = raw.members[key]
         st = {"route": "host", "candidates": 0, "records": 0, "compressed": int(m.stream.size), "inflated": int(m.size)}
         got = None
-        if m.body is not None:
-            try:
+        try:
+            if m.body is not None:
                 if inflater is None:
                     got = inflate(m.body, m.nbytes, device, st)
                     crc = device_crc32(got) if got is not None else 0
                 else:
                     got, crc = inflater(m.body, m.nbytes, st)
-            except ValueError as e:
-                raise ValueError("%s: member %s: %s" % (raw.path, key, e)) from None
-            if got is not None:
-                if crc32_combine(zlib.crc32(m.header), crc, m.nbytes) != m.crc:
-                    raise ValueError("%s: member %s: the inflated bytes do not give the CRC-32 of the directory (%08x)"
-                                     % (raw.path, key, m.crc))
-                st["route"] = "device"
-                if isinstance(got, torch.Tensor):
-                    dtype = getattr(torch, _NUMPY_TO_TORCH[m.dtype][6:])
-                    # (an empty tensor has no stride to view by)
-                    got = got.view(dtype).reshape(m.shape) if m.nbytes else torch.empty(m.shape, dtype=dtype, device=got.device)
+                if got is not None:
+                    crc = crc32_combine(zlib.crc32(m.header), crc, m.nbytes)
+                    st["route"] = "device"
+            elif foreign == "device" and m.foreign_header is not None:
+                if inflater is None:
+                    got = inflate_any(m.stream, m.size, device, stats=st.setdefault("any", {}))
+                    crc = device_crc32(got) if got is not None else 0
+                else:
+                    got, crc = inflater(m.stream, m.size, st)
+                if got is not None:
+                    got = got[len(m.foreign_header):]
+                    st["route"] = "any"
+        except ValueError as e:
+            raise ValueError("%s: member %s: %s" % (raw.path, key, e)) from None
+        if got is not None:
+            if crc != m.crc:
+                raise ValueError("%s: member %s: the inflated bytes do not give the CRC-32 of the directory (%08x)"
+                                 % (raw.path, key, m.crc))
+            if isinstance(got, torch.Tensor) or st["route"] == "any":
+                got = typed(got, m)
         if got is None:
             if host is None:
                 host = np.load(io.BytesIO(raw.data.tobytes()))

@@ -268,10 +268,9 @@ def build_parser():
 
 def select_reader(args):
     """the ``reader`` handed to ``evaluate_folder``: None (``default_reader``); with ``--native_nifti``, ``nifti.evaluator_reader``"""
-    if args.native_nifti:
-        from . import nifti
-        return nifti.evaluator_reader
-    return None
+    from . import nifti
+    cb = nifti.from_args(args)                         # (refuses --inflate_any without --native_nifti)
+    return cb.evaluator_reader if args.native_nifti else None
 
 
 def main(argv=None):

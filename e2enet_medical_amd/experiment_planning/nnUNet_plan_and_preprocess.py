@@ -73,13 +73,14 @@ def select_planners(args):
 def main(argv=None, reader=None):
     args = build_parser().parse_args(argv)
     planner_3d = select_planners(args)
-    reader = nifti.reader if (args.native_nifti and reader is None) else reader
+    inflate = nifti.inflate_from_args(args)            # (refuses --inflate_any without --native_nifti)
+    reader = nifti.callbacks(inflate).reader if (args.native_nifti and reader is None) else reader
 
     tasks = []
     for i in args.task_ids:
         task_name = convert_id_to_task_name(int(i))
         if args.verify_dataset_integrity:
-            verify_dataset_integrity(os.path.join(paths.nnUNet_raw_data, task_name), args.tf)
+            verify_dataset_integrity(os.path.join(paths.nnUNet_raw_data, task_name), args.tf, inflate=inflate)
         crop(task_name, False, args.tf, reader=reader, device_deflate=deflate.from_args(args))
         tasks.append(task_name)
 

@@ -106,11 +106,12 @@ def _read_raw(f):
     return deflate.read_npz_raw(f)
 
 
-def _inflate_softmax(raw):
+def _inflate_softmax(raw, foreign="host"):
     """the other half, on the thread that owns the GPU: ``softmax`` of one file as a device tensor.  A file that the device
-    encoder did not write is inflated on the host inside ``load_npz``."""
+    encoder did not write is inflated on the host inside ``load_npz`` -- with ``foreign="device"`` only where ``inflate_any`` does
+    not serve it."""
     from .. import deflate
-    return deflate.load_npz(raw, keys=("softmax",))["softmax"]
+    return deflate.load_npz(raw, keys=("softmax",), foreign=foreign)["softmax"]
 
 
 def _load_properties(f):
@@ -165,10 +166,12 @@ def merge_files(files, properties_files, out_file, override, store_npz, writer=N
     """Reference :26-53 for one case.  ``postprocessing`` (as ``load_postprocessing`` returns it) with ``postprocessed_file``: the raw
     label volume goes to ``out_file`` and the post-processed one to ``postprocessed_file``.  ``device_inflate``: as in ``merge``."""
     from .predict import nifti_writer
+    from .. import deflate
+    foreign = deflate.foreign_of(device_inflate, "merge_files: device_inflate")
     _refuse_too_many(len(files))
     if not override and _written(out_file) and (postprocessing is None or _written(postprocessed_file)):
         return
-    softmax = [_inflate_softmax(_read_raw(f)) if device_inflate else _load_softmax(f) for f in files]
+    softmax = [_inflate_softmax(_read_raw(f), foreign) if device_inflate else _load_softmax(f) for f in files]
     props = [_load_properties(f) for f in properties_files]
     seg, raw, mean = _merge_loaded(softmax, props, files, store_npz, postprocessing)
     _write_case(seg, raw, mean, props, out_file, postprocessed_file, writer if writer is not None else nifti_writer())
@@ -179,9 +182,12 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
     """Reference :56-95.  With ``postprocessing_file`` the raw results go to ``<output_folder>/not_postprocessed``, the post-processed
     ones to ``output_folder``, and the json is copied there.  ``device_inflate``: the read-ahead threads only read the files
     (``deflate.read_npz_raw``) and this thread inflates ``softmax`` on the device (``deflate.load_npz``) where the device encoder
-    wrote the file; the files written are those of the default route byte for byte."""
+    wrote the file; the files written are those of the default route byte for byte.  ``device_inflate="any"``: files of any other
+    writer (``np.savez_compressed``: stock ``-z`` folders) are inflated on the device too (``deflate.inflate_any``)."""
     from concurrent.futures import ThreadPoolExecutor
     from .predict import nifti_writer
+    from .. import deflate
+    foreign = deflate.foreign_of(device_inflate, "merge: device_inflate")
     writer = writer if writer is not None else nifti_writer()
     _refuse_too_many(len(folders))
     os.makedirs(output_folder, exist_ok=True)
@@ -220,7 +226,7 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
             read_ahead()
         while loading:
             (files, property_files, out_file, pp_file), reads = loading.popleft()
-            softmax = [_inflate_softmax(r.result()) if device_inflate else r.result() for r in reads]
+            softmax = [_inflate_softmax(r.result(), foreign) if device_inflate else r.result() for r in reads]
             read_ahead()
             props = [_load_properties(f) for f in property_files]
             seg, raw, mean = _merge_loaded(softmax, props, files, store_npz, postprocessing)
@@ -268,7 +274,8 @@ def select_writer(args, writer=None):
 def main(argv=None, writer=None):
     args = build_parser().parse_args(argv)
     merge(args.folders, args.output_folder, args.threads, override=True, postprocessing_file=args.postprocessing_file,
-          store_npz=args.npz, writer=select_writer(args, writer), device_inflate=args.device_inflate)
+          store_npz=args.npz, writer=select_writer(args, writer),
+          device_inflate="any" if args.inflate_any else args.device_inflate)           # (--inflate_any implies --device_inflate)
 
 
 if __name__ == "__main__":

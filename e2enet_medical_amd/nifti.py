@@ -182,12 +182,86 @@ def _volume_shape(h, path):
     return int(dim[3]), int(dim[2]), int(dim[1])
 
 
-def read_raw(path):
+class DeferredPayload:
+    """The voxels of a ``.nii.gz`` that ``read_raw(inflate="device")`` left compressed: ``stream`` (uint8 host array) is the raw
+    DEFLATE stream of the gzip member, ``total`` the length it inflates to (header included), ``offset`` / ``size`` where the
+    payload lies in that, ``crc`` the member's CRC-32.  ``_upload`` resolves it on the thread that owns the GPU."""
+    __slots__ = ("stream", "total", "offset", "size", "crc")
+
+    def __init__(self, stream, total, offset, size, crc):
+        self.stream, self.total, self.offset, self.size, self.crc = stream, total, offset, size, crc
+
+
+def gzip_member(data):
+    """``(offset of the raw DEFLATE stream, crc32, isize)`` of a file's bytes that hold one gzip member (RFC 1952): magic, CM = 8,
+    FEXTRA, FNAME, FCOMMENT and FHCRC honoured, the trailer taken from the last 8 bytes.  None for anything else (a reserved flag
+    bit, a header that runs over the end): such a file is the host route's to read or to refuse."""
+    n = len(data)
+    if n < 18 or bytes(data[:3]) != b"\x1f\x8b\x08":
+        return None
+    flags = int(data[3])
+    if flags & 0xE0:
+        return None
+    at = 10
+    if flags & 4:                                      # FEXTRA: XLEN and that many bytes
+        at += 2 + int(data[at]) + (int(data[at + 1]) << 8)
+        if at + 8 > n:
+            return None
+    for bit in (8, 16):                                # FNAME, FCOMMENT: zero-terminated
+        if flags & bit:
+            while at < n and data[at] != 0:
+                at += 1
+            at += 1
+    if flags & 2:                                      # FHCRC
+        at += 2
+    if at + 8 > n:
+        return None
+    crc, isize = struct.unpack("<II", bytes(data[n - 8:]))
+    return at, crc, isize
+
+
+_HEAD_WINDOW = 1 << 20              # compressed bytes looked at for the header and the gap up to vox_offset
+
+
+def _read_deferred(path):
+    """The device route of ``read_raw``: ``(the inflated bytes in front of the voxels' end that the host needs, DeferredPayload
+    factory)`` -- or None where the host route has to take the file (see ``read_raw``)."""
+    import zlib
+    data = np.fromfile(path, dtype=np.uint8)
+    member = gzip_member(data)
+    if member is None:
+        return None
+    at, crc, isize = member
+    d = zlib.decompressobj(-15)
+    try:
+        hdr = d.decompress(bytes(data[at:at + _HEAD_WINDOW]), HEADER_BYTES)
+    except zlib.error:
+        return None
+    if len(hdr) < HEADER_BYTES:
+        return None
+    return data, at, crc, isize, d, hdr
+
+
+def read_raw(path, inflate="host"):
     """Header and payload of a ``.nii`` / ``.nii.gz`` file as a ``NiftiRaw``.  Host only (safe in a thread pool): the payload is
     inflated straight into one preallocated buffer, which is what gets uploaded.  Every refusal is a ValueError naming the file
-    and the field."""
+    and the field.
+
+    ``inflate="device"`` (``.gz`` files; any other file is read as before): the host parses the gzip member header and inflates
+    only the bytes in front of ``vox_offset``; the payload stays compressed in a ``DeferredPayload`` and is inflated on the device
+    (``deflate.inflate_any``) when a decoder uploads it.  Still host only.  The header is parsed and refused exactly as on the host
+    route.  What the device route does not serve is read on the host route here and now, with its result or its refusal: a file
+    that is no single plain gzip member, a stream that fails in front of ``vox_offset``, an ISIZE that is not ``vox_offset`` + the
+    payload's size (a truncated payload, a second member, a total of 4 GiB or more)."""
+    import io
+    if inflate not in ("host", "device"):
+        raise ValueError("read_raw: inflate=%r is neither 'host' nor 'device'" % (inflate,))
     path = os.fspath(path)
-    with _opener(path)() as f:
+    opener = _opener(path)
+    deferred = _read_deferred(path) if inflate == "device" and path.lower().endswith(".gz") else None
+    if inflate == "device" and deferred is None:
+        return read_raw(path)
+    with (io.BytesIO(deferred[5]) if deferred else opener()) as f:
         hdr = _read_exact(f, HEADER_BYTES)
         h = parse_header(hdr, path)
         shape = _volume_shape(h, path)
@@ -203,18 +277,29 @@ def read_raw(path):
             _refuse(path, "vox_offset", "is %r: the voxels of a single-file NIfTI-1 start at or after byte 348" % vox_offset)
         spacing, origin, direction = geometry(h, path)
         skip = int(vox_offset) - HEADER_BYTES
-        if len(_read_exact(f, skip)) != skip:
-            _refuse(path, "vox_offset", "is %d, past the end of the file" % int(vox_offset))
         nbytes = shape[0] * shape[1] * shape[2] * elsize
-        payload = np.empty(nbytes, dtype=np.uint8)          # (numpy's allocation: aligned to any element size)
-        view, got = memoryview(payload), 0
-        while got < nbytes:
-            n = f.readinto(view[got:])
-            if not n:
-                break
-            got += n
-        if got != nbytes:
-            _refuse(path, "payload", "is truncated: %d bytes after vox_offset, dim and bitpix ask for %d" % (got, nbytes))
+        if deferred:
+            import zlib
+            data, at, crc, isize, d, _ = deferred
+            try:
+                skipped = len(d.decompress(d.unconsumed_tail, skip)) if skip else 0
+            except zlib.error:
+                skipped = -1
+            if skipped != skip or isize != int(vox_offset) + nbytes:
+                return read_raw(path)
+            payload = DeferredPayload(data[at:data.size - 8], int(vox_offset) + nbytes, int(vox_offset), nbytes, crc)
+        else:
+            if len(_read_exact(f, skip)) != skip:
+                _refuse(path, "vox_offset", "is %d, past the end of the file" % int(vox_offset))
+            payload = np.empty(nbytes, dtype=np.uint8)          # (numpy's allocation: aligned to any element size)
+            view, got = memoryview(payload), 0
+            while got < nbytes:
+                n = f.readinto(view[got:])
+                if not n:
+                    break
+                got += n
+            if got != nbytes:
+                _refuse(path, "payload", "is truncated: %d bytes after vox_offset, dim and bitpix ask for %d" % (got, nbytes))
     slope, inter = float(h["scl_slope"]), float(h["scl_inter"])
     scale = slope != 0. and math.isfinite(slope) and not (slope == 1. and inter == 0.)
     if scale and not math.isfinite(inter):
@@ -243,8 +328,39 @@ def _require_device():
         raise RuntimeError("NIfTI voxels are decoded on the GPU (csrc/nifti.hip); there is no host fallback")
 
 
+def resolve_payload(raw, inflater=None):
+    """The stored bytes of a ``NiftiRaw`` whose payload is a ``DeferredPayload``, as a uint8 device tensor: the member inflated on
+    the device, its CRC-32 checked there (a ValueError that names the file), the payload sliced out at ``vox_offset`` (one device
+    copy when that is no multiple of the element size).  Where ``inflate_any`` says None the file is read on the host route and
+    uploaded, with that route's refusals.  ``inflater(stream, total) -> (bytes as a tensor or array, or None; crc32)`` replaces the
+    device steps (tests without a device)."""
+    import torch
+    from . import deflate
+    p = raw.payload
+    if inflater is None:
+        _require_device()
+        try:
+            got = deflate.inflate_any(p.stream, p.total)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (raw.path, e)) from None
+        crc = deflate.device_crc32(got) if got is not None else 0
+    else:
+        got, crc = inflater(p.stream, p.total)
+    if got is None:
+        host = torch.from_numpy(read_raw(raw.path).payload)
+        return host.to("cuda") if inflater is None else host
+    if crc != p.crc:
+        raise ValueError("%s: the inflated bytes do not give the CRC-32 of the gzip trailer (%08x)" % (raw.path, p.crc))
+    if not isinstance(got, torch.Tensor):
+        got = torch.from_numpy(np.ascontiguousarray(got))
+    body = got[p.offset:p.offset + p.size]
+    return body.clone() if p.offset % raw.elsize else body
+
+
 def _upload(raw):
     import torch
+    if isinstance(raw.payload, DeferredPayload):
+        return resolve_payload(raw)
     _require_device()
     return torch.from_numpy(raw.payload).to("cuda")
 
@@ -299,13 +415,13 @@ def scan(raw):
 
 
 # ------------------------------------------------------------------------------------------------------------------ callbacks
-def reader(list_of_files):
+def reader(list_of_files, inflate="host"):
     """``reader(list_of_files) -> (data, properties)`` of the cropping, preprocessing and prediction entry points: ``data`` is an
     fp32 device tensor ``[C, Z, Y, X]``, every modality decoded straight into its channel; ``properties`` are those of the first
-    file (the reference's keys)."""
+    file (the reference's keys).  ``inflate``: as in ``read_raw`` (``callbacks("device")`` binds it)."""
     import torch
     assert isinstance(list_of_files, (list, tuple)), "case must be either a list or a tuple"
-    raws = [read_raw(f) for f in list_of_files]                  # (host; every refusal comes before the first upload)
+    raws = [read_raw(f, inflate) for f in list_of_files]         # (host; every refusal comes before the first upload)
     first = raws[0]
     for raw in raws[1:]:
         if raw.shape != first.shape:
@@ -437,25 +553,70 @@ def writer(seg, path, properties, device_deflate=False):
 writer.accepts_device = True
 
 
-def gt_reader(path):
+def gt_reader(path, inflate="host"):
     """``gt_reader(path) -> label array`` of ``validate``: the uint8 volume (decoded on the device), None for a missing file"""
     if not os.path.isfile(path):
         return None
-    return decode_u8(read_raw(path)).cpu().numpy()
+    return decode_u8(read_raw(path, inflate)).cpu().numpy()
 
 
-def evaluator_reader(path):
+def evaluator_reader(path, inflate="host"):
     """``reader(path) -> (volume, spacing)`` of ``NiftiEvaluator``.  This is the host half, run by the evaluator's read-ahead
     threads: the volume is the ``NiftiRaw``, which ``set_test`` / ``set_reference`` decode on the thread that owns the GPU.  The
     spacing is ``itk_spacing[::-1]``, array-axis order.  ``.npy`` volumes are read as before, without spacing."""
     if path.endswith(".npy"):
         return np.load(path), None
-    raw = read_raw(path)
+    raw = read_raw(path, inflate)
     return raw, tuple(raw.itk_spacing)[::-1]
 
 
+class Callbacks:
+    """``reader``, ``gt_reader`` and ``evaluator_reader`` bound to one ``inflate`` route of ``read_raw``, ``writer`` beside them"""
+
+    def __init__(self, inflate):
+        import functools
+        self.inflate = inflate
+        self.reader = functools.partial(reader, inflate=inflate)
+        self.gt_reader = functools.partial(gt_reader, inflate=inflate)
+        self.evaluator_reader = functools.partial(evaluator_reader, inflate=inflate)
+        self.writer = writer
+
+
+def callbacks(inflate="host"):
+    """The callbacks of this module for one route of ``read_raw``: for ``"host"`` the module's own functions, the very objects;
+    for ``"device"`` the same functions with ``inflate="device"`` bound (``.nii.gz`` payloads are inflated on the GPU)."""
+    import sys
+    if inflate == "host":
+        return sys.modules[__name__]
+    if inflate != "device":
+        raise ValueError("callbacks: inflate=%r is neither 'host' nor 'device'" % (inflate,))
+    return Callbacks(inflate)
+
+
+def inflate_from_args(args, also=()):
+    """``"device"`` with ``--inflate_any``, else ``"host"``.  The flag without ``--native_nifti`` does nothing to any .nii.gz and is
+    refused by name (a ValueError) before any work -- unless one of the switches named in ``also`` is set, for which the command
+    gives the flag a meaning of its own (``--resident_data`` of the training, ``--device_inflate`` of the ensembling)."""
+    if not getattr(args, "inflate_any", False):
+        return "host"
+    if getattr(args, "native_nifti", False):
+        return "device"
+    if any(getattr(args, name, None) not in (None, False) for name in also):
+        return "host"
+    raise ValueError("--inflate_any inflates the .nii.gz files that --native_nifti reads on the GPU: it needs --native_nifti%s"
+                     % "".join(" or --%s" % name for name in also))
+
+
+def from_args(args, also=()):
+    """``callbacks`` for the parsed switches of a command that called ``add_argument``"""
+    return callbacks(inflate_from_args(args, also))
+
+
 def add_argument(parser):
-    """the ``--native_nifti`` switch of the command-line tools"""
+    """the ``--native_nifti`` and ``--inflate_any`` switches of the command-line tools; ``from_args`` reads them"""
     parser.add_argument("--native_nifti", action="store_true", default=False,
                         help="read and write .nii.gz with this package's own NIfTI-1 code (header and gzip on the host, the voxels "
                              "decoded on the GPU) instead of SimpleITK; default: SimpleITK when it is installed")
+    parser.add_argument("--inflate_any", action="store_true", default=False,
+                        help="with --native_nifti: inflate the .nii.gz files that are read on the GPU as well (any gzip writer's; "
+                             "a file the GPU route does not serve is inflated on the host as before, with the same result)")

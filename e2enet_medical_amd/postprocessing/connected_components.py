@@ -303,13 +303,13 @@ def default_reader(path):
     return sitk.GetArrayFromImage(img), {'itk_spacing': img.GetSpacing(), 'itk_origin': img.GetOrigin(), 'itk_direction': img.GetDirection()}
 
 
-def native_reader(path):
+def native_reader(path, inflate="host"):
     """``default_reader`` with this package's own NIfTI-1 code: the host half (header and gzip; safe in a read-ahead thread) returns
     the ``nifti.NiftiRaw``, which the thread that owns the GPU decodes to a device uint8 tensor"""
     from .. import nifti
     if path.endswith(".npy"):
         return np.load(path), None
-    raw = nifti.read_raw(path)
+    raw = nifti.read_raw(path, inflate)                # ("device": the payload is inflated on the GPU when it is decoded)
     return raw, nifti.properties_of(raw)
 
 

@@ -86,9 +86,12 @@ def build_parser():
 
 def select_callbacks(args):
     """the ``reader`` / ``writer`` keywords of the folder search: none (its defaults); with ``--native_nifti`` this package's own"""
+    from .. import nifti
+    inflate = nifti.inflate_from_args(args)            # (refuses --inflate_any without --native_nifti)
     if args.native_nifti:
-        from .. import nifti
-        return {"reader": native_reader, "writer": nifti.writer}
+        import functools
+        return {"reader": native_reader if inflate == "host" else functools.partial(native_reader, inflate=inflate),
+                "writer": nifti.writer}
     return {}
 
 

@@ -69,6 +69,8 @@ def verify_same_geometry(img_1, img_2):
 def _value_at(raw, index):
     """the fp32 value of voxel ``index`` of a ``NiftiRaw``, from the host payload (numpy's arithmetic: the decode's rule)"""
     dt = np.dtype(nifti.DATATYPES[raw.datatype][0])
+    if isinstance(raw.payload, nifti.DeferredPayload):
+        raw = nifti.read_raw(raw.path)                 # (a report about one bad file: the host inflates it after all)
     stored = raw.payload[index * raw.elsize:(index + 1) * raw.elsize].view(dt.newbyteorder("S") if raw.swap else dt)[0]
     with np.errstate(over="ignore", invalid="ignore"):
         if raw.scale:
@@ -96,7 +98,7 @@ def verify_contains_only_expected_labels(itk_img, valid_labels):
     return _unexpected_labels(raw, nifti.scan(raw), valid_labels)
 
 
-def _read_ahead(pool, depth, groups):
+def _read_ahead(pool, depth, groups, inflate="host"):
     """``nifti.read_raw`` of a sequence of file groups on the threads of ``pool``, at most ``depth`` groups ahead of the consumer.
     ``groups`` yields (key, [files]) or (key, an exception: what is wrong with the group); this yields (key, [NiftiRaw]) or that pair
     as it is, in order; nothing behind an exception is read."""
@@ -108,20 +110,22 @@ def _read_ahead(pool, depth, groups):
                 more = False
             if item is not None:
                 key, files = item
-                pending.append((key, files if isinstance(files, Exception) else [pool.submit(nifti.read_raw, f) for f in files]))
+                pending.append((key, files if isinstance(files, Exception) else [pool.submit(nifti.read_raw, f, inflate) for f in files]))
         if not pending:
             return
         key, futures = pending.popleft()
         yield key, (futures if isinstance(futures, Exception) else [f.result() for f in futures])
 
 
-def verify_dataset_integrity(folder, num_threads=DEFAULT_NUM_THREADS):
+def verify_dataset_integrity(folder, num_threads=DEFAULT_NUM_THREADS, inflate="host"):
     """The reference's checks of a raw task folder (``dataset.json``, ``imagesTr``, ``labelsTr``, ``imagesTs`` when there is a test
     set): every listed file is there and none besides; per training case the geometry of every modality against the label, NaNs in the
     label, NaNs in every image; the declared labels start at 0 and are consecutive; no label file holds another value; the modalities
     of a test case share one geometry; the axis orientations.  AssertionError for missing files and wrong labels, RuntimeError for
     NaNs (after every case was listed), ``Warning`` raised for a geometry mismatch -- as in the reference.  ``num_threads`` host
-    threads (at most 16) inflate files ahead; this thread uploads and scans.  Neither the report nor the outcome depends on them."""
+    threads (at most 16) inflate files ahead; this thread uploads and scans.  Neither the report nor the outcome depends on them.
+    ``inflate="device"`` (``--inflate_any``): the threads only read the files, the payloads are inflated on the GPU
+    (``nifti.read_raw``)."""
     join, isfile = os.path.join, os.path.isfile
     assert isfile(join(folder, "dataset.json")), "There needs to be a dataset.json file in folder, folder=%s" % folder
     assert os.path.isdir(join(folder, "imagesTr")), "There needs to be a imagesTr subfolder in folder, folder=%s" % folder
@@ -157,7 +161,7 @@ def verify_dataset_integrity(folder, num_threads=DEFAULT_NUM_THREADS):
 
     print("Verifying training set")
     with ThreadPoolExecutor(max_workers=workers) as pool:
-        for c, raws in _read_ahead(pool, workers, training_files()):
+        for c, raws in _read_ahead(pool, workers, training_files(), inflate):
             print("checking case", c)
             if isinstance(raws, Exception):
                 raise raws
@@ -224,7 +228,7 @@ def verify_dataset_integrity(folder, num_threads=DEFAULT_NUM_THREADS):
                         # (a single modality has nothing to agree with: its file is not opened)
                         yield expected_image_files, (expected_image_files if num_modalities > 1 else [])
 
-            for expected_image_files, raws in _read_ahead(pool, workers, test_files()):
+            for expected_image_files, raws in _read_ahead(pool, workers, test_files(), inflate):
                 if isinstance(raws, Exception):
                     raise raws
                 for i, img in enumerate(raws[1:]):

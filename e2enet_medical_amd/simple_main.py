@@ -80,9 +80,10 @@ def build_parser():
 def select_validation_callbacks(args):
     """``(writer, gt_reader)`` handed to ``validate``: None, None (its own defaults); with ``--native_nifti``, ``nifti.writer`` and
     ``nifti.gt_reader``"""
+    from . import nifti
+    cb = nifti.from_args(args, also=("resident_data",))
     if args.native_nifti:
-        from . import nifti
-        return nifti.writer, nifti.gt_reader
+        return nifti.writer, cb.gt_reader
     return None, None
 
 
@@ -123,6 +124,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.device_inflate and args.resident_data is None:
         parser.error("--device_inflate needs --resident_data: it inflates the cases that are kept on the device")
+    if args.inflate_any and args.resident_data is None and not args.native_nifti:
+        parser.error("--inflate_any needs --resident_data (it inflates the zlib-written cases that are kept on the device) or "
+                     "--native_nifti (it inflates the .nii.gz files that are read)")
     print(args)
     task, fold, network = args.task, args.fold, args.network
     if not task.startswith("Task"):
@@ -139,7 +143,8 @@ def main(argv=None):
     trainer.base_num_features_override = args.base_num_features
     trainer.synthetic_data = bool(args.synthetic_data)
     trainer.resident_data_gib = args.resident_data
-    trainer.device_inflate = bool(args.device_inflate)
+    # (--inflate_any with --resident_data implies --device_inflate and extends it to members of other writers)
+    trainer.device_inflate = "any" if (args.inflate_any and args.resident_data is not None) else bool(args.device_inflate)
     if args.disable_saving:
         trainer.save_final_checkpoint = False
         trainer.save_best_checkpoint = False

@@ -50,8 +50,9 @@ def build_parser():
 def select_callbacks(args, reader=None, writer=None):
     """``(reader, writer)`` handed to ``predict_from_folder``: the caller's; with ``--native_nifti``, ``nifti.reader`` and
     ``nifti.writer`` where none was given"""
+    cb = nifti.from_args(args)                         # (refuses --inflate_any without --native_nifti)
     if args.native_nifti:
-        return (nifti.reader if reader is None else reader), (nifti.writer if writer is None else writer)
+        return (cb.reader if reader is None else reader), (nifti.writer if writer is None else writer)
     return reader, writer
 
 
@@ -76,7 +77,7 @@ def main(argv=None, reader=None, writer=None):
         raise ValueError("Unexpected value for argument folds")
     assert all_in_gpu in ['None', 'False', 'True']
     all_in_gpu = {"None": None, "True": True, "False": False}[all_in_gpu]
-    seg_reader = nifti.gt_reader if args.native_nifti else None
+    seg_reader = nifti.from_args(args).gt_reader if args.native_nifti else None
     if model == "3d_cascade_fullres" and lowres_segmentations is None:
         # reference :192-210: the first stage's predictions of the same input folder, into <output>/3d_lowres_predictions
         print("lowres_segmentations is None. Attempting to predict 3d_lowres first...")

@@ -31,7 +31,8 @@ class DeviceCaseCache:
     bookkeeping run without a GPU).  ``device_inflate``: a case that has no unpacked ``.npy`` is admitted from the shape in its
     ``.npy`` header, before any device work, and its ``data`` member is inflated into HBM by ``deflate.load_npz`` (``loader``
     replaces it in tests: ``loader(raw) -> tensor``) and converted to fp32 there; a member that is not this package's goes
-    through ``np.load`` inside ``load_npz``.  The cases on the device hold the same bits either way."""
+    through ``np.load`` inside ``load_npz`` -- with ``device_inflate="any"`` through ``deflate.inflate_any`` first (zlib-written stage
+    folders).  The cases on the device hold the same bits either way."""
 
     def __init__(self, budget_bytes=None, device="cuda", upload=None, device_inflate=False, loader=None):
         if budget_bytes is not None and budget_bytes < 0:
@@ -39,7 +40,9 @@ class DeviceCaseCache:
         self.budget_bytes = None if budget_bytes is None else int(budget_bytes)
         self.device = device
         self._upload = self._to_device if upload is None else upload
-        self.device_inflate = bool(device_inflate)
+        from ... import deflate
+        self.foreign = deflate.foreign_of(device_inflate, "DeviceCaseCache: device_inflate")      # None: off
+        self.device_inflate = self.foreign is not None
         self._loader = self._inflate_to_device if loader is None else loader
         self.inflated_cases = 0
         self._cases = {}
@@ -51,7 +54,7 @@ class DeviceCaseCache:
 
     def _inflate_to_device(self, raw):
         from ... import deflate
-        return deflate.load_npz(raw, keys=("data",), device=self.device)["data"]
+        return deflate.load_npz(raw, keys=("data",), device=self.device, foreign=self.foreign)["data"]
 
     def _fetch_inflated(self, path):
         """(case, resident) of a packed case under ``device_inflate``, or None where the host route has to take it: the archive has

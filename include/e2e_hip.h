@@ -921,6 +921,48 @@ int e2e_inflate_chunks(const unsigned char* comp, long long ncomp, const long lo
                        long long nchunks, unsigned char* out, long long nbytes, unsigned* status, void* stream);
 int e2e_crc32(const void* buf, long long nbytes, unsigned* chunk_crcs, unsigned* crc, void* stream);
 
+/* ---- N9: inflate any raw DEFLATE stream (RFC 1951) on the device (csrc/inflate_any.hip) ------------------------------------------
+ * Replaces: the host's single-threaded zlib pass over a zlib-written .npz member or a .nii.gz, and the upload of the inflated bytes.
+ * comp[0, n) is the stream; bit position p is bit p mod 8 (least significant first) of comp[p / 8]; bytes behind n read as zero.
+ * W = e2e_inflate_any_window_bytes() = 32768.  All buffers are device buffers; the host only compacts and sums small tables.
+ *   find: the compressed bytes are cut into nseg = ceil(n / segment_bytes) segments.  starts[s], s = 1 .. nseg - 1, receives the
+ *     first bit position p with 8 s S <= p < 8 (s + 1) S at which a non-final dynamic block header is valid, or -1: BFINAL 0,
+ *     BTYPE 10, HLIT <= 29, HDIST <= 29, a complete code-length code, no run over HLIT + HDIST, no repeat of nothing, symbol 256
+ *     present, a complete literal/length code, a distance code that is complete, empty or one code of length 1 (zlib's rules, the
+ *     ones N8 applies), and the header ends at or before bit 8 n.  starts[0] is not written (the host sets it to 0).
+ *   spans_count: starts[0, m) are ascending bit positions (the compacted result of find).  Span k is parsed block by block (stored,
+ *     fixed, dynamic; distances 1 .. 32768) from starts[k] until a block ends exactly at starts[k + 1]; the last span until a block
+ *     with BFINAL set, which must end in byte n - 1.  records[k] (e2e_inflate_any_record_words() = 8 words): word 0 status, word 1
+ *     whether the span ended with the final block, words 2, 3 the bit position behind its last block (low, high), words 4, 5 its
+ *     output length (low, high), words 6, 7 zero; words 1 .. 7 are zero when the status is not 0.  Status: 0 good; 1 BTYPE 11; 2 a header rule above; 3 a bit pattern without a symbol;
+ *     4 a symbol > 285; 5 a distance code > 29; 6 stored LEN != ~NLEN; 7 BFINAL in a span that is not the last, or a final block
+ *     that does not end in the last byte; 8 a block that runs behind n; 9 overshoot: a block end behind starts[k + 1]; 10 more
+ *     than max_span_bytes compressed bytes, or more than 8 max_span_bytes + 64 blocks and symbols; 13 a start outside [0, 8 n).
+ *     Nothing but the record is written.
+ *   spans_write: offs[0, m] is the exclusive prefix sum of the counted lengths (offs[m] = nbytes).  Span k is parsed again with the
+ *     same rules (nothing of the count is trusted but the offsets) into sym[offs[k], offs[k + 1]): a literal is its value; a match
+ *     copies symbols of the span; a source q < 0 (span-relative) is the marker 0x8000 | (W + q), "byte W + q of the W bytes in front
+ *     of this span".  A span that is invalid, reaches in front of absolute position 0 (status 12), gives another length than its
+ *     offsets say (11) or whose offsets leave [0, nbytes] stores nothing outside its own range of sym and adds 1 to *status
+ *     (device, zeroed by the call).
+ *   windows: wins[k W + j], 1 <= k < m, = the byte at absolute position offs[k] - W + j (0 in front of the output), from
+ *     win_{k-1} and the symbols of span k - 1, spans in order, one workgroup.  A marker in span 0 counts in *status.
+ *   resolve: out[i] = sym[i] < 0x8000 ? sym[i] : wins[k(i) W + (sym[i] & 0x7FFF)], k(i) the last span with offs[k] <= i.
+ * Refused with E2E_ERR_ARG before anything is launched: a null pointer, segment_bytes outside 16 .. 2^24, nseg != ceil(n /
+ * segment_bytes), n > 2^38, nbytes > 2^37, m > 2^26, max_span_bytes outside 1 .. 2^31, starts / offs not aligned to 8 bytes, sym
+ * or out not aligned to 16.                                                                                                       */
+int e2e_inflate_any_record_words(void);
+int e2e_inflate_any_window_bytes(void);
+int e2e_inflate_find(const unsigned char* comp, long long n, long long segment_bytes, long long nseg, long long* starts, void* stream);
+int e2e_inflate_spans_count(const unsigned char* comp, long long n, const long long* starts, long long m, long long max_span_bytes,
+                            unsigned* records, void* stream);
+int e2e_inflate_spans_write(const unsigned char* comp, long long n, const long long* starts, const long long* offs, long long m,
+                            long long max_span_bytes, unsigned short* sym, long long nbytes, unsigned* status, void* stream);
+int e2e_inflate_windows(const unsigned short* sym, const long long* offs, long long m, long long nbytes, unsigned char* wins,
+                        unsigned* status, void* stream);
+int e2e_inflate_resolve(const unsigned short* sym, const long long* offs, long long m, const unsigned char* wins, unsigned char* out,
+                        long long nbytes, unsigned* status, void* stream);
+
 /* ---- N7: the two-stage cascade (csrc/cascade.hip) -------------------------------------------------------------------------------
  * Replaces: resample_and_save of the 3d_lowres hand-over (e2enet/training/cascade_stuff/predict_next_stage.py:31-43:
  * resample_data_or_seg(order 1) of the [K, ...] softmax on the host, argmax(0), uint8) and the three transforms of
