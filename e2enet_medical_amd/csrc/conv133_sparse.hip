@@ -22,8 +22,8 @@
 //   * the plane table, the destination table and the liveness words arrive in plan order (built by the caller);
 //   * a neighbourhood row is read as ds_read_b128 + ds_read_b64 (the compiler merged the halo halves of two rows into one
 //     ds_read2_b64, whose accesses are banked mod 32 and collide 2-way: SQ_LDS_BANK_CONFLICT was 39 % of the LDS cycles);
-//   * the two-level summation flushes after `flush_every` chunks (a chain of ~18 products: every chunk at density >= 0.2, fewer
-//     flushes for sparser maps; the noise against fp64 stays below the torch-CPU conv's);
+//   * the two-level summation flushes after `flush_every` chunks (the heaviest output plane's chain stays within ~36 products:
+//     every chunk at density >= 0.2, fewer flushes for sparser maps; the noise against fp64 stays below the torch-CPU conv's);
 //   * an accumulating data gradient loads the old dx values in its PROLOGUE into the outer accumulators (they are free until the
 //     first flush): no read-modify-write round trip in the epilogue;
 //   * a data gradient that is the LAST writer of a gradient buffer also forms the InstanceNorm-backward sums of that buffer's
@@ -644,7 +644,6 @@ extern "C" int e2e_conv133_sparse_plan(const unsigned char* kmask, int R, int Cc
   const int groups = e2e::cdiv(Q, OCG), nchunks = e2e::cdiv(P, CK);
   const int NWG = groups * NW;                           // waves of all groups: they share ONE chunking of the input planes
   auto alive = [&](int q, int pp) -> unsigned char { return transpose ? kmask[(long long)pp * Cc + q] : kmask[(long long)q * Cc + pp]; };
-  long long nlive = 0;
   // -- output planes to waves, per 32-plane group: longest-processing-time first on the planes' live counts
   for (int g = 0; g < groups; ++g) {
     const int q0 = g * OCG, nq = std::min(OCG, Q - q0);
@@ -652,7 +651,6 @@ extern "C" int e2e_conv133_sparse_plan(const unsigned char* kmask, int R, int Cc
     for (int i = 0; i < nq; ++i) {
       for (int pp = 0; pp < P; ++pp) cnt[i] += alive(q0 + i, pp);
       order[i] = i;
-      nlive += cnt[i];
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cnt[a] > cnt[b]; });
     int wload[NW] = {0}, wfill[NW] = {0};
@@ -765,13 +763,35 @@ extern "C" int e2e_conv133_sparse_plan(const unsigned char* kmask, int R, int Cc
     }
   *kmax = km;
   if (flush_every != nullptr) {
-    // flush the chunk accumulators into the outer ones once a chain holds ~18 products: measured against fp64
+    // flush the chunk accumulators into the outer ones before a chain grows long: measured against fp64
     // (tools/scratch/sparse_err.py, 64 -> 32 at density 0.2) chains of ~58 products left the output 1.9e-7 rms from exact, ~29
     // products 1.5e-7, the torch-CPU conv 1.5e-7, a flush after every chunk 1.3e-7; the engine is to stay below the CPU path's noise
-    // (and the flushes cost nothing measurable: 0.777 / 0.763 ms at an interval of 4 / 2 chunks)
-    const double per_plane_chunk = Q > 0 ? (double)nlive / ((double)Q * nchunks) : (double)CK;   // live kernels per output plane and chunk
-    int f = per_plane_chunk > 0.0 ? (int)(2.0 / per_plane_chunk) : nchunks;
-    *flush_every = f < 1 ? 1 : (f > nchunks ? nchunks : f);
+    // (and the flushes cost nothing measurable: 0.777 / 0.763 ms at an interval of 4 / 2 chunks).
+    // The interval is the longest one for which the chain of the HEAVIEST output plane -- its live kernels in any run of
+    // `flush_every` chunks between two flushes, nine products each -- stays within four kernels (36 products), or within the
+    // plane's heaviest single chunk where that alone is more (a flush after every chunk is the shortest chain there is).  Until
+    // the structured-map tests the interval came from the MEAN live count per plane and chunk (chains of ~18 products on an i.i.d.
+    // map), which says nothing about a map whose work sits in a few planes: 160 -> 64 with one fully live input plane in an
+    // i.i.d. 0.02 map never flushed in the data gradient, that plane's gradient was ONE chain of 576 products, 2.33 x the
+    // torch-CPU conv's rms distance from fp64 (0.99 x with a flush per chunk; tests/test_gpu_structured_masks.py).
+    std::vector<int> per_chunk((size_t)Q * nchunks, 0);      // live kernels of output plane q in chunk c
+    int one_chunk = 0;
+    for (int q = 0; q < Q; ++q)
+      for (int pp = 0; pp < P; ++pp)
+        if (alive(q, pp)) one_chunk = std::max(one_chunk, ++per_chunk[(size_t)q * nchunks + chunk_of[pp]]);
+    const int bound = std::max(4, one_chunk);
+    int f = nchunks;
+    for (; f > 1; --f) {
+      int longest = 0;
+      for (int q = 0; q < Q && longest <= bound; ++q)
+        for (int c0 = 0; c0 < nchunks; c0 += f) {             // the kernel flushes after chunks f - 1, 2 f - 1, ... and the last
+          int run = 0;
+          for (int c = c0; c < std::min(nchunks, c0 + f); ++c) run += per_chunk[(size_t)q * nchunks + c];
+          longest = std::max(longest, run);
+        }
+      if (longest <= bound) break;
+    }
+    *flush_every = f;
   }
   return E2E_OK;
 }

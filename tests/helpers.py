@@ -206,3 +206,94 @@ def write_synthetic_task(pre_root, task="Task998_Synth", plans=None, n_cases=6, 
             gt[tuple(slice(o, o + a) for o, a in zip(off, after_crop))] = inner.astype(np.uint8)
             np.save(os.path.join(ddir, "gt_segmentations", name + ".npy"), gt)
     return ddir, plans
+
+
+# ---------------------------------------------------------------------------------- DSFF kernel maps with structure
+STRUCTURED_PATTERNS = ("dead_rows", "dead_cols", "unused_source", "heavy_rows", "heavy_cols", "one_heavy_row", "one_heavy_col",
+                       "dense_group", "all_dead")
+
+
+def structured_kmask_parts(rows, cols, pattern, col_range=None):
+    """The rows / columns that `pattern` singles out in a [rows, cols] map, as (dead_rows, dead_cols, heavy_rows, heavy_cols)."""
+    none = []
+    if pattern == "dead_rows":
+        mid = 4 * ((rows // 2) // 4) + 1                                   # the second row of a quad
+        quad = 4 * (1 if mid // 4 != 1 else 2)                             # one aligned quad, another one than mid's
+        dead = {mid} | set(range(quad, quad + 4))
+        if rows % 32 and rows > 32:                                        # the whole ragged last 32-group
+            dead |= set(range(32 * (rows // 32), rows))
+        return sorted(dead), none, none, none
+    if pattern == "dead_cols":
+        assert cols >= 12
+        block = 8 * (1 if cols >= 16 else 0)                               # one aligned block of 8: a whole chunk of the plain walk
+        single = block + 12 if block + 13 < cols else block + 10           # live neighbours on both sides, not the last column
+        dead = {single} | set(range(block, block + 8))
+        if cols % 8 == 1:
+            dead.add(cols - 1)                                             # the only plane of the last chunk
+        return none, sorted(dead), none, none
+    if pattern == "unused_source":
+        assert col_range is not None and 0 <= col_range[0] < col_range[1] <= cols, "unused_source: the caller passes the column range"
+        return none, list(range(col_range[0], col_range[1])), none, none
+    if pattern == "heavy_rows":
+        return [r for r in range(rows) if r % 8], none, list(range(0, rows, 8)), none
+    if pattern == "heavy_cols":
+        return none, [c for c in range(cols) if c % 8], none, list(range(0, cols, 8))
+    if pattern == "one_heavy_row":
+        return none, none, [rows // 2], none
+    if pattern == "one_heavy_col":
+        return none, none, none, [cols // 2]
+    if pattern == "dense_group":
+        return none, none, list(range(min(32, rows))), none
+    if pattern == "all_dead":
+        return list(range(rows)), list(range(cols)), none, none
+    raise ValueError("unknown pattern %r" % (pattern,))
+
+
+def structured_kmask(rows, cols, pattern, seed, density=0.25, col_range=None):
+    """A deterministic uint8 [rows, cols] kernel map of the kind training leaves behind (kernel_death empties whole filters, growth
+    refills elsewhere), where an i.i.d. map of the tests' sizes practically never holds such shapes:
+      dead_rows      i.i.d. `density`, with one row in the middle of a quad, one aligned quad and the ragged last 32-group all dead
+      dead_cols      i.i.d. `density`, with one column, one aligned block of 8 and (cols % 8 == 1) the last column all dead
+      unused_source  i.i.d. `density`, with columns col_range[0] .. col_range[1] - 1 (one source of a concat) all dead
+      heavy_rows     rows r % 8 == 0 fully live, everything else dead (density 0.125, no i.i.d. base); heavy_cols: its transpose
+      one_heavy_row  i.i.d. 0.02 plus one fully live row; one_heavy_col: its transpose
+      dense_group    rows 0..31 fully live, the rest i.i.d. 0.02
+      all_dead       zeros
+    Every pattern asserts its defining property on the map it returns."""
+    g = torch.Generator().manual_seed(seed)
+    dead_r, dead_c, heavy_r, heavy_c = structured_kmask_parts(rows, cols, pattern, col_range)
+    base = 0.02 if pattern in ("one_heavy_row", "one_heavy_col", "dense_group") else density
+    km = (torch.rand((rows, cols), generator=g) < base).to(torch.uint8)
+    if pattern in ("heavy_rows", "heavy_cols", "all_dead"):
+        km.zero_()
+    km[heavy_r, :] = 1
+    km[:, heavy_c] = 1
+    km[dead_r, :] = 0
+    km[:, dead_c] = 0
+    # ---- the defining properties
+    assert km.shape == (rows, cols) and km.dtype == torch.uint8 and int(km.max()) <= 1
+    assert int(km[dead_r].sum()) == 0 and int(km[:, dead_c].sum()) == 0
+    assert int(km[heavy_r].sum()) == len(heavy_r) * cols and int(km[:, heavy_c].sum()) == len(heavy_c) * rows
+    if pattern == "dead_rows":
+        assert any(r % 4 == 1 and r - 1 not in dead_r for r in dead_r), "a dead row inside a live quad"
+        assert any(r % 4 == 0 and all(r + i in dead_r for i in range(4)) for r in dead_r), "an aligned dead quad"
+        assert rows % 32 == 0 or rows < 32 or all(r in dead_r for r in range(32 * (rows // 32), rows)), "the ragged last group"
+        assert int(km.sum()) > 0
+    elif pattern == "dead_cols":
+        assert any(c % 8 == 0 and all(c + i in dead_c for i in range(8)) for c in dead_c), "an aligned dead block of 8 planes"
+        assert any(c - 1 not in dead_c and c + 1 not in dead_c for c in dead_c), "a single dead column"
+        assert cols % 8 != 1 or cols - 1 in dead_c
+        assert int(km.sum()) > 0
+    elif pattern == "unused_source":
+        assert int(km.sum()) > 0
+    elif pattern in ("heavy_rows", "heavy_cols"):
+        assert int(km.sum()) == (len(heavy_r) * cols if heavy_r else len(heavy_c) * rows)
+        assert len(heavy_r) + len(heavy_c) == -(-(rows if heavy_r else cols) // 8)              # density 0.125 where 8 divides the size
+    elif pattern in ("one_heavy_row", "one_heavy_col"):
+        n = cols if heavy_r else rows
+        assert int(km.sum()) - n <= 0.05 * rows * cols, "the base is sparse: the one row carries many times the mean"
+    elif pattern == "dense_group":
+        assert int(km[:32].sum()) == min(32, rows) * cols
+    elif pattern == "all_dead":
+        assert int(km.sum()) == 0
+    return km

@@ -9,7 +9,7 @@ import pytest
 import torch
 from torch import nn
 
-from tests.helpers import golden
+from tests.helpers import golden, structured_kmask, STRUCTURED_PATTERNS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -594,16 +594,17 @@ def test_dataloader3d_batches_equal_the_reference(tmp_path, tag, mode, kw):
     assert np.array_equal(np.random.randint(0, 2 ** 31 - 1, 4), g[tag + "_rng_after"])
 
 
-@pytest.mark.parametrize("R,Cc,dens", [(32, 64, 0.2), (64, 160, 0.2), (34, 33, 0.3), (128, 320, 0.1), (70, 90, 0.5)])
-def test_sparse_plan_is_a_valid_balanced_permutation(R, Cc, dens):
-    """e2e_conv133_sparse_plan (host side of the load-balanced DSFF conv, csrc/conv133_sparse.hip): for both directions the plan
-    places every output plane in exactly one wave slot of its 32-plane group and every input plane in exactly one chunk slot (the
-    same chunking for every group), its liveness words are the kernel map read through those slots (mask indices stay bit exact), it is a pure
-    function of the map, and the work of the slowest wave summed over the chunks is close to the mean (the point of the plan)."""
+def _sparse_plan_checks(km, iid_density):
+    """What holds of e2e_conv133_sparse_plan for ANY kernel map (permutation, liveness words, packed-block offsets, planned <= natural
+    cost, 1 <= flush <= chunks, purity), and for i.i.d. maps (iid_density not None) the balance.  Returns per direction
+    (forward, data gradient) a dict with kmax, flush, nchunks and `chain`: the longest run of products (9 per live kernel) that any
+    output plane adds into its chunk accumulators between two flushes, from pslot and the map."""
     import ctypes as C
     from e2enet_medical_amd._lib import lib
     L = lib()
-    km = (np.random.RandomState(R * 1000 + Cc).rand(R, Cc) < dens).astype(np.uint8)
+    R, Cc = km.shape
+    dens = iid_density
+    found = []
 
     def plan(tr):
         Q, P = (Cc, R) if tr else (R, Cc)
@@ -619,9 +620,9 @@ def test_sparse_plan_is_a_valid_balanced_permutation(R, Cc, dens):
         assert np.array_equal(wo.reshape(G, NC, 8), want.transpose(0, 2, 1))
         assert kmx.value == max(1, int(pc.sum(axis=1).max()))
         assert L.conv133_sparse_wpk_floats(P, Q, kmx.value) == G * NC * kmx.value * 12
-        return Q, P, G, NC, qs, ps, qd, fl.value
+        return Q, P, G, NC, qs, ps, qd, fl.value, kmx.value
     for tr in (0, 1):
-        Q, P, G, NC, qs, ps, qd, flush = plan(tr)
+        Q, P, G, NC, qs, ps, qd, flush, _ = plan(tr)
         again = plan(tr)
         assert all(np.array_equal(a, b) for a, b in zip((qs, ps, qd), again[4:7])) and flush == again[7]
         assert 1 <= flush <= NC
@@ -653,8 +654,49 @@ def test_sparse_plan_is_a_valid_balanced_permutation(R, Cc, dens):
         assert planned <= natural + 1e-6
         for g in range(1, G):                                        # ONE chunking of the input planes for all groups of a layer
             assert np.array_equal(ps[:NC * 8], ps[g * NC * 8:(g + 1) * NC * 8])           # (they share the staged planes through L2)
-        if Q % 32 == 0 and dens <= 0.3:
+        if dens is not None and Q % 32 == 0 and dens <= 0.3:
             assert natural / ideal >= 1.3 and (planned / ideal <= 1.2 if G == 1 else planned <= 0.87 * natural), (planned / ideal, natural / ideal)
+        chunk_live = np.zeros((Q, NC), np.int64)                     # live kernels of output plane q in chunk c (one chunking for all groups)
+        p0 = ps[:NC * 8].reshape(NC, 8)
+        for c in range(NC):
+            chunk_live[:, c] = alive[:, p0[c][p0[c] >= 0]].sum(axis=1)
+
+        def longest_chain(f):                                        # products between two flushes, the heaviest plane's
+            return max(int(chunk_live[:, c0:c0 + f].sum(axis=1).max()) for c0 in range(0, NC, f)) * 9
+        chain, one_chunk = longest_chain(flush), longest_chain(1)
+        # the flush interval is the longest that keeps the heaviest plane's chain within 36 products (or within its heaviest chunk)
+        assert chain <= max(36, one_chunk), (chain, one_chunk, flush)
+        assert all(longest_chain(f) > max(36, one_chunk) for f in range(flush + 1, NC + 1)), (flush, one_chunk)
+        found.append(dict(kmax=again[8], flush=flush, nchunks=NC, chain=chain))
+    return found
+
+
+STRUCTURED_PLAN_SHAPES = [(64, 160), (72, 64), (34, 33), (40, 33)]
+
+
+@pytest.mark.parametrize("R,Cc,dens", [(32, 64, 0.2), (64, 160, 0.2), (34, 33, 0.3), (128, 320, 0.1), (70, 90, 0.5)] +
+                         [(r, c, pat) for r, c in STRUCTURED_PLAN_SHAPES for pat in STRUCTURED_PATTERNS])
+def test_sparse_plan_is_a_valid_balanced_permutation(R, Cc, dens):
+    """e2e_conv133_sparse_plan (host side of the load-balanced DSFF conv, csrc/conv133_sparse.hip): for both directions the plan
+    places every output plane in exactly one wave slot of its 32-plane group and every input plane in exactly one chunk slot (the
+    same chunking for every group), its liveness words are the kernel map read through those slots (mask indices stay bit exact), it is a pure
+    function of the map, and the work of the slowest wave summed over the chunks is close to the mean (the point of the plan).
+    `dens` a number: an i.i.d. map of that density.  `dens` a pattern of helpers.structured_kmask: maps with dead and overloaded
+    rows and columns, on which everything but the balance ratio must hold as well, and the limits of the plan's geometry: a fully
+    live 32-plane group fills a chunk's block (kmax = 256), an empty map keeps one (empty) slot and never flushes early."""
+    if isinstance(dens, str):
+        km = structured_kmask(R, Cc, dens, seed=R * 1000 + Cc, col_range=(Cc - 13, Cc)).numpy()
+        fwd, bwd = _sparse_plan_checks(km, None)
+        print("sparse plan %dx%d %s: forward %s, data gradient %s" % (R, Cc, dens, fwd, bwd))
+        if dens == "dense_group":
+            assert fwd["kmax"] == 256                               # 32 output planes x 8 input planes, all live
+        if dens == "all_dead":
+            assert fwd["kmax"] == 1 and bwd["kmax"] == 1
+            assert fwd["flush"] == fwd["nchunks"] and bwd["flush"] == bwd["nchunks"]
+            assert fwd["chain"] == 0 and bwd["chain"] == 0
+        return
+    km = (np.random.RandomState(R * 1000 + Cc).rand(R, Cc) < dens).astype(np.uint8)
+    _sparse_plan_checks(km, dens)
 
 
 def test_trainer_never_trains_on_noise_by_accident_and_splits_like_sklearn(tmp_path):
